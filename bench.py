@@ -1,7 +1,13 @@
 """Headline benchmark: images/sec of full training steps (forward, seven per-key losses, per-key
 gradients, TF-Adam, gradient all-reduce) of the part-discovery model on synthetic 128x128 batches.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the result line.  ``--full`` adds what the headline does not need:
+the CPU baseline leg (BASELINE config #1 on the torch-CPU restatement of the reference step, ``cpu_baseline`` in the line;
+``--no-cpu-baseline`` drops it again).  ``--dump-outputs DIR`` writes, after the timed steps, what the last timed step computed
+(rank 0): its per-key losses (``loss_<key>.npy``, float64 [1]) and a fixed, seeded sample of every optimizer key's updated fp32
+master weights (``params_<key>.npy``, float32), so that two builds run with the same arguments can be compared output for output.
 
 N > 1 works both ways the driver may start it:
   * ``python bench.py --gpus N``: this process is only a launcher -- it never touches the GPU, starts N rank
@@ -54,7 +60,10 @@ def parse_args():
                     help="what the perceptual trunk sees (the three readings of edflow VGG19Features(original_scale=True), "
                          "model.py:610-612, UNVERIFIED): the images as they are (headline) | bilinear to 256x256 | then one random "
                          "224x224 window per step.  The extra trunk work is counted in train_gflop_per_image.")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true", help="also run the measurements beyond the headline (the CPU baseline leg)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write the last timed step's losses and a seeded sample of the updated weights to DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline leg")
     ap.add_argument("--cpu-batch", type=int, default=8, help="BASELINE config #1: batch 8")
     ap.add_argument("--cpu-threads", type=int, default=0, help="0 = min(os.cpu_count(), {})".format(CPU_THREAD_CAP))
     ap.add_argument("--cpu-budget", type=float, default=45.0, help="seconds of timed CPU work (at least 2 steps are timed)")
@@ -159,6 +168,26 @@ def cpu_baseline(parts, batch, threads, budget_s):
                       "{:.2f} s/step".format(steps, batch, parts, threads, CPU_THREAD_CAP, dt, dt / steps)}
 
 
+DUMP_PARAM_SAMPLE = 1 << 18        # weights per optimizer key in --dump-outputs (7 keys: 7 MiB of float32 at most)
+
+
+def dump_outputs(out_dir, trainer, losses):
+    """--dump-outputs: the per-key losses train_step returned for the last timed step, and the same fixed, seeded positions of every
+    optimizer key's flat fp32 master weights after it (all of them where a key has fewer)."""
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    for k, v in sorted(dict(losses).items()):
+        np.save(os.path.join(out_dir, "loss_{}.npy".format(k)), np.array([float(v)], dtype=np.float64))
+    for k, g in trainer.model.bank.groups.items():
+        p = g["flat"]["p"]
+        n = int(p.numel())
+        if n > DUMP_PARAM_SAMPLE:
+            idx = np.sort(np.random.default_rng(0).choice(n, DUMP_PARAM_SAMPLE, replace=False))
+            p = p[torch.from_numpy(idx).to(p.device)]
+        np.save(os.path.join(out_dir, "params_{}.npy".format(k)), p.detach().float().cpu().numpy())
+
+
 def run_rank(args):
     import torch
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -211,8 +240,10 @@ def run_rank(args):
     torch.cuda.synchronize()
     ops.KernelTimer.enabled = True
     t0 = time.perf_counter()
+    losses = None
     for _ in range(args.steps):
-        trainer.train_step(batch)
+        losses = None                  # (a step's lazily read losses are not held across the next step)
+        losses = trainer.train_step(batch)
     if world > 1:
         torch.distributed.barrier()
     torch.cuda.synchronize()
@@ -223,6 +254,8 @@ def run_rank(args):
         torch.distributed.all_reduce(tmax, op=torch.distributed.ReduceOp.MAX)
     dt = float(tmax)
     rccl_world = torch.distributed.get_world_size() if world > 1 else 1
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, trainer, losses)
 
     if rank == 0:
         images = args.batch * world * args.steps
@@ -303,7 +336,7 @@ def run_rank(args):
             out["dp_wait_ms"] = dpw
         if not ops.KernelTimer.events:
             out["roofline"]["note"] = "no launch timed: under HIP-graph replay (hip_graph / UPS_GRAPH=1) the roofline launches are graph nodes"
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             threads = args.cpu_threads or min(os.cpu_count() or 1, CPU_THREAD_CAP)
             if args.config == "cub128p10":      # the CPU leg is BASELINE config #1 (the CUB yaml at batch 8)
                 out["cpu_baseline"] = cpu_baseline(args.parts, args.cpu_batch, threads, args.cpu_budget)

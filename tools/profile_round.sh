@@ -117,7 +117,7 @@ for cf in deepfashion256p16 pennaction128 cub256p20; do python3 bench.py --no-cp
 python3 bench.py --no-cpu-baseline --config cub256p20 --precision bf16 2>/dev/null | grep '"metric"' > $O/${TAG}_bench_cub256p20_bf16.json
 # round 5: the un-profiled headline line (with the CPU baseline leg), the fp32 line, and the fp8 weight gradient of the roofline layer
 # (SQ counters, HBM traffic, isolated timings against the bf16 kernel)
-python3 bench.py --steps 20 --warmup 5 2>/dev/null | grep '"metric"' > $O/${TAG}_final_bench_b64.json
+python3 bench.py --full --steps 20 --warmup 5 2>/dev/null | grep '"metric"' > $O/${TAG}_final_bench_b64.json
 python3 bench.py --precision fp32 --steps 5 --warmup 2 --no-cpu-baseline 2>/dev/null | grep '"metric"' > $O/${TAG}_bench_b64_fp32.json
 bash tools/pmc_conv.sh ${TAG}_sq8_wgrad wgrad dv_rb128 f8 > /dev/null 2>&1
 (echo "== wgrad, fp8 kernel (conv_wgrad3x3_f8.hip): e5m2 copy of the gradient in, fp16 forward tensor quantised while staged"; cat $R/gpurun_out/pmc_${TAG}_sq8_wgrad.txt) > $O/${TAG}_sq_wgrad_dv_rb128_fp8.txt 2>/dev/null

@@ -8,7 +8,7 @@ TAG=${1:-round4}
 cd $R
 O=$R/gpurun_out/profiles_$TAG
 rm -rf $O; mkdir -p $O
-python3 bench.py --steps 20 --warmup 5 2>/dev/null | grep '"metric"' > $O/${TAG}_final_bench_b64.json
+python3 bench.py --full --steps 20 --warmup 5 2>/dev/null | grep '"metric"' > $O/${TAG}_final_bench_b64.json
 python3 bench.py --no-cpu-baseline --precision fp8 2>/dev/null | grep '"metric"' > $O/${TAG}_final_bench_b64_fp8.json
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -- python3 bench.py --no-cpu-baseline > $O/bench.log 2>&1
 grep '"metric"' $O/bench.log > $O/${TAG}_bench_b64.json
