@@ -244,6 +244,36 @@ int ups_coord_wgrad(const float* gsum, int32_t hi, int32_t wi, int32_t ho, int32
 int ups_col_sum(const void* dout, int32_t dtype, int64_t rows, int32_t co, int32_t ldo,
                 float* out, float* workspace, void* stream);
 
+/* ---------------------------------------------------------------- weight-normalised transposed convolution
+ * upsample(x, nf, "conv_transposed") = deconv2d(x, nf, stride 2), 3x3, TF 'SAME' (N:818-822, 938-1039):
+ *     y[n, 2i+ky, 2j+kx, o] = b[o] + sum_c x~[n, i, j, c] * W[ky][kx][o][c],   W = g[o] * V / max(||V_o||, 1e-6)
+ * (taps landing on row / column 2H are dropped; x~ = x plus the two CoordConv channels in CoordConv scopes).  V [3,3,nf,cin_v] is
+ * the TF transpose layout [kh, kw, out, in], cin_v = ci_log (+2 with coordinates).
+ *
+ * ups_deconv_prep: once per weight version, from V and g: inv_norm [nf], the fp32 W [3,3,nf,cin_v] (w32), and optionally
+ *   w_fwd  forward operand [9][ceil(round8(ci_log)/BK)][nf][BK] of fwd_dtype (F32 / BF16 / F16; BK = 64 bytes / element) -- the
+ *          `w` of ups_deconv3x3_s2_fwd and of the per-class ups_conv_igemm launches (tap_w = 3 ky + kx);
+ *   w_dx   input-gradient operand [9][ceil(round8(nf)/BK)][ci_log][BK] of dx_dtype (F32 / BF16): the `w` of the stride-2 forward
+ *          convolution dx = conv2d(dy, W[.., :ci_log]) (ups_conv_igemm, taps (r, s) = (ky, kx));
+ *   ctab   CoordConv tables [4 classes 2 py + px][64][3][nf] in the ups_conv_desc.coord_tab layout of the class launches, whose taps are
+ *          r-major over the class's rows (py = 0: ky 0 / 2 from input rows i / i-1; py = 1: ky 1 from row i) and columns; hi x wi
+ *          is the INPUT size (add_coordinates runs at the input's resolution). */
+int ups_deconv_prep(const float* V, const float* g, int32_t nf, int32_t cin_v, int32_t ci_log, int32_t fwd_dtype, void* w_fwd,
+                    int32_t dx_dtype, void* w_dx, float* w32, float* inv_norm, float* ctab, int32_t hi, int32_t wi, void* stream);
+/* One-launch forward on the 16-bit MFMA: x [n,h,w,ldi] (BF16 or F16), ci = round8(ci_log) channels reduced, y [n,2h,2w,ldo] with
+ * channels [nf, ldo) written as zero; bias [nf] (or NULL), ctab = ups_deconv_prep's tables (or NULL).  UPS_E_UNSUPPORTED (nothing
+ * launched) unless w % 16 == 0, ci <= 256 and nf <= 256: the caller then runs the four per-class ups_conv_igemm launches. */
+int ups_deconv3x3_s2_fwd(const void* x, int32_t dtype, int32_t n, int32_t h, int32_t w, int32_t ci, int32_t ldi, const void* w_fwd,
+                         const float* bias, const float* ctab, int32_t nf, int32_t ldo, void* y, void* stream);
+/* From dy [n,2h,2w,ldo] (F32 / BF16): db[o] = sum dy and, with coords, dwc [9][nf][2] = the gradient of W's two coordinate columns
+ * (sum over the lattice points a tap reaches of dy * coordinate).  part: splits * 19 * nf floats of scratch (deterministic). */
+int ups_deconv_bias_coord_grad(const void* dy, int32_t dtype, int32_t n, int32_t h, int32_t w, int32_t nf, int32_t ldo, int32_t coords,
+                               float* db, float* dwc, float* part, int32_t splits, void* stream);
+/* dW -> dV [3,3,nf,cin_v], dg [nf] through the normalisation: dg = <Vhat_o, dW_o>, dV = (g / ||V_o||) (dW_o - Vhat_o dg_o).
+ * dW arrives as dwx [9][nf][ci_log] (columns of x) and dwc [9][nf][2] (coordinate columns; NULL when cin_v == ci_log). */
+int ups_deconv_wn_bwd(const float* V, const float* g, const float* dwx, const float* dwc, int32_t nf, int32_t cin_v, int32_t ci_log,
+                      float* dV, float* dg, void* stream);
+
 /* ---------------------------------------------------------------- resampling / pooling
  * Legacy TF-1 bilinear x2 (N:834-847, tf.image.resize_images BILINEAR, no half-pixel centres). */
 int ups_bilinear2x_fwd(const void* x, void* y, int32_t dtype, int32_t n, int32_t h, int32_t w, int32_t c, void* stream);
@@ -478,7 +508,7 @@ int ups_gauss_hm(const float* pts, const float* stddev, float* out, int32_t B, i
 int ups_gauss_hm3(const float* mu, const float* L, float* out, int32_t B, int32_t h, int32_t w, int32_t K, void* stream);
 
 /* ---------------------------------------------------------------- misc
- * dtype conversion of a flat buffer (fp32 <-> bf16) */
+ * dtype conversion of a flat buffer (fp32 <-> bf16, fp32 <-> fp16, fp16 -> bf16) */
 int ups_convert(const void* src, int32_t src_dtype, void* dst, int32_t dst_dtype, int64_t count, void* stream);
 /* dst[row][0..c) = src[row][0..c) (fp32 -> dtype), dst[row][c..ldd) = 0 */
 int ups_pad_convert(const float* src, int32_t c, void* dst, int32_t dtype, int32_t ldd, int64_t rows, void* stream);

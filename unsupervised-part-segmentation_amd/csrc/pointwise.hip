@@ -801,6 +801,8 @@ extern "C" int ups_convert(const void* src, int32_t sd, void* dst, int32_t dd, i
     else if (sd == UPS_F32 && dd == UPS_F16) hipLaunchKernelGGL((convert_kernel<float, f16>), dim3(grid), dim3(256), 0, s, (const float*)src, (f16*)dst, (long long)count);
     else if (sd == UPS_F16 && dd == UPS_F32) hipLaunchKernelGGL((convert_kernel<f16, float>), dim3(grid), dim3(256), 0, s, (const f16*)src, (float*)dst, (long long)count);
     else if (sd == UPS_BF16 && dd == UPS_BF16) hipLaunchKernelGGL((convert_kernel<bf16, bf16>), dim3(grid), dim3(256), 0, s, (const bf16*)src, (bf16*)dst, (long long)count);
+    // (an fp16 forward input of a deconvolution, staged as the bf16 output gradient of its swapped-role weight gradient)
+    else if (sd == UPS_F16 && dd == UPS_BF16) hipLaunchKernelGGL((convert_kernel<f16, bf16>), dim3(grid), dim3(256), 0, s, (const f16*)src, (bf16*)dst, (long long)count);
     else { ups_set_error("ups_convert: bad dtypes"); return UPS_E_ARG; }
     UPS_LAUNCH_CHECK();
     return UPS_OK;

@@ -97,6 +97,10 @@ _SIGS = {
     "ups_batch_sum": ([_P, _I, _I, _L, _I, _I, _P, _P], C.c_int),
     "ups_coord_wgrad": ([_P, _I, _I, _I, _I, _I, _I, _I, C.POINTER(_I), C.POINTER(_I), _I, _I, _F, _F, _I, _P, _P, _P, _P], C.c_int),
     "ups_col_sum": ([_P, _I, _L, _I, _I, _P, _P, _P], C.c_int),
+    "ups_deconv_prep": ([_P, _P, _I, _I, _I, _I, _P, _I, _P, _P, _P, _P, _I, _I, _P], C.c_int),
+    "ups_deconv3x3_s2_fwd": ([_P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _I, _I, _P, _P], C.c_int),
+    "ups_deconv_bias_coord_grad": ([_P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _I, _P], C.c_int),
+    "ups_deconv_wn_bwd": ([_P, _P, _P, _P, _I, _I, _I, _P, _P, _P], C.c_int),
     "ups_bilinear2x_fwd": ([_P, _P, _I, _I, _I, _I, _I, _P], C.c_int),
     "ups_bilinear2x_bwd": ([_P, _P, _I, _I, _I, _I, _I, _P], C.c_int),
     "ups_depth_to_space": ([_P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P], C.c_int),

@@ -48,10 +48,22 @@ def uniform_init(seed, name, shape, bound):
     return ((2.0 * u - 1.0) * bound).to(torch.float32)
 
 
+def init_variable(seed, name, shape, bound, kind="uniform"):
+    """One variable's initial value by init kind: "uniform" (conv2d, above), "normal" (N(0, bound^2): deconv2d's V, nn.py:968-975),
+    "ones" / "zeros" (its g / b); deterministic per variable name."""
+    if kind == "uniform":
+        return uniform_init(seed, name, shape, bound)
+    if kind == "normal":
+        return (torch.randn(shape, generator=_rng(seed, name), dtype=torch.float64) * bound).to(torch.float32)
+    if kind in ("ones", "zeros"):
+        return (torch.ones if kind == "ones" else torch.zeros)(shape, dtype=torch.float32)
+    raise ValueError("init kind '{}' (uniform | normal | ones | zeros)".format(kind))
+
+
 class ParamBank(object):
     """All trainable variables, grouped per optimizer key into flat fp32 buffers
     (params / grads / Adam m / Adam v) so that the optimizer and the DP all-reduce touch one
-    contiguous range per sub-network.  ``specs``: name -> (shape, bound)."""
+    contiguous range per sub-network.  ``specs``: name -> (shape, bound) or (shape, bound, init kind) (init_variable)."""
 
     def __init__(self, specs, device, seed=0, keys=SUBMODULES):
         self.specs = specs
@@ -77,8 +89,8 @@ class ParamBank(object):
 
     @torch.no_grad()
     def initialize(self, seed):
-        for n, (shape, bound) in self.specs.items():
-            self.params[n].copy_(uniform_init(seed, n, shape, bound))
+        for n, spec in self.specs.items():
+            self.params[n].copy_(init_variable(seed, n, *spec))
         ops.WeightVersion.value += 1
 
     @torch.no_grad()
@@ -116,6 +128,7 @@ class Scope(object):
         self.owner, self.prefix, self.coords = owner, prefix, coords
         self.act = L.ACT[activation]
         self.counter = 0
+        self.dcounter = 0            # deconv2d_k: a counter of its own (nn.py get_name, 40-46)
         self.fmt = fmt               # L.F16: every tensor of this scope's forward pass is fp16 (the mask decoder)
 
     def _layer(self, cin, cout, k, stride, act_in, in_post=False, out_act=L.ACT_NONE):
@@ -217,9 +230,41 @@ class Scope(object):
         f8, ops.Fp8.last_out = ops.Fp8.last_out, None
         return Act(t, x.n, 2 * x.h, 2 * x.w, x.c, f8=f8)
 
+    def _deconv_layer(self, cin, nf):
+        name = "{}/deconv2d_{}".format(self.prefix, self.dcounter)
+        self.dcounter += 1
+        own = self.owner
+        if own.dry:
+            # nn.py:956-978 (init=False branch): V [3,3,nf,Cin(+2)] ~ N(0, 0.05), g = 1, b = 0
+            own.specs[name + "/V"] = ((3, 3, nf, cin + (2 if self.coords else 0)), 0.05, "normal")
+            own.specs[name + "/g"] = ((nf,), 1.0, "ones")
+            own.specs[name + "/b"] = ((nf,), 0.0, "zeros")
+            return None
+        lay = own.layers.get((name,))
+        if lay is None:
+            P, G = own.bank.params, own.bank.grads
+            lay = ops.DeconvLayer(name, P[name + "/V"], P[name + "/g"], P[name + "/b"], self.coords)
+            lay.grad_V, lay.grad_g, lay.grad_b = G[name + "/V"], G[name + "/g"], G[name + "/b"]
+            lay.registry = own.prep
+            lay.f16 = self.fmt == L.F16
+            own.layers[(name,)] = lay
+        return lay
+
+    def deconv2d(self, x, nf):
+        """nn.deconv2d(x, nf, stride 2) (nn.py:938-1039): 3x3, 'SAME', weight-normalised, CoordConv channels in CoordConv scopes, no
+        activation.  Its tensors stay 16-bit in precision fp8 (no fp8 copy is handed on)."""
+        if x.post:
+            raise L.UpsError("{}: up-sampling of a post-activation tensor".format(self.prefix))
+        lay = self._deconv_layer(x.c, nf)
+        if lay is None:
+            return Act(None, x.n, 2 * x.h, 2 * x.w, nf, fmt=self.fmt)
+        assert x.fmt == self.fmt, "tensor format does not match the scope's"
+        return Act(ops.deconv(x.t, lay, fmt=self.fmt), x.n, 2 * x.h, 2 * x.w, nf, fmt=self.fmt)
+
     def upsample(self, x, num_units, method="subpixel", post=False):
         """nn.upsample (nn.py:820-849): "linear" (ignores num_units), "subpixel" (conv2d to 4 * num_units + depth_to_space),
-        "nearest_neighbor".  ("conv_transposed" -- the weight-normalised deconv2d of nn.py:938-1039 -- is not built.)"""
+        "nearest_neighbor", "conv_transposed" (the weight-normalised deconv2d, nn.py:938-1039).  Only "linear" stores its
+        output post-activation; the others return the plain form."""
         if method == "linear":
             return self.upsample_linear(x, post=post)
         if x.post:
@@ -233,7 +278,9 @@ class Scope(object):
             if x.t is None:
                 return Act(None, x.n, 2 * x.h, 2 * x.w, x.c, fmt=self.fmt)
             return Act(ops.Nearest2xFn.apply(x.t, self.fmt), x.n, 2 * x.h, 2 * x.w, x.c, fmt=self.fmt)
-        raise NotImplementedError("upsample method '{}' (linear | subpixel | nearest_neighbor)".format(method))
+        if method == "conv_transposed":
+            return self.deconv2d(x, num_units)
+        raise NotImplementedError("upsample method '{}' (linear | subpixel | nearest_neighbor | conv_transposed)".format(method))
 
     def act_mean(self, x):
         assert self.fmt is None, "act_mean has no fp16 form"

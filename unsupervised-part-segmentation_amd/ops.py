@@ -1015,6 +1015,224 @@ def conv(x, layer, res=None, res_self=False, out_f32=False, ldo=None, mask=None,
     return ConvFn.apply(x, layer.V, layer.b, None, layer, 0, out_f32, ldo, mask[0], mask[1], mask[2].contiguous(), None, False)
 
 
+# ---------------------------------------------------------------------------------------------------------------------------------
+# upsample(x, nf, "conv_transposed"): weight-normalised deconv2d, 3x3 / stride 2 / 'SAME' (nn.py:818-822, 938-1039; csrc/deconv3x3_s2.hip)
+DECONV_ONE_LAUNCH = True        # False: the forward as four per-class ups_conv_igemm launches (tools/bench_deconv.py, parity tests)
+# the four output parity classes: taps (k, source offset) of an even / odd output row (or column) -- r-major in the class launches
+_DECONV_TAPS = {0: ((0, 0), (2, -1)), 1: ((1, 0),)}
+
+
+class DeconvLayer(object):
+    """One deconv2d variable triple: V [3,3,nf,Cin(+2)] (TF transpose layout [kh, kw, out, in]), g [nf], b [nf].  The layer is
+    the input gradient of a stride-2 3x3 convolution with forward weights W = g * l2_normalize(V): its forward is four parity
+    classes of taps, dx a stride-2 forward convolution of dy with W, dW a stride-2 weight gradient with the two tensors' roles
+    swapped.  W's operands are made by ups_deconv_prep once per weight version (registered with the model's PrepRegistry like
+    ConvLayer.prepared_d2s, so that a captured step re-makes them behind Adam)."""
+
+    def __init__(self, name, V, g, b, coords):
+        self.name, self.V, self.g, self.b, self.coords = name, V, g, b, coords
+        self.co = V.shape[2]
+        self.cin_v = V.shape[3]
+        self.ci_log = self.cin_v - (2 if coords else 0)
+        self.grad_V = self.grad_g = self.grad_b = None     # optional views into the flat gradient bucket
+        self.registry = None
+        self.frozen = False
+        self.f16 = False
+        self.after_wgrad = None
+        self._cache = {}
+
+    _mark_ready = ConvLayer._mark_ready
+    _wait_ready = ConvLayer._wait_ready
+    _wait_master = ConvLayer._wait_master
+
+    def prepared(self, fwd_code, dx_code, hi, wi):
+        """W's operands for an hi x wi input: forward (fwd_code), input gradient (dx_code), fp32 W, 1 / ||V_o||, CoordConv tables."""
+        key = ("deconv", fwd_code, dx_code, hi, wi)
+        ent = self._cache.get(key)
+        dev = self.V.device
+        if ent is None:
+            bkf, bkd = (16 if fwd_code == L.F32 else 32), (16 if dx_code == L.F32 else 32)
+            ent = {"version": -1,
+                   "w_fwd": torch.empty((9, -(-round8(self.ci_log) // bkf), self.co, bkf), dtype=L.torch_dtype(fwd_code), device=dev),
+                   "w_dx": torch.empty((9, -(-round8(self.co) // bkd), self.ci_log, bkd), dtype=L.torch_dtype(dx_code), device=dev),
+                   "w32": torch.empty_like(self.V), "inv": torch.empty((self.co,), dtype=torch.float32, device=dev),
+                   "ctab": torch.empty((4, 64, 3, self.co), dtype=torch.float32, device=dev) if self.coords else None}
+
+            def prep():
+                self._wait_master()
+                L.call("ups_deconv_prep", L.ptr(self.V), L.ptr(self.g), self.co, self.cin_v, self.ci_log, fwd_code, L.ptr(ent["w_fwd"]),
+                       dx_code, L.ptr(ent["w_dx"]), L.ptr(ent["w32"]), L.ptr(ent["inv"]), L.ptr(ent["ctab"]), hi, wi, L.stream())
+                ent["version"] = WeightVersion.value
+            ent["prep"] = prep
+            self._cache[key] = ent
+            if self.registry is not None and not self.frozen:
+                self.registry.extra.append(prep)
+        if ent["version"] != WeightVersion.value and not (self.frozen and ent["version"] >= 0):
+            ent["prep"]()
+            self._mark_ready(ent)
+        else:
+            self._wait_ready(ent)
+        return ent
+
+
+def _dx_code(x):
+    return L.F32 if x.dtype == torch.float32 else L.BF16
+
+
+def deconv_forward(x, layer, fmt=None, one_launch=None):
+    """y [n, 2hi, 2wi, round8(nf)] = deconv(x (+coords), W) + b; x [n, hi, wi, ldi].  fmt = L.F16: x and y hold fp16 (bf16 containers).
+    16-bit tensors go to the one-launch kernel (ups_deconv3x3_s2_fwd) where it takes the shape, everything else to four per-class
+    launches of the convolution engine (the per-class input-gradient launches of conv_dgrad, fed with W, bias and class tables)."""
+    n, hi, wi, ldi = x.shape
+    fcode = L.dt(x) if fmt is None else fmt
+    assert fcode != L.F16 or x.dtype == torch.bfloat16
+    ent = layer.prepared(fcode, _dx_code(x), hi, wi)
+    nf, ci, ldo = layer.co, round8(layer.ci_log), round8(layer.co)
+    assert ci <= ldi, (layer.name, layer.ci_log, ldi)
+    out = torch.empty((n, 2 * hi, 2 * wi, ldo), dtype=x.dtype, device=x.device)
+    ctab = ent["ctab"]
+    one_launch = DECONV_ONE_LAUNCH if one_launch is None else one_launch
+    if one_launch and fcode != L.F32:
+        rc = L.load().ups_deconv3x3_s2_fwd(L.ptr(x), fcode, n, hi, wi, ci, ldi, L.ptr(ent["w_fwd"]), L.ptr(layer.b), L.ptr(ctab),
+                                           nf, ldo, L.ptr(out), L.stream())
+        if rc == 0:
+            return out
+        if rc != -2:            # UPS_E_UNSUPPORTED: nothing launched, the shape goes to the class launches
+            L.check(rc, "ups_deconv3x3_s2_fwd")
+    for py in (0, 1):
+        for px in (0, 1):
+            dy, dx, tw = [], [], []
+            for ky, oy in _DECONV_TAPS[py]:
+                for kx, ox in _DECONV_TAPS[px]:
+                    dy.append(oy); dx.append(ox); tw.append(3 * ky + kx)
+            d = L.ConvDesc()
+            d.dtype = fcode
+            d.n, d.hi, d.wi, d.ci, d.ldi = n, hi, wi, ci, ldi
+            d.ho, d.wo, d.co, d.co_fill, d.ldo = hi, wi, nf, ldo, ldo
+            d.out_h, d.out_w, d.out_sy, d.out_sx, d.out_oy, d.out_ox = 2 * hi, 2 * wi, 2, 2, py, px
+            d.in_sy = d.in_sx = 1
+            _fill_taps(d, dy + [0] * 9, dx + [0] * 9, tw + [0] * 9, len(dy))
+            d.kh, d.kw = len(_DECONV_TAPS[py]), len(_DECONV_TAPS[px])
+            d.act_in, d.act_slope, d.out_f32, d.dact_kind = L.ACT_NONE, 0.2, 0, 0
+            d.ldr = d.ldd = 0
+            d.in_, d.w, d.out = x.data_ptr(), ent["w_fwd"].data_ptr(), out.data_ptr()
+            d.bias = layer.b.data_ptr()
+            d.coord_tab = ctab[2 * py + px].data_ptr() if ctab is not None else None
+            _attach_ws(d, x.device)
+            L.call("ups_conv_igemm", C.byref(d), L.stream())
+    return out
+
+
+def deconv_dgrad(g, x, layer, fmt=None):
+    """dx = conv2d(dy, W[.., :Cin], stride 2, 'SAME') -- a forward launch of the convolution engine (the stride-2 kernels where their
+    gates admit the shape).  g [n, 2hi, 2wi, ldg] in the gradient dtype."""
+    n, hi, wi, ldi = x.shape
+    ent = _deconv_ent(layer, x, fmt)
+    gx = torch.empty_like(x)
+    d = L.ConvDesc()
+    d.dtype = _dx_code(x)
+    d.n, d.hi, d.wi, d.ci, d.ldi = n, 2 * hi, 2 * wi, round8(layer.co), g.shape[-1]
+    d.ho, d.wo, d.co, d.co_fill, d.ldo = hi, wi, layer.ci_log, ldi, ldi
+    d.out_h, d.out_w, d.out_sy, d.out_sx, d.out_oy, d.out_ox = hi, wi, 1, 1, 0, 0
+    d.in_sy = d.in_sx = 2
+    _fill_taps(d, [t // 3 for t in range(9)], [t % 3 for t in range(9)], list(range(9)), 9)     # pad 0 before (even 2hi)
+    d.kh = d.kw = 3
+    d.act_in, d.act_slope, d.out_f32, d.dact_kind = L.ACT_NONE, 0.2, 0, 0
+    d.ldr = d.ldd = 0
+    d.in_, d.w, d.out = g.data_ptr(), ent["w_dx"].data_ptr(), gx.data_ptr()
+    d.bias, d.coord_tab, d.res, d.dact = None, None, None, None
+    _attach_ws(d, x.device)
+    assert round8(layer.co) <= g.shape[-1]
+    L.call("ups_conv_igemm", C.byref(d), L.stream())
+    return gx
+
+
+def _deconv_ent(layer, x, fmt):
+    """The entry the forward of this input used."""
+    ent = layer._cache.get(("deconv", L.dt(x) if fmt is None else fmt, _dx_code(x)) + tuple(x.shape[1:3]))
+    if ent is not None:
+        return ent
+    raise L.UpsError("{}: no prepared deconvolution weights for input {}".format(layer.name, tuple(x.shape)))
+
+
+def deconv_wgrad(g, x, layer, fmt=None):
+    """(dV, dg, db): dW[.., :Cin] from the stride-2 weight-gradient kernel with dy as the convolution's input and x as its output
+    gradient, dW's coordinate columns and db from ups_deconv_bias_coord_grad, then (dV, dg) through the normalisation."""
+    n, hi, wi, ldi = x.shape
+    dev = x.device
+    nf, ci_log = layer.co, layer.ci_log
+    gV = layer.grad_V if layer.grad_V is not None else torch.empty_like(layer.V)
+    gg = layer.grad_g if layer.grad_g is not None else torch.empty_like(layer.g)
+    gb = layer.grad_b if layer.grad_b is not None else torch.empty_like(layer.b)
+    if fmt == L.F16:            # fp16 forward input (bf16 container): the weight-gradient kernel stages its output gradient as bf16
+        xb = torch.empty_like(x)
+        L.call("ups_convert", L.ptr(x), L.F16, L.ptr(xb), L.BF16, x.numel(), L.stream())
+        x = xb
+    dwx = torch.empty((3, 3, nf, ci_log), dtype=torch.float32, device=dev)
+    d = L.WgradDesc()
+    d.dtype = _dx_code(x)
+    d.n, d.hi, d.wi, d.ci, d.ldi = n, 2 * hi, 2 * wi, round8(nf), g.shape[-1]
+    d.ci_log, d.cin_v = nf, nf
+    d.ho, d.wo, d.co, d.ldo = hi, wi, ci_log, ldi
+    d.in_sy = d.in_sx = 2
+    _fill_taps(d, [t // 3 for t in range(9)], [t % 3 for t in range(9)], list(range(9)), 9)
+    d.act_in, d.act_slope = L.ACT_NONE, 0.2
+    sk, wsb = C.c_int32(0), C.c_size_t(0)
+    scratch_b = torch.empty((ci_log,), dtype=torch.float32, device=dev)     # (the swapped form's "bias" gradient: unused)
+    d.in_, d.dout, d.grad, d.grad_bias = g.data_ptr(), x.data_ptr(), dwx.data_ptr(), scratch_b.data_ptr()
+    L.call("ups_conv_wgrad_plan", C.byref(d), C.byref(sk), C.byref(wsb))
+    ws = WORKSPACE.get(wsb.value, dev)
+    d.splitk, d.workspace = sk.value, ws.data_ptr()
+    L.call("ups_conv_wgrad", C.byref(d), L.stream())
+    splits = max(1, min(256, n * 2 * hi))
+    part = torch.empty((splits * 19 * nf,), dtype=torch.float32, device=dev)
+    dwc = torch.empty((3, 3, nf, 2), dtype=torch.float32, device=dev) if layer.coords else None
+    L.call("ups_deconv_bias_coord_grad", L.ptr(g), _dx_code(g), n, hi, wi, nf, g.shape[-1], int(layer.coords), L.ptr(gb), L.ptr(dwc),
+           L.ptr(part), splits, L.stream())
+    L.call("ups_deconv_wn_bwd", L.ptr(layer.V), L.ptr(layer.g), L.ptr(dwx), L.ptr(dwc), nf, layer.cin_v, ci_log, L.ptr(gV), L.ptr(gg),
+           L.stream())
+    return gV, gg, gb
+
+
+class DeconvFn(torch.autograd.Function):
+    """Autograd node of DeconvLayer: the weight gradients land in the layer's views of the flat gradient bucket, enqueued on the
+    weight-gradient side stream like ConvFn's (skip_wgrad passes leave them alone)."""
+
+    @staticmethod
+    def forward(ctx, x, V, g, b, layer, fmt=None):
+        x = x.contiguous()
+        out = deconv_forward(x, layer, fmt=fmt)
+        ctx.save_for_backward(x)
+        ctx.layer, ctx.fmt = layer, fmt
+        return out
+
+    @staticmethod
+    def backward(ctx, gy):
+        x, = ctx.saved_tensors
+        layer = ctx.layer
+        gy = to_act_dtype(gy, x.dtype, layer.co)
+        gx = gV = gg = gb = None
+        if any(ctx.needs_input_grad[1:4]) and not GradMode.skip_wgrad:
+            if Streams.enabled and layer.grad_V is not None and not Streams.on_aux(x.device):
+                cur = torch.cuda.current_stream(x.device)
+                side = Streams.get("wgrad", x.device)
+                side.wait_stream(cur)
+                with torch.cuda.stream(side):
+                    gV, gg, gb = deconv_wgrad(gy, x, layer, fmt=ctx.fmt)
+                Streams.keep(x.device, gy, x)
+            else:
+                gV, gg, gb = deconv_wgrad(gy, x, layer, fmt=ctx.fmt)
+            if layer.after_wgrad is not None:
+                layer.after_wgrad()
+        if ctx.needs_input_grad[0]:
+            gx = deconv_dgrad(gy, x, layer, fmt=ctx.fmt)
+        return gx, gV, gg, gb, None, None
+
+
+def deconv(x, layer, fmt=None):
+    return DeconvFn.apply(x, layer.V, layer.g, layer.b, layer, fmt)
+
+
 def masked_conv_eligible(dtype, size, n_parts):
     """The fused form runs on the bf16 3x3 / stride-1 patch kernels: 16-aligned images, at most 32 parts."""
     return dtype == torch.bfloat16 and size % 16 == 0 and size >= 16 and n_parts <= 32

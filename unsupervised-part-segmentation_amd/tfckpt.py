@@ -300,7 +300,7 @@ def to_trainer_state(bundle):
             m[name[:-5]] = arr
         elif name.endswith("/Adam_1"):
             v[name[:-7]] = arr
-        elif name.endswith("/V") or name.endswith("/b"):
+        elif name.endswith("/V") or name.endswith("/b") or (name.endswith("/g") and "/deconv2d_" in name):    # g: deconv2d's scale
             params[name] = arr
         else:
             other[name] = arr
