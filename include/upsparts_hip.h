@@ -340,6 +340,23 @@ int ups_l1_bwd(const void* a, const void* b, void* gb, int32_t dtype, int64_t ro
 /* out[0] (+)= scale * sum(partial[0..n)) */
 int ups_sum_scale(const float* partial, int32_t n, float scale, float* out, int32_t accumulate, void* stream);
 
+/* ---------------------------------------------------------------- Gram-matrix terms of the perceptual loss (csrc/gram.hip)
+ * edflow VGG19Features(default_gram=w) (UNVERIFIED): term = w * mean_{b,i,j} |G(F_t)[b] - G(F_g)[b]|, G(F)[b] = F[b]^T F[b] / (4 h w),
+ * F = act(map) as [n, h w, c] (c logical channels of an [n, h, w, ld] map, F32 or BF16; act NONE, RELU or LRELU with slope 0).
+ * The kernels see the unnormalised D_b = F_g[b]^T F_g[b] - F_t[b]^T F_t[b]; the caller applies 1 / (4 h w) and the mean over n c c.
+ *
+ * ups_gram_plan: out[0] = K splits, out[1] = partial floats (n * tile pairs), out[2] = workspace floats (0 without a split),
+ *   out[3] = sign bytes (n * cp * cp, cp = c rounded up to 32).
+ * ups_gram_l1_fwd: a = target, b = generated; partial[b, pair] = sum over the pair's 32x32 tile of |D| (off-diagonal tiles twice),
+ *   finished by ups_sum_scale; sign [n][cp][cp] int8 = sign(D) (symmetric, 0 outside [c, c]) for the backward.  Deterministic.
+ * ups_gram_l1_bwd: gb[b] += scale * scale_dev[0] * act'(b) * (act(b)[b] S_b) on channels [0, c) (ACCUMULATES into the L1 term's
+ *   gradient; channels [c, ld) untouched); scale_dev may be NULL. */
+int ups_gram_plan(int32_t n, int64_t hw, int32_t c, int32_t dtype, int64_t* out);
+int ups_gram_l1_fwd(const void* a, const void* b, int32_t dtype, int32_t n, int64_t hw, int32_t c, int32_t ld, int32_t act,
+                    float* partial, void* sign, float* workspace, void* stream);
+int ups_gram_l1_bwd(const void* b, const void* sign, void* gb, int32_t dtype, int32_t n, int64_t hw, int32_t c, int32_t ld,
+                    int32_t act, const float* scale_dev, float scale, void* stream);
+
 /* ---------------------------------------------------------------- part path
  * l = mean + eps (N:1427-1433); m = softmax_P(l) (N:58-62); hard = (m == max_P m) (N:134-136);
  * argmax = first maximal index (M:447,470); hard_bits[pixel] = bit set of the hard mask (bit p = hard[pixel][p], P <= 32:

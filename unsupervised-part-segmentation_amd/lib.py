@@ -127,6 +127,9 @@ _SIGS = {
     "ups_l1_fwd": ([_P, _P, _I, _L, _I, _I, _I, _P, _I, _P], C.c_int),
     "ups_l1_bwd": ([_P, _P, _P, _I, _L, _I, _I, _I, _P, _F, _P], C.c_int),
     "ups_sum_scale": ([_P, _I, _F, _P, _I, _P], C.c_int),
+    "ups_gram_plan": ([_I, _L, _I, _I, C.POINTER(C.c_int64)], C.c_int),
+    "ups_gram_l1_fwd": ([_P, _P, _I, _I, _L, _I, _I, _I, _P, _P, _P, _P], C.c_int),
+    "ups_gram_l1_bwd": ([_P, _P, _P, _I, _I, _L, _I, _I, _I, _P, _F, _P], C.c_int),
     "ups_part_softmax_fwd": ([_P, _P, _P, _P, _P, _P, _P, _L, _I, _P], C.c_int),
     "ups_part_softmax_moments_tile": ([_I], _I),
     "ups_part_softmax_moments_ints": ([_L, _I], _Z),

@@ -18,6 +18,7 @@ import ctypes as C
 import contextlib
 import math
 import os
+import warnings
 from collections import OrderedDict
 from collections.abc import Mapping
 
@@ -209,6 +210,22 @@ class _LazyLosses(Mapping):
         return len(self._d())
 
 
+def gram_weight_of(config, logger=None):
+    """`gram_weight` (model.py:608, edflow VGG19Features(default_gram=...)): a plain number passed to the constructor, not a make_var
+    schedule; default 0.0 in every shipped yaml.  edflow adds the Gram terms only when the weight is > 0: 0 or below means none."""
+    v = config.get("gram_weight", 0.0)
+    if isinstance(v, bool) or not isinstance(v, (int, float)):
+        raise ValueError("gram_weight: a number is expected (got {!r}); it is not a make_var schedule".format(v))
+    v = float(v)
+    if v < 0:
+        msg = "gram_weight {} < 0: no Gram terms (edflow adds them only for a positive weight)".format(v)
+        if logger:
+            logger.warning(msg)
+        else:
+            warnings.warn(msg)
+    return v if v > 0 else 0.0
+
+
 class Trainer(object):
     """Mirror of model.py:570-1068 plus the pieces edflow's TFBaseTrainer supplied (session loop,
     one Adam per loss key over the variables whose name contains the key, logging cadence)."""
@@ -238,8 +255,7 @@ class Trainer(object):
         if unknown:
             raise ValueError("probe: unknown hook(s) {}".format(sorted(unknown)))
         self.perceptual_input = config.get("perceptual_input", "native")
-        if float(config.get("gram_weight", 0.0)) != 0.0:        # model.py:608: default 0.0 in every shipped yaml
-            raise NotImplementedError("gram_weight != 0 (Gram-matrix terms of edflow's VGG19Features) is not on the shipped path")
+        self.gram_weight = gram_weight_of(config, self.logger)
         if config.get("use_pretty", False) or config.get("add_pretty", False):
             raise NotImplementedError("the 'pretty' image discriminator (model.py:190-212) is not used by the shipped configs")
         vw = config.get("vgg_widths", N.VGG_WIDTHS)
@@ -902,7 +918,7 @@ class Trainer(object):
             for i, (name, (zin, tgt, cz)) in enumerate(ins.items()):
                 with torch.cuda.stream(sides[i]):
                     g_img = nets.dsingle(name, Act(model.to_act(zin().view(1, 1, 1, cz)), 1, 1, 1, cz)).t
-                    lss = scale * self.vgg.loss(tgt.contiguous(), g_img, c.T)
+                    lss = scale * self.vgg.loss(tgt.contiguous(), g_img, c.T, gram_weight=self.gram_weight)
                     crit[name] = (lss, g_img)
                     if name in keys:
                         torch.autograd.grad([lss], [bank.params[n] for n in bank.groups[name]["names"]])
@@ -1003,10 +1019,10 @@ class Trainer(object):
         gen_in = self._perceptual_view(c, c.gen)
         if c.ft_pre is not None:
             c.main_stream.wait_event(c.ft_ready)
-            c.rec = self.vgg.loss(None, gen_in, T, target_features=c.ft_pre)
+            c.rec = self.vgg.loss(None, gen_in, T, target_features=c.ft_pre, gram_weight=self.gram_weight)
         else:
             tgt_in = c.vt if c.pmode == "native" else self._perceptual_view(c, model.to_act(c.vt))
-            c.rec = self.vgg.loss(tgt_in, gen_in, T)
+            c.rec = self.vgg.loss(tgt_in, gen_in, T, gram_weight=self.gram_weight)
         c.auto_rec = (1e-3 * 0.5 * (S * S * 3)) * c.rec                    # model.py:613-619
 
     def _bwd_reconstruction(self, c):

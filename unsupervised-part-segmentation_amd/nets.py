@@ -540,8 +540,9 @@ class VggTrunk(object):
                     feats.append((h, lay.co, L.ACT_RELU))
         return feats
 
-    def loss(self, target_img, generated_img, act_dtype, target_features=None):
-        """sum_l mean |f_l(target) - f_l(generated)| (feature weights 1, gram weight 0: model.py:608).
+    def loss(self, target_img, generated_img, act_dtype, target_features=None, gram_weight=0.0):
+        """sum_l mean |f_l(target) - f_l(generated)| (feature weights 1, model.py:608), plus, when gram_weight > 0, edflow's Gram terms
+        sum_l gram_weight * mean |G(f_l(target)) - G(f_l(generated))| (ops.PerceptualTermFn; UNVERIFIED normalisation ops.GRAM_DIV).
         target_features: f(target) computed earlier (the target is a data input: the trainer evaluates it on a side stream)."""
         if target_features is None:
             with torch.no_grad():
@@ -550,6 +551,9 @@ class VggTrunk(object):
         fg = self.features(generated_img, act_dtype)
         total = None
         for (a, c, act), (b, _, _) in zip(ft, fg):
-            term = ops.L1MeanFn.apply(a, b, c, act)
+            if gram_weight > 0:          # edflow adds the Gram terms only for a positive weight
+                term = ops.PerceptualTermFn.apply(a, b, c, act, float(gram_weight))
+            else:
+                term = ops.L1MeanFn.apply(a, b, c, act)
             total = term if total is None else total + term
         return total

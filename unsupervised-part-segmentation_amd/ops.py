@@ -1512,6 +1512,64 @@ class L1MeanFn(torch.autograd.Function):
         return None, gb, None, None
 
 
+# G(F)[b] = F[b]^T F[b] / (GRAM_DIV * h * w): edflow VGG19Features' Gram normalisation as recalled (UNVERIFIED; tests/gram_ref.py
+# restates the same constant)
+GRAM_DIV = 4.0
+_GRAM_PLANS = {}
+
+
+def gram_plan(n, hw, c, dtype):
+    """(K splits, partial floats, workspace floats, sign bytes) of ups_gram_l1_fwd at this shape (cached: one C call per shape)."""
+    key = (n, hw, c, dtype)
+    if key not in _GRAM_PLANS:
+        out = (C.c_int64 * 4)()
+        L.check(L.load().ups_gram_plan(n, hw, c, dtype, out), "ups_gram_plan")
+        _GRAM_PLANS[key] = tuple(int(v) for v in out)
+    return _GRAM_PLANS[key]
+
+
+class PerceptualTermFn(torch.autograd.Function):
+    """One feature map's perceptual term with edflow's Gram term: mean |act(a) - act(b)| + gram_w * mean_{b,i,j} |G(a) - G(b)|
+    (a, b [n,h,w,ld], G over the c logical channels of act(.)); gradient w.r.t. b only (a is the target).  The L1 kernels write the
+    term and its gradient, the Gram kernels (csrc/gram.hip) add theirs into the same scalar and the same gb."""
+
+    @staticmethod
+    def forward(ctx, a, b, c_log, act, gram_w):
+        a, b = a.contiguous(), b.contiguous()
+        n, ld = b.shape[0], b.shape[-1]
+        rows = b.numel() // ld
+        hw = rows // n
+        partial = torch.empty(L1_BLOCKS, dtype=torch.float32, device=b.device)
+        out = torch.empty((), dtype=torch.float32, device=b.device)
+        L.call("ups_l1_fwd", L.ptr(a), L.ptr(b), L.dt(b), rows, c_log, ld, act, L.ptr(partial), L1_BLOCKS, L.stream())
+        L.call("ups_sum_scale", L.ptr(partial), L1_BLOCKS, 1.0 / (rows * c_log), L.ptr(out), 0, L.stream())
+        _, npart, nws, nsign = gram_plan(n, hw, c_log, L.dt(b))
+        gpart = torch.empty(npart, dtype=torch.float32, device=b.device)
+        sign = torch.empty(nsign, dtype=torch.int8, device=b.device)
+        ws = torch.empty(nws, dtype=torch.float32, device=b.device) if nws else None
+        L.call("ups_gram_l1_fwd", L.ptr(a), L.ptr(b), L.dt(b), n, hw, c_log, ld, act, L.ptr(gpart), L.ptr(sign), L.ptr(ws),
+               L.stream())
+        norm = 1.0 / (GRAM_DIV * hw)
+        L.call("ups_sum_scale", L.ptr(gpart), npart, gram_w * norm / (n * c_log * c_log), L.ptr(out), 1, L.stream())
+        ctx.save_for_backward(a, b, sign)
+        ctx.c_log, ctx.act, ctx.gram_w = c_log, act, gram_w
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        a, b, sign = ctx.saved_tensors
+        n, ld = b.shape[0], b.shape[-1]
+        rows = b.numel() // ld
+        hw, c_log = rows // n, ctx.c_log
+        gb = torch.empty_like(b)
+        g = g.contiguous().float()
+        L.call("ups_l1_bwd", L.ptr(a), L.ptr(b), L.ptr(gb), L.dt(b), rows, c_log, ld, ctx.act, L.ptr(g),
+               1.0 / (rows * c_log), L.stream())
+        coef = 2.0 * ctx.gram_w / (n * c_log * c_log) / (GRAM_DIV * hw)
+        L.call("ups_gram_l1_bwd", L.ptr(b), L.ptr(sign), L.ptr(gb), L.dt(b), n, hw, c_log, ld, ctx.act, L.ptr(g), coef, L.stream())
+        return None, gb, None, None, None
+
+
 class CriticHeadFn(torch.autograd.Function):
     """Head of a separable MI critic (model.py:159-173 last line, 524-536, 821-826, 855): (h_pi [2B,..,K], h_al [2B,..,K]) ->
     (loss, accuracy, mean joint logit) as three device scalars, rows [0,B) = joint pairs, [B,2B) = marginal pairs.  One launch
