@@ -13,18 +13,6 @@
 
 #include "common.h"
 
-#if defined(UPS_PHASE_TIMING)
-// debug build (tools/probes/phase_timing.sh): thread 0 of each block records the 100 MHz wall clock at phase boundaries and the
-// slot it ran in (HW_ID: CU / SE, XCC_ID, LDS base) -- where a block's life goes, which XCD ends when
-__device__ unsigned long long ups_phase_t[8 * 65536];
-extern "C" int ups_phase_dump(unsigned long long* host, int nblocks) {
-    return (int)hipMemcpyFromSymbol(host, HIP_SYMBOL(ups_phase_t), sizeof(unsigned long long) * 8 * (size_t)nblocks, 0, hipMemcpyDeviceToHost);
-}
-#define UPS_PHASE(k) do { if (threadIdx.x == 0 && blockIdx.x < 65536) ups_phase_t[blockIdx.x * 8 + (k)] = wall_clock64(); } while (0)
-#else
-#define UPS_PHASE(k)
-#endif
-
 namespace {
 
 constexpr int TS = 16;                 // tile side
@@ -123,17 +111,13 @@ template <> struct Frag16<bf16, 0> { typedef bf16x8 type; };
 template <> struct Frag16<f16, 0> { typedef f16x8 type; };
 // F8: a 16-byte fragment holds 16 e4m3 channels -- two v_mfma_f32_16x16x32_fp8_fp8 per fragment pair (low / high 8 bytes:
 // both operands use the same byte -> k mapping), a 64-byte pixel / weight row is a chunk of 64 channels.
-// A2: the A fragments of the NEXT tap are requested at the start of the current one (a second register set: the instances
-// whose patch arrives by LDS-DMA have the 16 VGPRs to spare) instead of behind its last MFMAs, where their LDS latency sat
-// in front of every tap.
-template <typename T, int TM16, int TN16, int ROWB, int F8, bool A2 = false>
+template <typename T, int TM16, int TN16, int ROWB, int F8>
 __device__ __forceinline__ void bf16_taps16(const unsigned char* A, const unsigned char* B, const int (&arow)[TM16],
                                             int po0, int po1, int po2, int sw0, int sw1, int sw2, int b_tap_stride,
                                             f32x4v (&acc)[TM16][TN16]) {
     typedef typename Frag16<T, F8>::type frag_t;
-    frag_t fa2[A2 ? 2 : 1][TM16], fb[2][2];
+    frag_t fa[TM16], fb[2][2];
     auto fetch_a = [&](int t) __attribute__((always_inline)) {
-        frag_t (&fa)[TM16] = fa2[A2 ? (t & 1) : 0];
         const int po = t == 0 ? po0 : (t == 1 ? po1 : po2);
         const int sw = t == 0 ? sw0 : (t == 1 ? sw1 : sw2);
         if constexpr (ROWB > 0) {
@@ -160,8 +144,6 @@ __device__ __forceinline__ void bf16_taps16(const unsigned char* A, const unsign
             // the next B pair is requested before this pair's MFMAs (second register slot), the next tap's A fragments behind
             // the last MFMAs that read the current ones
             if (step + 1 < 3 * NP) fetch_b((step + 1) / NP, (step + 1) % NP, (step + 1) & 1);
-            if constexpr (A2) { if (jh == 0 && t + 1 < 3) fetch_a(t + 1); }
-            frag_t (&fa)[TM16] = fa2[A2 ? (t & 1) : 0];
             __builtin_amdgcn_s_setprio(1);
 #pragma unroll
             for (int i = 0; i < TM16; ++i)
@@ -180,7 +162,7 @@ __device__ __forceinline__ void bf16_taps16(const unsigned char* A, const unsign
                         acc[i][2 * jh + jj] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fb[step & 1][jj], fa[i], acc[i][2 * jh + jj], 0, 0, 0);
                     }
             __builtin_amdgcn_s_setprio(0);
-            if constexpr (!A2) { if (jh + 1 == NP && t + 1 < 3) fetch_a(t + 1); }
+            if (jh + 1 == NP && t + 1 < 3) fetch_a(t + 1);
         }
     }
 }
@@ -211,12 +193,8 @@ __device__ __forceinline__ void f8s_tap(const unsigned char* A, const unsigned c
         __builtin_amdgcn_s_setprio(1);
 #pragma unroll
         for (int i = 0; i < TM16; ++i)      // weights as the row operand (e4m3), pixels e4m3 (activations) or e5m2 (gradients)
-#if defined(UPS_ABLATE_MFMA)
-            acc[i][j][0] += __int_as_float(fb[BBUFS == 2 ? (j & 1) : 0][i] ^ fa[i][j & 7]);
-#else
             acc[i][j] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(fb[BBUFS == 2 ? (j & 1) : 0], fa[i], acc[i][j], 0, E5M2 ? 1 : 0,
                                                                           0, 0x7f7f7f7f, 0, 0x7f7f7f7f);
-#endif
         __builtin_amdgcn_s_setprio(0);
         // no hoisting of later fetches above these MFMAs (the scheduler otherwise requests every B fragment up front and
         // spills accumulators to hold them)
@@ -278,11 +256,6 @@ template <typename T, int BN, int OCC, int SUB, int F8 = 0, bool PRE = false, in
 __global__ __launch_bounds__(512, 2 * OCC) void conv3x3_patch_kernel(const PatchK p, const int tiles_x, const int tiles_y,
                                                                  const int ntn, const int kchunks, const int nblocks) {
     constexpr int EPC = Chunk<T>::N;
-#if defined(UPS_PATCH_A2)
-    constexpr bool A2FR = DMAP;                  // second A-fragment register set (bf16_taps16): measured SLOWER (round 3: the 128-wide
-#else                                            // two-blocks-per-CU instances spill at 128 VGPRs: dgrad 2.28 -> 3.07 ms), off by default
-    constexpr bool A2FR = false;
-#endif
     constexpr int BK = 4 * EPC;                  // weight-row elements of T per 64-byte row (the fp8 rows are addressed as T too)
     constexpr int BKA = F8 ? 64 : BK;            // input channels per chunk
     constexpr bool F8S = F8 >= 3;                // block-scaled K = 128 MFMA over pairs of 64-channel chunks (f8s_tap)
@@ -290,13 +263,7 @@ __global__ __launch_bounds__(512, 2 * OCC) void conv3x3_patch_kernel(const Patch
     static_assert(!F8 || (sizeof(T) == 2 && SUB == TS && (OCC == 1 || PRE)), "fp8 operands: bf16 tensors, one tile per image; two blocks per CU only with a pre-quantised input");
     static_assert(!F8S || (PRE && OCC == 2 && BN >= 64 && TAPS == 0 && !DMAP), "block-scaled fp8: pre-quantised input, two blocks per CU");
     static_assert(!PRE || F8, "a pre-quantised input implies fp8 operands");
-#if defined(UPS_F8S_WN1)
-    // (block-scaled fp8, alternative wave tile: 2 tile rows x ALL the N-tile's channels -- 16 A registers resident, the B fragments
-    // stream through two slots; 20 instead of 16 fragment reads per step and an epilogue that spills: not the default)
-    constexpr int WN = (BN == 32 || F8 >= 3) ? 1 : 2;
-#else
     constexpr int WN = (BN == 32) ? 1 : 2;
-#endif
     constexpr int WM = 8 / WN;                   // 4 or 8 waves along the pixels
     constexpr int TM = 256 / WM / 32;            // 2 or 1
     constexpr int TN = BN / WN / 32;             // 2, 1, 1
@@ -315,14 +282,6 @@ __global__ __launch_bounds__(512, 2 * OCC) void conv3x3_patch_kernel(const Patch
 
     const int tid = threadIdx.x, lane = tid & 63;
     const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);   // wave-uniform values derived from it live in SGPRs
-    UPS_PHASE(0);
-#if defined(UPS_PHASE_TIMING)
-    if (threadIdx.x == 0 && blockIdx.x < 65536) {
-        const unsigned hw = __builtin_amdgcn_s_getreg((31 << 11) | 4), xcc = __builtin_amdgcn_s_getreg((3 << 11) | 20);
-        const unsigned lb = __builtin_amdgcn_s_getreg((7 << 11) | 6);
-        ups_phase_t[blockIdx.x * 8 + 7] = (unsigned long long)hw | ((unsigned long long)xcc << 32) | ((unsigned long long)lb << 40);
-    }
-#endif
     const float act_ns = ups_slope_eff(p.act_in, p.act_slope);   // branch-free activation-on-load
     const float dact_ns = ups_slope_eff(p.dact_kind, p.act_slope); // act'(x) = x > 0 ? 1 : dact_ns (only used when dact != NULL)
     const float oact_ns = ups_slope_eff(p.out_act, p.act_slope);   // stored value = max(v, oact_ns * v) when out_act is set
@@ -416,13 +375,11 @@ __global__ __launch_bounds__(512, 2 * OCC) void conv3x3_patch_kernel(const Patch
     // is static and the compiler can use counted vmcnt waits across the prefetch distance
     auto ld_a = [&](int off, int koff) -> uint4 {
         uint4 v = zero4;
-#if !defined(UPS_ABLATE_GLOAD)
         if (off >= 0 && koff + cha < p.ci) {
             int o = off;
             asm volatile("" : "+v"(o));     // keep the 32-bit offset: scalar base (image + chunk) + vector offset addressing
             v = *(const uint4*)((const unsigned char*)(in + koff) + (unsigned)o);
         }
-#endif
         return v;
     };
     const T* __restrict__ in_o = in + (long long)origin * p.ldi;
@@ -432,7 +389,6 @@ __global__ __launch_bounds__(512, 2 * OCC) void conv3x3_patch_kernel(const Patch
     auto ld_rel = [&](unsigned pk, int koff, uint4& hi) -> uint4 {
         uint4 v = zero4;
         if constexpr (F8) hi = zero4;
-#if !defined(UPS_ABLATE_GLOAD)
         asm volatile("" : "+v"(pk));        // derived offsets are recomputed per chunk, not hoisted into held registers
         const unsigned rel = pk & 0xffffu;
         if (rel != 0xffffu && koff + cha < p.ci) {
@@ -448,7 +404,6 @@ __global__ __launch_bounds__(512, 2 * OCC) void conv3x3_patch_kernel(const Patch
             // part-masked input (model.py:185): the pixel belongs to this block's part image only where its hard-mask bit is set
             if (mbits_o && !((mbits_o[rel] >> part) & 1u)) v = zero4;
         }
-#endif
         return v;
     };
     auto load_patch = [&](int cc) __attribute__((always_inline)) {
@@ -525,10 +480,8 @@ __global__ __launch_bounds__(512, 2 * OCC) void conv3x3_patch_kernel(const Patch
             const int tl = item / (BN * 4), rem = item - tl * (BN * 4);
             const int row = rem >> 2, ch = rem & 3;
             const int c = nt * BN + row;
-#if !defined(UPS_ABLATE_GLOAD)
             if (c < p.co)
                 v = *(const uint4*)(w + (((long long)p_w(p.tap_wi, 3 * g + tl) * kchunks + cc) * p.co + c) * BK + ch * EPC);
-#endif
         }
         return v;
     };
@@ -598,11 +551,7 @@ __global__ __launch_bounds__(512, 2 * OCC) void conv3x3_patch_kernel(const Patch
         // of them: the next chunk's 18 / 37 KB are requested at once, one barrier and one exposed round trip per CHUNK
         constexpr bool CHUNKST = (SUB < TS || (CSTD && DMAP && SUB == TS)) && BN <= 64 && F8 == 0 && OCC == 1;
         constexpr int NST = (OCC == 2) ? 2 : (CHUNKST ? 6 : 3);          // ring stages (tap-rows)
-#if defined(UPS_OCC2_FRAG2)
-        constexpr int FRAG_BUFS = 2;
-#else
         constexpr int FRAG_BUFS = (BN == 128) ? 1 : 2;   // 128-wide tiles at two blocks per CU: <= 128 VGPRs without spills
-#endif
         // a single-chunk problem (ci <= 32) never touches the second patch buffer: the launcher then requests less LDS
         // (2 blocks per CU instead of 1, which hides the per-block load latency of these 3-iteration blocks)
         unsigned char* Bst = smem + (((kchunks == 1 && SUB == TS) || OCC == 2) ? 1 : 2) * ABY;   // NST x BST
@@ -630,7 +579,6 @@ __global__ __launch_bounds__(512, 2 * OCC) void conv3x3_patch_kernel(const Patch
                 // uniform slab base (scalar) + per-lane 32-bit offset
                 const int wslice = TAPS != 0 ? 3 * g + d_tl[q] : p_w(p.tap_wi, 3 * g + d_tl[q]);
                 const T* slab = w + ((long long)wslice * kchunks + cc) * p.co * BK;
-#if !defined(UPS_ABLATE_DMA)
                 // issued as inline asm: hipcc's wait-count pass treats the builtin as a FLAT access that may touch LDS
                 // and from then on waits lgkmcnt(0) before every fragment use (no counted waits); hidden from the pass,
                 // the fragment waits are counted.  The pass's own vmcnt(N) waits stay safe (extra younger operations
@@ -638,7 +586,6 @@ __global__ __launch_bounds__(512, 2 * OCC) void conv3x3_patch_kernel(const Patch
                 const unsigned lds_dst = __builtin_amdgcn_readfirstlane(smem_lds + (unsigned)(stg + j * 1024 - smem));
                 asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2"
                              :: "s"(lds_dst), "v"(d_off[q]), "s"(slab) : "memory", "m0");
-#endif
             }
         };
         const unsigned char* __restrict__ in_b = (const unsigned char*)(in + (long long)origin * p.ldi);
@@ -649,10 +596,8 @@ __global__ __launch_bounds__(512, 2 * OCC) void conv3x3_patch_kernel(const Patch
                 for (int q = 0; q < 3; ++q) {
                     if (wid + 8 * q >= (PW * PWPS + 15) / 16) continue;        // piece 23 of 22.5 (wave-uniform)
                     const unsigned lds_dst = __builtin_amdgcn_readfirstlane(smem_lds + (unsigned)(boff + (wid + 8 * q) * 1024));
-#if !defined(UPS_ABLATE_GLOAD)
                     asm volatile("s_mov_b64 exec, %0\n\ts_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %2, %3\n\ts_mov_b64 exec, -1"
                                  :: "s"(pd_mask[q]), "s"(lds_dst), "v"(pd_off[q]), "s"(base) : "memory", "m0");
-#endif
                 }
             }
         };
@@ -735,10 +680,8 @@ __global__ __launch_bounds__(512, 2 * OCC) void conv3x3_patch_kernel(const Patch
 #pragma unroll
             for (int q = 0; q < NW8; ++q) {
                 const unsigned lds_dst = __builtin_amdgcn_readfirstlane(smem_lds + (unsigned)(2 * ABY + (st & 1) * BST8 + (wid + 8 * q) * 1024));
-#if !defined(UPS_ABLATE_DMA)
                 asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2"
                              :: "s"(lds_dst), "v"(d8_off[q]), "s"(slab) : "memory", "m0");
-#endif
             }
         };
         auto dma_patch8 = [&](int dc) __attribute__((always_inline)) {
@@ -749,10 +692,8 @@ __global__ __launch_bounds__(512, 2 * OCC) void conv3x3_patch_kernel(const Patch
                 for (int q = 0; q < 3; ++q) {
                     if (wid + 8 * q >= (PW * PWPS + 15) / 16) continue;        // piece 23 of 22.5 (wave-uniform)
                     const unsigned lds_dst = __builtin_amdgcn_readfirstlane(smem_lds + (unsigned)(half * ABY + (wid + 8 * q) * 1024));
-#if !defined(UPS_ABLATE_GLOAD)
                     asm volatile("s_mov_b64 exec, %0\n\ts_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %2, %3\n\ts_mov_b64 exec, -1"
                                  :: "s"(pd_mask[q]), "s"(lds_dst), "v"(pd_off[q]), "s"(base) : "memory", "m0");
-#endif
                 }
             }
         };
@@ -777,7 +718,6 @@ __global__ __launch_bounds__(512, 2 * OCC) void conv3x3_patch_kernel(const Patch
             __builtin_amdgcn_s_barrier();
         }
         } else {
-        UPS_PHASE(1);
         // the tile's sign bytes (PatchK.sgn_res): [256 px][BN / 8], zero outside a ragged image and past the tensor's channels.  REQUESTED
         // first -- they come from HBM, the weights from L2 -- and committed to LDS behind the patch / weight requests, so that their round
         // trip runs under the patch's (two registers for the length of the prologue)
@@ -809,7 +749,6 @@ __global__ __launch_bounds__(512, 2 * OCC) void conv3x3_patch_kernel(const Patch
         if (one_shot || CHUNKST) dma_w(2);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
-        UPS_PHASE(2);
         if (one_shot) {
             add_res_patch(Abuf, 0);
 #pragma unroll
@@ -817,7 +756,7 @@ __global__ __launch_bounds__(512, 2 * OCC) void conv3x3_patch_kernel(const Patch
                 const unsigned char* B = Bst + g * BST + (wn * TN * 32) * 64 + boff16;
                 if constexpr (TAPS != 0) {
                     const int po0 = ((TAPS == 1 ? g : 2 - g) * PWPS + (TAPS == 1 ? 0 : 2)) * APX;
-                    bf16_taps16<T, TM16, TN16, (SUB == TS ? PWPS * APX : 0), F8, A2FR>(Abuf, B, arow16, po0, po0 + (TAPS == 1 ? APX : -APX),
+                    bf16_taps16<T, TM16, TN16, (SUB == TS ? PWPS * APX : 0), F8>(Abuf, B, arow16, po0, po0 + (TAPS == 1 ? APX : -APX),
                                             po0 + (TAPS == 1 ? 2 * APX : -2 * APX), TAPS == 1 ? swx0 : swx2, swx1, TAPS == 1 ? swx2 : swx0,
                                             BN * 64, acc16);
                 } else {
@@ -825,7 +764,7 @@ __global__ __launch_bounds__(512, 2 * OCC) void conv3x3_patch_kernel(const Patch
                     const int po0 = ((p_dy(p.tap_off, 3 * g) + 1) * PWPS + dx0) * APX;
                     const int po1 = ((p_dy(p.tap_off, 3 * g + 1) + 1) * PWPS + dx1) * APX;
                     const int po2 = ((p_dy(p.tap_off, 3 * g + 2) + 1) * PWPS + dx2) * APX;
-                    bf16_taps16<T, TM16, TN16, (SUB == TS ? PWPS * APX : 0), F8, A2FR>(Abuf, B, arow16, po0, po1, po2,
+                    bf16_taps16<T, TM16, TN16, (SUB == TS ? PWPS * APX : 0), F8>(Abuf, B, arow16, po0, po1, po2,
                                             a_lane16 + ((q16 ^ a_swz16(px_l16 + dx0)) << 4), a_lane16 + ((q16 ^ a_swz16(px_l16 + dx1)) << 4),
                                             a_lane16 + ((q16 ^ a_swz16(px_l16 + dx2)) << 4), BN * 64, acc16);
                 }
@@ -841,9 +780,6 @@ __global__ __launch_bounds__(512, 2 * OCC) void conv3x3_patch_kernel(const Patch
             const int n1 = it + 1;
             if (n1 < total) {
                 if constexpr (!DMAP) { if (n1 % 3 == 0) load_patch(n1 / 3); }
-#if defined(UPS_ABLATE_PATCHWAIT)     // (timing experiment of round 6, results garbage: the next chunk's patch requested a whole chunk ahead INTO THE
-                if constexpr (DMAP) { if (g == 0 && cc + 1 < kchunks) dma_patch(cc + 1); }      // BUFFER BEING READ, no re-staging barrier: what a second patch buffer would buy)
-#endif
                 dma_w(n1);
             }
             const unsigned char* A = Abuf;
@@ -853,7 +789,7 @@ __global__ __launch_bounds__(512, 2 * OCC) void conv3x3_patch_kernel(const Patch
                 // static tap geometry: tap-row g reads patch rows g .. (forward) / 2-g .. (flipped), its three taps the column
                 // shifts 0, 1, 2 / 2, 1, 0: two scalar operations instead of the tap decode, loop-invariant lane terms
                 const int po0 = ((TAPS == 1 ? g : 2 - g) * PWPS + (TAPS == 1 ? 0 : 2)) * APX;
-                bf16_taps16<T, TM16, TN16, (SUB == TS ? PWPS * APX : 0), F8, A2FR>(A, B, arow16, po0, po0 + (TAPS == 1 ? APX : -APX),
+                bf16_taps16<T, TM16, TN16, (SUB == TS ? PWPS * APX : 0), F8>(A, B, arow16, po0, po0 + (TAPS == 1 ? APX : -APX),
                                         po0 + (TAPS == 1 ? 2 * APX : -2 * APX), TAPS == 1 ? swx0 : swx2, swx1, TAPS == 1 ? swx2 : swx0,
                                         BN * 64, acc16);
             } else {
@@ -861,31 +797,19 @@ __global__ __launch_bounds__(512, 2 * OCC) void conv3x3_patch_kernel(const Patch
             const int po0 = ((p_dy(p.tap_off, 3 * g) + 1) * PWPS + dx0) * APX;
             const int po1 = ((p_dy(p.tap_off, 3 * g + 1) + 1) * PWPS + dx1) * APX;
             const int po2 = ((p_dy(p.tap_off, 3 * g + 2) + 1) * PWPS + dx2) * APX;
-            bf16_taps16<T, TM16, TN16, (SUB == TS ? PWPS * APX : 0), F8, A2FR>(A, B, arow16, po0, po1, po2, a_lane16 + ((q16 ^ a_swz16(px_l16 + dx0)) << 4),
+            bf16_taps16<T, TM16, TN16, (SUB == TS ? PWPS * APX : 0), F8>(A, B, arow16, po0, po1, po2, a_lane16 + ((q16 ^ a_swz16(px_l16 + dx0)) << 4),
                                     a_lane16 + ((q16 ^ a_swz16(px_l16 + dx1)) << 4),
                                     a_lane16 + ((q16 ^ a_swz16(px_l16 + dx2)) << 4), BN * 64, acc16);
             }
-#if !defined(UPS_ABLATE_PATCHWAIT)
             if (n1 < total && n1 % 3 == 0) {
                 asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-#if !defined(UPS_ABLATE_BARRIER)
                 __builtin_amdgcn_s_barrier();                 // every wave has read the last tap of this chunk's patch
-#endif
                 if constexpr (DMAP) dma_patch(n1 / 3);
-                else {
-#if !defined(UPS_ABLATE_LSTORE)
-                store_patch(Abuf);
-#endif
-                }
+                else store_patch(Abuf);
             }
-#endif
-#if !defined(UPS_ABLATE_WWAIT)            // (timing experiment of round 6, results garbage: the wait for the next tap-row's weights)
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#endif
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-#if !defined(UPS_ABLATE_BARRIER)          // (timing experiment of round 6 on THIS loop -- the dominant instances run it; results garbage)
             __builtin_amdgcn_s_barrier();
-#endif
         }
         } else if constexpr (CHUNKST) {
         for (int cc = 0; cc < kchunks; ++cc) {
@@ -901,7 +825,7 @@ __global__ __launch_bounds__(512, 2 * OCC) void conv3x3_patch_kernel(const Patch
                 const unsigned char* B = Bst + ((3 * cc + g) % NST) * BST + (wn * TN * 32) * 64 + boff16;
                 if constexpr (TAPS != 0) {
                     const int po0 = ((TAPS == 1 ? g : 2 - g) * PWPS + (TAPS == 1 ? 0 : 2)) * APX;
-                    bf16_taps16<T, TM16, TN16, (SUB == TS ? PWPS * APX : 0), F8, A2FR>(A, B, arow16, po0, po0 + (TAPS == 1 ? APX : -APX),
+                    bf16_taps16<T, TM16, TN16, (SUB == TS ? PWPS * APX : 0), F8>(A, B, arow16, po0, po0 + (TAPS == 1 ? APX : -APX),
                                             po0 + (TAPS == 1 ? 2 * APX : -2 * APX), TAPS == 1 ? swx0 : swx2, swx1, TAPS == 1 ? swx2 : swx0,
                                             BN * 64, acc16);
                 } else {
@@ -909,7 +833,7 @@ __global__ __launch_bounds__(512, 2 * OCC) void conv3x3_patch_kernel(const Patch
                     const int po0 = ((p_dy(p.tap_off, 3 * g) + 1) * PWPS + dx0) * APX;
                     const int po1 = ((p_dy(p.tap_off, 3 * g + 1) + 1) * PWPS + dx1) * APX;
                     const int po2 = ((p_dy(p.tap_off, 3 * g + 2) + 1) * PWPS + dx2) * APX;
-                    bf16_taps16<T, TM16, TN16, (SUB == TS ? PWPS * APX : 0), F8, A2FR>(A, B, arow16, po0, po1, po2,
+                    bf16_taps16<T, TM16, TN16, (SUB == TS ? PWPS * APX : 0), F8>(A, B, arow16, po0, po1, po2,
                                             a_lane16 + ((q16 ^ a_swz16(px_l16 + dx0)) << 4), a_lane16 + ((q16 ^ a_swz16(px_l16 + dx1)) << 4),
                                             a_lane16 + ((q16 ^ a_swz16(px_l16 + dx2)) << 4), BN * 64, acc16);
                 }
@@ -937,7 +861,7 @@ __global__ __launch_bounds__(512, 2 * OCC) void conv3x3_patch_kernel(const Patch
             if (g == 0) add_res_patch(A, cc);
             if constexpr (TAPS != 0) {
                 const int po0 = ((TAPS == 1 ? g : 2 - g) * PWPS + (TAPS == 1 ? 0 : 2)) * APX;
-                bf16_taps16<T, TM16, TN16, (SUB == TS ? PWPS * APX : 0), F8, A2FR>(A, B, arow16, po0, po0 + (TAPS == 1 ? APX : -APX),
+                bf16_taps16<T, TM16, TN16, (SUB == TS ? PWPS * APX : 0), F8>(A, B, arow16, po0, po0 + (TAPS == 1 ? APX : -APX),
                                         po0 + (TAPS == 1 ? 2 * APX : -2 * APX), TAPS == 1 ? swx0 : swx2, swx1, TAPS == 1 ? swx2 : swx0,
                                         BN * 64, acc16);
             } else {
@@ -945,15 +869,13 @@ __global__ __launch_bounds__(512, 2 * OCC) void conv3x3_patch_kernel(const Patch
             const int po0 = ((p_dy(p.tap_off, 3 * g) + 1) * PWPS + dx0) * APX;
             const int po1 = ((p_dy(p.tap_off, 3 * g + 1) + 1) * PWPS + dx1) * APX;
             const int po2 = ((p_dy(p.tap_off, 3 * g + 2) + 1) * PWPS + dx2) * APX;
-            bf16_taps16<T, TM16, TN16, (SUB == TS ? PWPS * APX : 0), F8, A2FR>(A, B, arow16, po0, po1, po2, a_lane16 + ((q16 ^ a_swz16(px_l16 + dx0)) << 4),
+            bf16_taps16<T, TM16, TN16, (SUB == TS ? PWPS * APX : 0), F8>(A, B, arow16, po0, po1, po2, a_lane16 + ((q16 ^ a_swz16(px_l16 + dx0)) << 4),
                                     a_lane16 + ((q16 ^ a_swz16(px_l16 + dx1)) << 4),
                                     a_lane16 + ((q16 ^ a_swz16(px_l16 + dx2)) << 4), BN * 64, acc16);
             }
-#if !defined(UPS_ABLATE_LSTORE)
             // (the activation patch goes through registers for the fused activation / zero padding; hipcc waits
             // vmcnt(0) for it, which also drains the DMAs once per channel chunk -- measured cost ~0.2 ms of 3.2 ms)
             if constexpr (!DMAP) { if (n1 < total && n1 % 3 == 0) store_patch(Abuf + ((n1 / 3) & 1) * ABY); }
-#endif
             // the weights of tap-row it+1 must have landed; the NW DMAs of tap-row it+2 may stay in flight
             if (n2 < total) {
                 if (NW == 3) asm volatile("s_waitcnt vmcnt(3)" ::: "memory");
@@ -963,9 +885,7 @@ __global__ __launch_bounds__(512, 2 * OCC) void conv3x3_patch_kernel(const Patch
                 asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             }
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-#if !defined(UPS_ABLATE_BARRIER)          // (timing experiment of round 6: what the per-tap-row barrier costs; results are garbage without it)
             __builtin_amdgcn_s_barrier();
-#endif
         }
         }
         }       // (!F8S)
@@ -1004,24 +924,7 @@ __global__ __launch_bounds__(512, 2 * OCC) void conv3x3_patch_kernel(const Patch
     }
     }
 
-    UPS_PHASE(3);
     // ---- epilogue
-#if defined(UPS_EPI_PRIO)
-    __builtin_amdgcn_s_setprio(UPS_EPI_PRIO);      // (round-6 experiment: the epilogue's vector instructions ahead of the CU neighbour's MFMA bursts)
-#endif
-#if defined(UPS_ABLATE_EPI)
-    {   // ablation build: keep the accumulators alive, write (almost) nothing
-        float sacc = 0.f;
-#pragma unroll
-        for (int i = 0; i < TM; ++i)
-#pragma unroll
-            for (int j = 0; j < TN; ++j)
-#pragma unroll
-                for (int e = 0; e < 16; ++e) sacc += sizeof(T) == 2 ? acc16[2 * i + (e >> 3)][2 * j + ((e >> 2) & 1)][e & 3] : acc[i][j][e];
-        if (sacc == 12345.678f) ((float*)p.out)[0] = sacc;
-        return;
-    }
-#endif
     if constexpr (F8) {
         // max |act(x)| of the launch (blocks of the first N-tile; 64 slots spread the atomics): next launch's scale
         if constexpr (!PRE) {
@@ -1115,7 +1018,6 @@ __global__ __launch_bounds__(512, 2 * OCC) void conv3x3_patch_kernel(const Patch
                 }
                 __syncthreads();
             }
-            UPS_PHASE(4);
             // Accumulator element e of acc16[i][j], lane (p16 = lane & 15, q16 = lane >> 4), is tile pixel (row wm*TM16 + i,
             // column p16), channel (wn*TN16 + j)*16 + 4*q16 + e of the N-tile: 4 consecutive channels per lane, so the
             // residual comes in and the result goes out with one 8-byte LDS access per (i, j).  The CoordConv term of an
@@ -1241,7 +1143,6 @@ __global__ __launch_bounds__(512, 2 * OCC) void conv3x3_patch_kernel(const Patch
                 }
             }
             __syncthreads();
-            UPS_PHASE(5);
             if (p.mask_grad) {
                 // input gradient of the part-masked convolution, reduced to the hard mask: g_hard[b][y][x][part] =
                 // sum_c gx[c] * view[b][y][x][c] with gx rounded to the activation dtype first (as the tensor it replaces was)
@@ -1314,7 +1215,6 @@ __global__ __launch_bounds__(512, 2 * OCC) void conv3x3_patch_kernel(const Patch
                 const float m = wave_max(of8_amax);
                 if (lane == 0) ups_amax_slot(p.out_f8_amax + (bid & 63), m);
             }
-            UPS_PHASE(6);
             return;
         }
     }

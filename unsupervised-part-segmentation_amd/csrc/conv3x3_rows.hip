@@ -4,7 +4,7 @@
 //
 // The patch-tiled kernel (conv3x3_patch.hip) runs these layers at 2.5 TB/s: a 16x16 tile is one block with its own prologue, its
 // own copy of the 3x3 weight set through LDS, one dependent HBM round trip for its halo patch and an epilogue -- 9.5 us of block
-// life for 0.5 us of MFMA work, 470 vector instructions per wave (tools/probes/phase_timing.py).  Here a block owns a band of 32
+// life for 0.5 us of MFMA work, 470 vector instructions per wave (phase-timing build).  Here a block owns a band of 32
 // full-width image rows and streams them:
 //   * every input row is fetched ONCE, whole, by LDS-DMA (one 1 KiB global_load_lds_dwordx4 per wave and row) into a ring of NR row
 //     buffers [32-channel plane][pixel slot = x + 1][64 B] (slots 0 and W + 1 stay zero: the horizontal padding); the swizzle of the
@@ -804,7 +804,7 @@ int launch_rows_s2(const RowsK& k, hipStream_t s) {
 // ---------------------------------------------------------------------------------------------------------------------------------
 // K-deep, thin-out form: the mask decoder's logit convolution 256 (+2 CoordConv) -> P <= 16 channels (cub/code/SB_model48i/model.py:154),
 // a 1.07 GB read for 84 MB of output.  The patch kernel ran it with one 32-channel patch chunk in flight per block -- 20 us of
-// dependent HBM round trips per tile (tools/probes/phase_timing.py), 2 TB/s.  Here a block owns a strip of 32 columns x 32 rows and
+// dependent HBM round trips per tile (phase-timing build), 2 TB/s.  Here a block owns a strip of 32 columns x 32 rows and
 // its eight waves split K: wave w streams the rows of ITS 32-channel plane (34 pixel slots with the halo) through a private ring --
 // its own DMA pieces, its own counted waits, no barrier for the input at all -- with the nine taps' weights of that plane in
 // registers (36 VGPRs), and computes a partial 32 pixels x 16 channels per output row (18 MFMAs for 18 fragment reads).  The eight

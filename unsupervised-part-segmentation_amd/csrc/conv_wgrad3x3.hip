@@ -75,12 +75,6 @@ __device__ inline bf16x8 tr_frag_d(const unsigned char* tile, int row0, int wco,
     return u.b;
 }
 
-#if defined(UPS_WGRAD_NO_PIPE)
-constexpr bool PIPE_X = false;
-#else
-constexpr bool PIPE_X = true;
-#endif
-
 template <int CB, int BN, int TH, bool SLIDE = false>
 __global__ __launch_bounds__(512) void conv_wgrad3x3_kernel(const Wg3K p, const int cit, const int cot, const int nsplit) {
     constexpr int PROWS = TH + 2, PPIX = PWID * PROWS;
@@ -261,7 +255,7 @@ __global__ __launch_bounds__(512) void conv_wgrad3x3_kernel(const Wg3K p, const 
     float bsum = 0.f;        // bias gradient: column sums straight from the dout fragments (k = 8*(lane>>5)+j, col = lane&31)
 
     if constexpr (WK == 1 && SLIDE) {
-      if (!p.mask && PIPE_X) {
+      if (!p.mask) {
         // Software-pipelined staging: the X items of unit u+1 are converted and written to LDS in the MIDDLE of unit u's MFMAs
         // (they were requested during unit u-1), the loads of unit u+2 are issued right behind and stay in flight across the
         // barrier (counted wait: only the dout DMA of unit u+1, issued first, has to have landed).  One block per CU runs its

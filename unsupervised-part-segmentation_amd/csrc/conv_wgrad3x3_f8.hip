@@ -156,12 +156,8 @@ __global__ __launch_bounds__(512) void conv_wgrad3x3_f8_kernel(const Wg8K p, con
 #pragma unroll
         for (int k = 0; k < 2; ++k) {
             const unsigned lds_dst = __builtin_amdgcn_readfirstlane(smem_lds + (unsigned)(2 * XB + dbuf * DB + (wid + 8 * k) * 1024));
-#if !defined(UPS_W8_NO_DMA)
             asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2"
                          :: "s"(lds_dst), "v"(dd[k]), "s"(db) : "memory", "m0");
-#else
-            asm volatile("" :: "s"(lds_dst), "v"(dd[k]), "s"(db));                                  // (ablation: no dout traffic)
-#endif
         }
     };
     auto load_x = [&](int u) __attribute__((always_inline)) {
@@ -175,14 +171,10 @@ __global__ __launch_bounds__(512) void conv_wgrad3x3_f8_kernel(const Wg8K p, con
             unsigned r = xr[k], f = xs[k];
             asm volatile("" : "+v"(r), "+v"(f));
             uint4 v0 = zero4, v1 = zero4;
-#if !defined(UPS_W8_NO_XLOAD)
             if (((f >> 16) & edge) == 0u) {
                 const unsigned char* src = xb + (__umul24(r, x_rowb) + x_chb);
                 v0 = *(const uint4*)src; v1 = *(const uint4*)(src + 16);
             }
-#else
-            v0 = v1 = make_uint4(r, 0x3c003c00u, 0x3c003c00u, 0x3c003c00u);                          // (ablation: no X traffic)
-#endif
             rx[k][0] = v0; rx[k][1] = v1;
         }
     };
@@ -191,11 +183,7 @@ __global__ __launch_bounds__(512) void conv_wgrad3x3_f8_kernel(const Wg8K p, con
         unsigned char* X = Xbuf + buf * XB;
         unsigned f = xs[k];
         asm volatile("" : "+v"(f));
-#if defined(UPS_W8_NO_QUANT)
-        const uint4 v = rx[k][0];                                                                     // (ablation: no conversion arithmetic)
-#else
         const uint4 v = quant16<F16IN, ACT>(rx[k][0], rx[k][1], sx, act_ns, amax);
-#endif
         if (k + 1 < NX || tid + 512 * k < NITEMS) *(uint4*)(X + (f & 0xffffu)) = v;
     };
     static_assert(NX == 2, "pipelined staging: two items per thread and unit");
@@ -252,11 +240,7 @@ __global__ __launch_bounds__(512) void conv_wgrad3x3_f8_kernel(const Wg8K p, con
             }
 #pragma unroll
             for (int jb = 0; jb < 4; ++jb)
-#if defined(UPS_W8_NO_MFMA)
-                acc[t][jb][0] += __int_as_float(fa[t & 1][jb] ^ fb[jb][t & 7]);                           // (ablation: no matrix work)
-#else
                 acc[t][jb] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(fa[t & 1], fb[jb], acc[t][jb], 0, 1, 0, 0x7f7f7f7f, 0, 0x7f7f7f7f);
-#endif
 #pragma unroll
             for (int jb = 0; jb < 4; ++jb) asm volatile("" : "+v"(acc[t][jb]));
             __builtin_amdgcn_sched_barrier(0);

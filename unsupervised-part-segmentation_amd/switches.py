@@ -9,8 +9,10 @@ behaviour is a function of an undocumented environment").
   longer exists).
 * kinds: `product` = a supported way to run (also reachable as a config key where one is named), `ab` = kept for A/B measurements of a
   decision that is documented in docs/design/, `test` = a hook the test-suite uses to reach a code path at small sizes, `debug`.
-* Compile-time forms (`-DUPS_ABLATE_*`, `-DUPS_W8_NO_*`, `-DUPS_PHASE_TIMING`, `-DUPS_ROWS_FWD_SIGN`, `-DUPS_ROWS_NO_FENCE` ...) are not
-  switches of the shipped library: they exist only in A/B builds made by tools/ab_build.sh and are listed in COMPILE_TIME below.
+* Compile-time forms (`-DUPS_ROWS_FWD_SIGN`, `-DUPS_ROWS_NO_FENCE`, `-DUPS_VMAX_BUILTIN`: the wrong-result investigation of
+  docs/design/rows_hazard.md) are not switches of the shipped library: they exist only in A/B builds made by tools/ab_build.sh and are
+  listed in COMPILE_TIME below.  The ablation and phase-timing instruments of the convolution kernels are no longer in the
+  sources: docs/design/kernel_instruments.diff restores them and names their -D flags.
 Retired in round 6 after measuring neutral twice (docs/design/negative_results.md): UPS_CRITICS_LATE, UPS_PRE_FREE, UPS_LAZY_SIDES,
 UPS_STREAM_ORDER; deleted with the code they selected: UPS_ROWS_DG, UPS_ROWS2_DG."""
 import os
@@ -72,9 +74,7 @@ SWITCHES = OrderedDict([
     ("UPS_UNPOOL_MFMA", ("1", "test", "partpath.hip", "0: the VALU form of unpool_bwd (the unit test compares both)")),
 ])
 
-COMPILE_TIME = ("UPS_ABLATE_BARRIER", "UPS_ABLATE_PATCHWAIT", "UPS_ABLATE_WWAIT", "UPS_EPI_PRIO", "UPS_ABLATE_DMA", "UPS_ABLATE_EPI", "UPS_ABLATE_GLOAD", "UPS_ABLATE_LSTORE", "UPS_ABLATE_MFMA", "UPS_F8S_WN1", "UPS_OCC2_FRAG2",
-                "UPS_PATCH_A2", "UPS_PHASE_TIMING", "UPS_W8_NO_DMA", "UPS_W8_NO_MFMA", "UPS_W8_NO_QUANT", "UPS_W8_NO_XLOAD", "UPS_WGRAD_NO_PIPE",
-                "UPS_ROWS_FWD_SIGN", "UPS_ROWS_NO_FENCE", "UPS_VMAX_BUILTIN")
+COMPILE_TIME = ("UPS_ROWS_FWD_SIGN", "UPS_ROWS_NO_FENCE", "UPS_VMAX_BUILTIN")
 NOT_SWITCHES = ("UPS_ABI_VERSION", "UPS_ACT_", "UPS_OK", "UPS_E_", "UPS_BF16", "UPS_F16", "UPS_F32", "UPS_CHECK_ARG", "UPS_LAUNCH_CHECK")
 
 
