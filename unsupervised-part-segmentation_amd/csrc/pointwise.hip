@@ -552,8 +552,27 @@ inline int grid_for(long long work, int cap = 16384) {
         UPS_LAUNCH_CHECK();                                                                               \
     } while (0)
 
+// The dtype contract of the streaming launchers: a code without a kernel instance is refused here, before anything is launched (an
+// fp16 tensor sent through the bf16 instance would be computed on its bits and returned as UPS_OK).  F32_BF16: launchers whose kernels
+// exist in fp32 and bf16 only; ANY: the three codes of the ABI.
+#define UPS_CHECK_DTYPE_F32_BF16(dtype)                                                                   \
+    do {                                                                                                  \
+        if ((dtype) != UPS_F32 && (dtype) != UPS_BF16) {                                                  \
+            ups_set_error("%s: dtype %d has no instance (f32 | bf16)", __func__, (int)(dtype));           \
+            return UPS_E_ARG;                                                                             \
+        }                                                                                                 \
+    } while (0)
+#define UPS_CHECK_DTYPE_ANY(dtype)                                                                        \
+    do {                                                                                                  \
+        if ((dtype) != UPS_F32 && (dtype) != UPS_BF16 && (dtype) != UPS_F16) {                            \
+            ups_set_error("%s: bad dtype %d", __func__, (int)(dtype));                                    \
+            return UPS_E_ARG;                                                                             \
+        }                                                                                                 \
+    } while (0)
+
 extern "C" int ups_bilinear2x_fwd(const void* x, void* y, int32_t dtype, int32_t n, int32_t h, int32_t w, int32_t c, void* stream) {
     UPS_CHECK_ARG(x && y && c % 8 == 0);
+    UPS_CHECK_DTYPE_ANY(dtype);
     const long long work = (long long)n * h * w * (c / (dtype == UPS_F32 ? 4 : 8));
     hipStream_t s = (hipStream_t)stream;
     if (dtype == UPS_F32) hipLaunchKernelGGL(bilinear2x_fwd_kernel<float>, dim3(grid_for(work)), dim3(256), 0, s, (const float*)x, (float*)y, n, h, w, c);
@@ -565,6 +584,7 @@ extern "C" int ups_bilinear2x_fwd(const void* x, void* y, int32_t dtype, int32_t
 extern "C" int ups_bilinear2x_fwd_act(const void* x, void* y, int32_t dtype, int32_t n, int32_t h, int32_t w, int32_t c, int32_t act,
                                       float slope, void* stream) {
     UPS_CHECK_ARG(x && y && c % 8 == 0 && slope >= 0.f && slope <= 1.f && act >= UPS_ACT_NONE && act <= UPS_ACT_RELU);
+    UPS_CHECK_DTYPE_ANY(dtype);
     const long long work = (long long)n * h * w * (c / (dtype == UPS_F32 ? 4 : 8));
     hipStream_t s = (hipStream_t)stream;
     const float ons = act == UPS_ACT_NONE ? -1.f : (act == UPS_ACT_LRELU ? slope : 0.f);
@@ -576,6 +596,7 @@ extern "C" int ups_bilinear2x_fwd_act(const void* x, void* y, int32_t dtype, int
 }
 extern "C" int ups_bilinear2x_bwd(const void* gy, void* gx, int32_t dtype, int32_t n, int32_t h, int32_t w, int32_t c, void* stream) {
     UPS_CHECK_ARG(gy && gx && c % 8 == 0);
+    UPS_CHECK_DTYPE_F32_BF16(dtype);
     const long long work = (long long)n * h * w * (c / (dtype == UPS_F32 ? 4 : 8));
     hipStream_t s = (hipStream_t)stream;
     if (dtype == UPS_F32) hipLaunchKernelGGL(bilinear2x_bwd_kernel<float>, dim3(grid_for(work)), dim3(256), 0, s, (const float*)gy, (float*)gx, n, h, w, c);
@@ -653,7 +674,7 @@ static int crop_launch(const void* src, void* dst, int32_t dtype, int32_t n, int
     const long long work = (long long)n * (bwd ? h : ho) * (bwd ? w : wo) * (c / (dtype == UPS_F32 ? 4 : 8));
     hipStream_t s = (hipStream_t)stream;
     if (dtype == UPS_F32) hipLaunchKernelGGL(crop_kernel<float>, dim3(grid_for(work)), dim3(256), 0, s, (const float*)src, (float*)dst, n, h, w, c, ho, wo, yx_dev, bwd);
-    else if (dtype == UPS_BF16 || dtype == UPS_F16)
+    else if (dtype == UPS_BF16 || dtype == UPS_F16)            // (fp16 moves through the bf16 instance: a bit copy of 16-bit words)
         hipLaunchKernelGGL(crop_kernel<bf16>, dim3(grid_for(work)), dim3(256), 0, s, (const bf16*)src, (bf16*)dst, n, h, w, c, ho, wo, yx_dev, bwd);
     else { ups_set_error("bad dtype %d", (int)dtype); return UPS_E_ARG; }
     UPS_LAUNCH_CHECK();
@@ -669,6 +690,7 @@ extern "C" int ups_crop_bwd(const void* gy, void* gx, int32_t dtype, int32_t n, 
 }
 extern "C" int ups_act_mean_fwd(const void* x, void* y, int32_t dtype, int32_t n, int32_t hw, int32_t c, int32_t act, float slope, void* stream) {
     UPS_CHECK_ARG(x && y);
+    UPS_CHECK_DTYPE_F32_BF16(dtype);
     hipStream_t s = (hipStream_t)stream;
     const int grid = ups_cdiv((long long)n * c, 256);
     if (dtype == UPS_F32) hipLaunchKernelGGL(act_mean_fwd_kernel<float>, dim3(grid), dim3(256), 0, s, (const float*)x, (float*)y, n, hw, c, act, slope);
@@ -678,6 +700,7 @@ extern "C" int ups_act_mean_fwd(const void* x, void* y, int32_t dtype, int32_t n
 }
 extern "C" int ups_act_mean_bwd(const void* x, const void* gy, void* gx, int32_t dtype, int32_t n, int32_t hw, int32_t c, int32_t act, float slope, void* stream) {
     UPS_CHECK_ARG(x && gy && gx);
+    UPS_CHECK_DTYPE_F32_BF16(dtype);
     hipStream_t s = (hipStream_t)stream;
     const int grid = ups_cdiv((long long)n * hw * c, 256);
     if (dtype == UPS_F32) hipLaunchKernelGGL(act_mean_bwd_kernel<float>, dim3(grid), dim3(256), 0, s, (const float*)x, (const float*)gy, (float*)gx, n, hw, c, act, slope);
@@ -702,6 +725,7 @@ extern "C" int ups_elu_bwd(const void* x, const void* gy, void* gx, int32_t dtyp
 }
 extern "C" int ups_maxpool2_fwd(const void* x, void* y, int32_t dtype, int32_t n, int32_t h, int32_t w, int32_t c, void* stream) {
     UPS_CHECK_ARG(x && y && c % 8 == 0 && h % 2 == 0 && w % 2 == 0);
+    UPS_CHECK_DTYPE_F32_BF16(dtype);
     const long long work = (long long)n * (h / 2) * (w / 2) * (c / (dtype == UPS_F32 ? 4 : 8));
     hipStream_t s = (hipStream_t)stream;
     if (dtype == UPS_F32) hipLaunchKernelGGL(maxpool2_fwd_kernel<float>, dim3(grid_for(work)), dim3(256), 0, s, (const float*)x, (float*)y, n, h, w, c);
@@ -723,6 +747,7 @@ extern "C" int ups_maxpool2_fwd_f8(const void* x, void* y, int32_t n, int32_t h,
 }
 extern "C" int ups_maxpool2_bwd(const void* x, const void* gy, void* gx, int32_t dtype, int32_t n, int32_t h, int32_t w, int32_t c, void* stream) {
     UPS_CHECK_ARG(x && gy && gx && c % 8 == 0 && h % 2 == 0 && w % 2 == 0);
+    UPS_CHECK_DTYPE_F32_BF16(dtype);
     const long long work = (long long)n * (h / 2) * (w / 2) * (c / (dtype == UPS_F32 ? 4 : 8));
     hipStream_t s = (hipStream_t)stream;
     if (dtype == UPS_F32) hipLaunchKernelGGL(maxpool2_bwd_kernel<float>, dim3(grid_for(work)), dim3(256), 0, s, (const float*)x, (const float*)gy, (float*)gx, n, h, w, c);
@@ -732,6 +757,7 @@ extern "C" int ups_maxpool2_bwd(const void* x, const void* gy, void* gx, int32_t
 }
 extern "C" int ups_copy_channels(const void* src, int32_t lds, void* dst, int32_t ldd, int32_t dtype, int64_t rows, int32_t c, void* stream) {
     UPS_CHECK_ARG(src && dst && c % 8 == 0 && lds % 8 == 0 && ldd % 8 == 0);
+    UPS_CHECK_DTYPE_ANY(dtype);          // (fp16 moves through the bf16 instance: a bit copy of 16-bit words)
     const long long work = (long long)rows * (c / (dtype == UPS_F32 ? 4 : 8));
     hipStream_t s = (hipStream_t)stream;
     if (dtype == UPS_F32) hipLaunchKernelGGL((copy_channels_kernel<float, false>), dim3(grid_for(work)), dim3(256), 0, s, (const float*)src, lds, (float*)dst, ldd, (long long)rows, c);
@@ -741,6 +767,7 @@ extern "C" int ups_copy_channels(const void* src, int32_t lds, void* dst, int32_
 }
 extern "C" int ups_add_channels(const void* src, int32_t lds, void* dst, int32_t ldd, int32_t dtype, int64_t rows, int32_t c, void* stream) {
     UPS_CHECK_ARG(src && dst && c % 8 == 0 && lds % 8 == 0 && ldd % 8 == 0);
+    UPS_CHECK_DTYPE_F32_BF16(dtype);
     const long long work = (long long)rows * (c / (dtype == UPS_F32 ? 4 : 8));
     hipStream_t s = (hipStream_t)stream;
     if (dtype == UPS_F32) hipLaunchKernelGGL((copy_channels_kernel<float, true>), dim3(grid_for(work)), dim3(256), 0, s, (const float*)src, lds, (float*)dst, ldd, (long long)rows, c);
@@ -750,6 +777,7 @@ extern "C" int ups_add_channels(const void* src, int32_t lds, void* dst, int32_t
 }
 extern "C" int ups_vgg_preprocess_fwd(const void* x, int32_t x_is_f32, int32_t ldx, void* y, int32_t dtype, int64_t pixels, void* stream) {
     UPS_CHECK_ARG(x && y && ldx >= 3);
+    UPS_CHECK_DTYPE_F32_BF16(dtype);
     hipStream_t s = (hipStream_t)stream;
     const int grid = ups_cdiv(pixels, 256);
     if (dtype == UPS_F32) hipLaunchKernelGGL((vgg_pre_fwd_kernel<float, float>), dim3(grid), dim3(256), 0, s, (const float*)x, ldx, (float*)y, (long long)pixels);
@@ -760,6 +788,7 @@ extern "C" int ups_vgg_preprocess_fwd(const void* x, int32_t x_is_f32, int32_t l
 }
 extern "C" int ups_vgg_preprocess_bwd(const void* gy, void* gx, int32_t dtype, int32_t ldgx, int64_t pixels, void* stream) {
     UPS_CHECK_ARG(gy && gx && ldgx >= 3);
+    UPS_CHECK_DTYPE_F32_BF16(dtype);
     hipStream_t s = (hipStream_t)stream;
     const int grid = ups_cdiv(pixels, 256);
     if (dtype == UPS_F32) hipLaunchKernelGGL(vgg_pre_bwd_kernel<float>, dim3(grid), dim3(256), 0, s, (const float*)gy, (float*)gx, ldgx, (long long)pixels);
@@ -769,6 +798,7 @@ extern "C" int ups_vgg_preprocess_bwd(const void* gy, void* gx, int32_t dtype, i
 }
 extern "C" int ups_l1_fwd(const void* a, const void* b, int32_t dtype, int64_t rows, int32_t c, int32_t ld, int32_t act, float* partial, int32_t nblocks, void* stream) {
     UPS_CHECK_ARG(a && b && partial && ld % 8 == 0 && c <= ld && nblocks >= 1);
+    UPS_CHECK_DTYPE_F32_BF16(dtype);
     hipStream_t s = (hipStream_t)stream;
     if (dtype == UPS_F32) hipLaunchKernelGGL(l1_fwd_kernel<float>, dim3(nblocks), dim3(256), 0, s, (const float*)a, (const float*)b, (long long)rows, c, ld, act, partial);
     else hipLaunchKernelGGL(l1_fwd_kernel<bf16>, dim3(nblocks), dim3(256), 0, s, (const bf16*)a, (const bf16*)b, (long long)rows, c, ld, act, partial);
@@ -777,6 +807,7 @@ extern "C" int ups_l1_fwd(const void* a, const void* b, int32_t dtype, int64_t r
 }
 extern "C" int ups_l1_bwd(const void* a, const void* b, void* gb, int32_t dtype, int64_t rows, int32_t c, int32_t ld, int32_t act, const float* scale_dev, float scale, void* stream) {
     UPS_CHECK_ARG(a && b && gb && ld % 8 == 0 && c <= ld);
+    UPS_CHECK_DTYPE_F32_BF16(dtype);
     const long long work = (long long)rows * (ld / (dtype == UPS_F32 ? 4 : 8));
     hipStream_t s = (hipStream_t)stream;
     if (dtype == UPS_F32) hipLaunchKernelGGL(l1_bwd_kernel<float>, dim3(grid_for(work)), dim3(256), 0, s, (const float*)a, (const float*)b, (float*)gb, (long long)rows, c, ld, act, scale_dev, scale);
@@ -810,6 +841,7 @@ extern "C" int ups_convert(const void* src, int32_t sd, void* dst, int32_t dd, i
 
 extern "C" int ups_pad_convert(const float* src, int32_t c, void* dst, int32_t dtype, int32_t ldd, int64_t rows, void* stream) {
     UPS_CHECK_ARG(src && dst && ldd >= c && rows >= 0);
+    UPS_CHECK_DTYPE_ANY(dtype);
     if (rows == 0) return UPS_OK;
     hipStream_t s = (hipStream_t)stream;
     const int grid = grid_for((long long)rows * ldd);
