@@ -392,23 +392,19 @@ int launch(const ups_conv_desc& dd, hipStream_t s) {
     int bn = ctot > 64 ? 128 : (ctot > 32 ? 64 : 32);
     if (bn == 128 && mtiles * ups_cdiv(ctot, 128) < 256) bn = 64;
     if (bn == 64 && mtiles * ups_cdiv(ctot, 64) < 256) bn = 32;
-    {   // UPS_IGEMM_FORCE="<bn>,<cps>": tuning override (one of 128,1 / 64,2 / 64,1 / 32,4 / 32,1)
-        static int fbn = -1, fcps = -1;
-        if (fbn < 0) {
-            const char* e = getenv("UPS_IGEMM_FORCE");
-            fbn = 0;
-            if (e) sscanf(e, "%d,%d", &fbn, &fcps);
-        }
-        if (fbn > 0) bn = fbn;
+    // UPS_IGEMM_FORCE="<bn>,<cps>": tuning override (one of 128,1 / 64,2 / 64,1 / 32,4 / 32,1), read once
+    static int fbn = -1, fcps = 0;
+    if (fbn < 0) {
+        const char* e = getenv("UPS_IGEMM_FORCE");
+        int a = 0, b = 0;
+        if (e && sscanf(e, "%d,%d", &a, &b) == 2 && b > 0) fcps = b;
+        fbn = a > 0 ? a : 0;
     }
+    if (fbn > 0) bn = fbn;
     const int ntn = ups_cdiv(ctot, bn);
     const bool skinny = mtiles * ntn < 1024 && d.ntaps * kchunks >= 8;
     int cps = !skinny ? 1 : (bn == 32 ? 4 : (bn == 64 ? 2 : 1));
-    {
-        const char* e = getenv("UPS_IGEMM_FORCE");
-        int a = 0, b = 0;
-        if (e && sscanf(e, "%d,%d", &a, &b) == 2 && b > 0) cps = b;
-    }
+    if (fcps > 0) cps = fcps;
     // split-K for latency-bound problems: few tiles, long K loop, workspace supplied.  Wider tiles + more blocks.
     d.ws = nullptr; d.splits = 1; d.stages_per_split = 0; d.ldw = 0;
     {
@@ -474,7 +470,6 @@ extern "C" int ups_sign_pack(const void* x, int32_t dtype, int64_t chunks, void*
 // so: ups_conv_sign_out_written() reports on the calling thread's last ups_conv_igemm call.
 thread_local int g_ups_sign_written = 0;        // (set to 1 by the launcher of a kernel that writes the bits)
 extern "C" int ups_conv_sign_out_written(void) { return g_ups_sign_written; }
-static int sign_out_pass(const ups_conv_desc* d, void* stream) { (void)d; (void)stream; return UPS_OK; }
 int ups_conv3x3_first_try(const ups_conv_desc* d, hipStream_t s);   // conv3x3_first.hip
 int ups_conv3x3_s2_try(const ups_conv_desc* d, hipStream_t s);      // conv3x3_s2.hip
 int ups_conv3x3_rows_try(const ups_conv_desc* d, hipStream_t s);    // conv3x3_rows.hip
@@ -518,7 +513,7 @@ extern "C" int ups_conv_igemm(const ups_conv_desc* d, void* stream) {
         }
         {
             const int sr = ups_conv3x3_s2_try(d, (hipStream_t)stream);
-            if (sr == 0) { UPS_LAUNCH_CHECK(); return sign_out_pass(d, stream); }
+            if (sr == 0) { UPS_LAUNCH_CHECK(); return UPS_OK; }
             if (sr < 0) { ups_set_error("ups_conv_igemm: stride-2 kernel launch setup failed"); return sr; }
         }
         // thin residual blocks on large batches of full-width rows: the row-streaming kernel; the K-deep logit convolution: its
@@ -554,5 +549,5 @@ extern "C" int ups_conv_igemm(const ups_conv_desc* d, void* stream) {
              : (d->dtype == UPS_F16 ? launch<f16>(*d, (hipStream_t)stream) : launch<bf16>(*d, (hipStream_t)stream));
     if (rc != UPS_OK) { ups_set_error("ups_conv_igemm: bad problem size"); return rc; }
     UPS_LAUNCH_CHECK();
-    return sign_out_pass(d, stream);
+    return UPS_OK;
 }

@@ -311,6 +311,37 @@ class Fp8State(object):
         """A producer keeps writing its copy only while somebody reads it: after two unread copies the site goes quiet."""
         return not (site.get("emitted", 0) >= 2 and site.get("used", 0) == 0)
 
+    def site(self, holder, key, device, e5m2=False, layer=None):
+        """The producer site stored at holder[key] (made on first use: its scale slot and the step it was born in), or None once
+        the site has gone quiet (``wanted``).  e5m2: the copy is a gradient's, its slot takes that format's range.  layer: the
+        holder is that layer's cache -- the site then records this state's generation and is read back through ``layer_entry``.
+        Open: the point-wise sites (BilinearFn, MaxPoolFn: holder = a dict owned by the Scope) carry no generation guard."""
+        so = holder.get(key) if layer is None else self.layer_entry(layer, key)
+        if so is None:
+            so = holder[key] = {"slot": self.slot(device), "born": self.steps}
+            if layer is not None:
+                so["gen"] = self.generation
+            if e5m2:
+                self.fmax[so["slot"]] = self.E5M2_MAX
+        return so if self.wanted(so) else None
+
+    def emit(self, site, shape, device):
+        """The uint8 tensor this launch writes the site's copy into, or None in the step the site was born in (the launch then only
+        records the maximum: the delayed scale of the tensor exists one ``update()`` later)."""
+        if self.steps <= site["born"]:
+            return None
+        site["emitted"] = site.get("emitted", 0) + 1
+        return torch.empty(shape, dtype=torch.uint8, device=device)
+
+    @staticmethod
+    def handle(site, t, act=None):
+        """What a producer hands on: ``next_in`` / ``last_out`` (act = the activation the copy was quantised behind) or, without
+        `act`, the argument of ``register_grad_copy``."""
+        h = {"t": t, "slot": site["slot"], "site": site}
+        if act is not None:
+            h["act"] = act
+        return h
+
     @staticmethod
     def mark_used(copy):
         site = copy.get("site")
@@ -622,6 +653,81 @@ def _attach_ws(d, device):
     d.workspace, d.workspace_bytes = ws.data_ptr(), ws.numel()
 
 
+def _conv_desc(dcode, src, in_dims, w, out, out_dims, taps, kh, kw, slope, in_stride=1, lattice=None):
+    """The fields every ups_conv_desc shares; all others start at zero / NULL.  in_dims = (n, hi, wi, ci, ldi) of `src`;
+    out_dims = (ho, wo, co, co_fill, ldo): the ho x wo results of the kh x kw taps = (dy, dx, weight index) land in `out` densely
+    or, with lattice = (out_h, out_w, stride, oy, ox), on every stride-th pixel from (oy, ox) of an out_h x out_w tensor."""
+    d = L.ConvDesc()
+    d.dtype = dcode
+    d.n, d.hi, d.wi, d.ci, d.ldi = in_dims
+    d.ho, d.wo, d.co, d.co_fill, d.ldo = out_dims
+    out_h, out_w, st, oy, ox = lattice if lattice is not None else (d.ho, d.wo, 1, 0, 0)
+    d.out_h, d.out_w, d.out_sy, d.out_sx, d.out_oy, d.out_ox = out_h, out_w, st, st, oy, ox
+    d.in_sy = d.in_sx = in_stride
+    _fill_taps(d, taps[0], taps[1], taps[2], kh * kw)
+    d.kh, d.kw = kh, kw
+    d.act_slope = slope
+    d.in_, d.w, d.out = src.data_ptr(), w.data_ptr(), out.data_ptr() if out is not None else None
+    _attach_ws(d, src.device)
+    return d
+
+
+def _attach_dgrad(d, layer, x, x_bits, res):
+    """Epilogue of an input-gradient launch: gx = act'(x) * (what the taps summed) (+ res); act' off x or off its sign bytes."""
+    d.dact_kind = layer.act_in
+    d.ldd = x.shape[-1]
+    if layer.act_in != L.ACT_NONE:
+        d.dact = x.data_ptr()
+        d.dact_bits = x_bits.data_ptr() if x_bits is not None else None
+    if res is not None:
+        d.res, d.ldr = res.data_ptr(), res.shape[-1]
+
+
+def _attach_f8_operand(d, prepare, t, src, stat):
+    """The fp8 kernel's operands.  src (a producer's copy of the input tensor `t`, or None): its bytes and the scale they were
+    written with; without one the kernel quantises `t` with this layer's delayed scale and records the maximum.  prepare:
+    layer.prepared_f8 (stat "fwd") / layer.prepared_f8_grad ("dgrad"): the e4m3 weights and their dequantisation factors."""
+    if src is not None:
+        f8 = prepare(None)
+        Fp8.stats[stat + "_copy_in"] += 1
+        Fp8.mark_used(src)
+        d.in_f8 = src["t"].data_ptr()
+        d.f8_scale = Fp8.scale[src["slot"]:].data_ptr()
+    else:
+        f8 = prepare(t)
+        d.f8_scale = Fp8.scale[f8["slot"]:].data_ptr()
+        d.f8_amax = Fp8.amax[f8["slot"]].data_ptr()
+    d.w = f8["w"].data_ptr()
+    d.f8_deq = f8["deq"].data_ptr()
+    Fp8.stats[stat + "_f8"] += 1
+
+
+def _attach_f8_copy(d, site, shape, device, stat):
+    """The epilogue records the output's maximum in the site's slot and, once its delayed scale exists, writes the fp8 copy:
+    returns that tensor or None."""
+    d.out_f8_amax = Fp8.amax[site["slot"]].data_ptr()
+    t8 = Fp8.emit(site, shape, device)
+    if t8 is not None:
+        d.out_f8, d.out_f8_scale = t8.data_ptr(), Fp8.scale[site["slot"]:].data_ptr()
+        Fp8.stats[stat] += 1
+    return t8
+
+
+def _launch_conv(d, layer, kind=None, flops=None):
+    """ups_conv_igemm on the current stream.  kind ("fwd" / "dgrad"): a launch bench.py's roofline times when it watches this layer."""
+    if kind is not None and KernelTimer.layer == layer.name and KernelTimer.active():
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        L.call("ups_conv_igemm", C.byref(d), L.stream())
+        e1.record()
+        KernelTimer.events.append((e0, e1))
+        KernelTimer.kinds.append(kind)
+        if flops is not None:
+            KernelTimer.flops = flops
+    else:
+        L.call("ups_conv_igemm", C.byref(d), L.stream())
+
+
 def conv_forward(x, layer, res=None, out_f32=False, ldo=None, co_fill=None, mask=None, fmt=None, res_post=False):
     """out = conv(act(x) (+coords), V) + b (+ res);  x [n,hi,wi,ldi].
     fmt = L.F16: x, res and (unless out_f32) out hold fp16 in bf16 containers (module docstring).
@@ -637,59 +743,32 @@ def conv_forward(x, layer, res=None, out_f32=False, ldo=None, co_fill=None, mask
     ldo = ldo if ldo is not None else (layer.co if out_f32 else round8(layer.co))
     co_fill = co_fill if co_fill is not None else ldo
     out = torch.empty((n, ho, wo, ldo), dtype=torch.float32 if out_f32 else x.dtype, device=x.device)
-    d = L.ConvDesc()
-    f8_out = None
-    d.dtype = dcode
-    d.n, d.hi, d.wi, d.ci, d.ldi = n, hi, wi, round8(layer.ci_log), ldi
-    d.ho, d.wo, d.co, d.co_fill, d.ldo = ho, wo, layer.co, co_fill, ldo
-    d.out_h, d.out_w, d.out_sy, d.out_sx, d.out_oy, d.out_ox = ho, wo, 1, 1, 0, 0
-    d.in_sy = d.in_sx = layer.stride
-    dy, dx, tw = layer.fwd_taps(hi, wi)
-    _fill_taps(d, dy, dx, tw, layer.k * layer.k)
-    d.kh = d.kw = layer.k
-    d.act_in, d.act_slope, d.out_f32, d.dact_kind = (L.ACT_NONE if layer.in_post else layer.act_in), layer.slope, int(out_f32), 0
+    d = _conv_desc(dcode, x, (n, hi, wi, round8(layer.ci_log), ldi), ent["w_fwd"], out, (ho, wo, layer.co, co_fill, ldo),
+                   layer.fwd_taps(hi, wi), layer.k, layer.k, layer.slope, in_stride=layer.stride)
+    d.act_in, d.out_f32 = (L.ACT_NONE if layer.in_post else layer.act_in), int(out_f32)
     d.out_act = layer.out_act
-    d.res_act = layer.act_in if (res is not None and res_post) else L.ACT_NONE       # residual stored as act(x): inverted in the epilogue
-    assert not (d.res_act and layer.act_in != L.ACT_LRELU), "only a leaky-ReLU residual can be stored post-activation"
-    d.ldr = res.shape[-1] if res is not None else 0
-    d.ldd = 0
-    d.in_, d.w, d.out = x.data_ptr(), ent["w_fwd"].data_ptr(), out.data_ptr()
     d.bias = layer.b.data_ptr()
     d.coord_tab = ent["ctab"].data_ptr() if layer.coords else None
-    d.res = res.data_ptr() if res is not None else None
-    d.dact = None
+    if res is not None:
+        d.res, d.ldr = res.data_ptr(), res.shape[-1]
+        d.res_act = layer.act_in if res_post else L.ACT_NONE       # residual stored as act(x): inverted in the epilogue
+        assert not (d.res_act and layer.act_in != L.ACT_LRELU), "only a leaky-ReLU residual can be stored post-activation"
+    f8_out = None
     if mask is not None:
         d.mask_bits, d.mask_batch = mask[0].data_ptr(), x.shape[0]
     elif dcode != L.F16 and Fp8.eligible(layer, x) and (not Fp8.copy_only() or Fp8.usable(Fp8.next_in, layer, x, ldi)):
         src, want_act = Fp8.next_in, Fp8.next_out_act
-        if Fp8.usable(src, layer, x, ldi):
-            f8 = layer.prepared_f8(None)               # the producer quantised act(x) with its tensor's scale
-            Fp8.stats["fwd_copy_in"] += 1
-            Fp8.mark_used(src)
-            d.in_f8 = src["t"].data_ptr()
-            d.f8_scale = Fp8.scale[src["slot"]:].data_ptr()
-        else:
-            f8 = layer.prepared_f8(x)
-            d.f8_scale = Fp8.scale[f8["slot"]:].data_ptr()
-            d.f8_amax = Fp8.amax[f8["slot"]].data_ptr()
-        d.w = f8["w"].data_ptr()
-        d.f8_deq = f8["deq"].data_ptr()
-        Fp8.stats["fwd_f8"] += 1
+        # (a usable copy: the producer quantised act(x) with its tensor's scale)
+        _attach_f8_operand(d, layer.prepared_f8, x, src if Fp8.usable(src, layer, x, ldi) else None, "fwd")
         if Fp8.PRODUCER and want_act is not None and not out_f32 and ldo % 64 == 0 and co_fill == ldo:
-            eo = Fp8.layer_entry(layer, "f8o")
-            if eo is None:
-                eo = layer._cache["f8o"] = {"slot": Fp8.slot(x.device), "born": Fp8.steps, "gen": Fp8.generation}
-            if Fp8.wanted(eo):
-                d.out_f8_amax = Fp8.amax[eo["slot"]].data_ptr()
+            eo = Fp8.site(layer._cache, "f8o", x.device, layer=layer)
+            if eo is not None:
                 # a post-activation output already holds want_act(out): its copy is the quantisation of the stored value
                 assert not layer.out_act or layer.out_act == want_act
                 d.out_f8_act = L.ACT_NONE if layer.out_act else want_act
-                if Fp8.steps > eo["born"]:                 # its delayed scale exists
-                    t8 = torch.empty(out.shape, dtype=torch.uint8, device=x.device)
-                    d.out_f8, d.out_f8_scale = t8.data_ptr(), Fp8.scale[eo["slot"]:].data_ptr()
-                    f8_out = {"t": t8, "act": want_act, "slot": eo["slot"], "site": eo}
-                    eo["emitted"] = eo.get("emitted", 0) + 1
-                    Fp8.stats["fwd_copy_out"] += 1
+                t8 = _attach_f8_copy(d, eo, out.shape, x.device, "fwd_copy_out")
+                if t8 is not None:
+                    f8_out = Fp8.handle(eo, t8, want_act)
     Fp8.next_in = Fp8.next_out_act = None
     Fp8.last_out = f8_out
     SignBits.last = None
@@ -697,18 +776,8 @@ def conv_forward(x, layer, res=None, out_f32=False, ldo=None, co_fill=None, mask
         SignBits.last = torch.empty((n, ho, wo, ldo // 8), dtype=torch.uint8, device=x.device)
         d.sign_out = SignBits.last.data_ptr()
     SignBits.want = False
-    _attach_ws(d, x.device)
     assert round8(layer.ci_log) <= ldi, (layer.name, layer.ci_log, ldi)
-    if KernelTimer.layer == layer.name and KernelTimer.active():
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        L.call("ups_conv_igemm", C.byref(d), L.stream())
-        e1.record()
-        KernelTimer.events.append((e0, e1))
-        KernelTimer.kinds.append("fwd")
-        KernelTimer.flops = 2.0 * n * ho * wo * layer.k * layer.k * layer.cin_v * layer.co
-    else:
-        L.call("ups_conv_igemm", C.byref(d), L.stream())
+    _launch_conv(d, layer, "fwd", 2.0 * n * ho * wo * layer.k * layer.k * layer.cin_v * layer.co)
     if SignBits.last is not None and not L.load().ups_conv_sign_out_written():
         SignBits.last = None            # the launch went to a kernel that does not write them (best effort: upsparts_hip.h)
     return out
@@ -745,26 +814,12 @@ def conv_dgrad(g, x, layer, res=None, mask_view=None, n_parts=0, f8_src="pop", x
     if cd2s:
         # one stride-1 3x3 convolution over the gradient lattice with 4 C channels (parity class, channel), written
         # depth-to-space: g is read once and whole output rows are stored (the per-class launches below store every other pixel)
-        d = L.ConvDesc()
-        d.dtype = dcode
-        d.n, d.hi, d.wi, d.ci, d.ldi = n, ho, wo, round8(layer.co), g.shape[-1]
-        d.ho, d.wo, d.co, d.co_fill, d.ldo = ho, wo, 4 * cd2s, 4 * cd2s, ldi
-        d.out_h, d.out_w, d.out_sy, d.out_sx, d.out_oy, d.out_ox = hi, wi, 1, 1, 0, 0
-        d.in_sy = d.in_sx = 1
-        _fill_taps(d, [t // 3 - 1 for t in range(9)], [t % 3 - 1 for t in range(9)], list(range(9)), 9)
-        d.kh = d.kw = 3
-        d.act_in, d.act_slope, d.out_f32 = 0, layer.slope, 0
-        d.dact_kind = layer.act_in
-        d.ldr = res.shape[-1] if res is not None else 0
-        d.ldd = ldi
-        d.in_, d.w, d.out = g.data_ptr(), layer.prepared_d2s(hi, wi)["w"].data_ptr(), gx.data_ptr()
-        d.bias, d.coord_tab = None, None
-        d.res = res.data_ptr() if res is not None else None
-        d.dact = x.data_ptr() if layer.act_in != L.ACT_NONE else None
-        d.dact_bits = x_bits.data_ptr() if (x_bits is not None and d.dact) else None
+        d = _conv_desc(dcode, g, (n, ho, wo, round8(layer.co), g.shape[-1]), layer.prepared_d2s(hi, wi)["w"], gx,
+                       (ho, wo, 4 * cd2s, 4 * cd2s, ldi), ([t // 3 - 1 for t in range(9)], [t % 3 - 1 for t in range(9)], range(9)),
+                       3, 3, layer.slope, lattice=(hi, wi, 1, 0, 0))
+        _attach_dgrad(d, layer, x, x_bits, res)
         d.d2s = cd2s
-        _attach_ws(d, x.device)
-        L.call("ups_conv_igemm", C.byref(d), L.stream())
+        _launch_conv(d, layer)
         return gx
     classes = [(0, 0)] if st == 1 else [(py, px) for py in range(st) for px in range(st)]
     for (py, px) in classes:
@@ -780,26 +835,11 @@ def conv_dgrad(g, x, layer, res=None, mask_view=None, n_parts=0, f8_src="pop", x
                 if (px + pbx - s) % st:
                     continue
                 dy.append((py + pby - r) // st); dx.append((px + pbx - s) // st); tw.append(r * k + s)
-        d = L.ConvDesc()
-        d.dtype = dcode
-        d.n, d.hi, d.wi, d.ci, d.ldi = n_img, ho, wo, round8(layer.co), g.shape[-1]
-        d.ho, d.wo, d.co, d.co_fill, d.ldo = lat_h, lat_w, layer.ci_log, ldi, ldi
-        d.out_h, d.out_w, d.out_sy, d.out_sx, d.out_oy, d.out_ox = hi, wi, st, st, py, px
-        d.in_sy = d.in_sx = 1
-        if not dy:      # no tap reaches this parity class: gradient is zero there (still apply res)
-            dy, dx, tw = [0], [0], [0]
+        if not dy:      # no tap reaches this parity class
             raise L.UpsError("empty tap class is not expected for k=3/k=1 'SAME' convolutions")
-        _fill_taps(d, dy + [0] * 9, dx + [0] * 9, tw + [0] * 9, len(dy))
-        d.kh, d.kw = 1, len(dy)
-        d.act_in, d.act_slope, d.out_f32 = 0, layer.slope, 0
-        d.dact_kind = layer.act_in
-        d.ldr = res.shape[-1] if res is not None else 0
-        d.ldd = ldi
-        d.in_, d.w, d.out = g.data_ptr(), ent["w_dgrad"].data_ptr(), gx.data_ptr() if gx is not None else None
-        d.bias, d.coord_tab = None, None
-        d.res = res.data_ptr() if res is not None else None
-        d.dact = x.data_ptr() if layer.act_in != L.ACT_NONE else None
-        d.dact_bits = x_bits.data_ptr() if (x_bits is not None and d.dact) else None
+        d = _conv_desc(dcode, g, (n_img, ho, wo, round8(layer.co), g.shape[-1]), ent["w_dgrad"], gx,
+                       (lat_h, lat_w, layer.ci_log, ldi, ldi), (dy, dx, tw), 1, len(dy), layer.slope, lattice=(hi, wi, st, py, px))
+        _attach_dgrad(d, layer, x, x_bits, res)
         if mask_view is not None:
             d.mask_grad, d.mask_view, d.mask_batch = g_hard.data_ptr(), mask_view.data_ptr(), n
         elif st == 1 and Fp8.enabled and Fp8.GRAD and g.dtype == torch.bfloat16:
@@ -808,48 +848,21 @@ def conv_dgrad(g, x, layer, res=None, mask_view=None, n_parts=0, f8_src="pop", x
             src_ok = use_f8 and src is not None and layer.ci_log > 32 and g.shape[-1] % 16 == 0
             emit = False
             if use_f8 and (src_ok or not Fp8.copy_only()):
-                if src_ok:
-                    f8 = layer.prepared_f8_grad(None)      # the producer wrote e5m2(g * scale) in its epilogue
-                    Fp8.stats["dgrad_copy_in"] += 1
-                    Fp8.mark_used(src)
-                    d.in_f8 = src["t"].data_ptr()
-                    d.f8_scale = Fp8.scale[src["slot"]:].data_ptr()
-                else:
-                    f8 = layer.prepared_f8_grad(g)
-                    d.f8_scale = Fp8.scale[f8["slot"]:].data_ptr()
-                    d.f8_amax = Fp8.amax[f8["slot"]].data_ptr()
-                d.w = f8["w"].data_ptr()
-                d.f8_deq = f8["deq"].data_ptr()
+                # (a copy in hand: the producer wrote e5m2(g * scale) in its epilogue)
+                _attach_f8_operand(d, layer.prepared_f8_grad, g, src if src_ok else None, "dgrad")
                 d.f8_e5m2 = 1
-                Fp8.stats["dgrad_f8"] += 1
                 emit = True
             elif layer.k == 3 and round8(layer.co) <= 32 and hi % 16 == 0 and wi % 16 == 0:
                 emit = True     # a bf16 launch off the 128-wide two-blocks-per-CU instance (the P-channel head): it can write the copy
             if emit and Fp8.PRODUCER and gx is not None and ldi % 64 == 0 and layer.ci_log == ldi:
-                eo = Fp8.layer_entry(layer, "f8go")
-                if eo is None:
-                    eo = layer._cache["f8go"] = {"slot": Fp8.slot(x.device), "born": Fp8.steps, "gen": Fp8.generation}
-                    Fp8.fmax[eo["slot"]] = Fp8.E5M2_MAX
-                if Fp8.wanted(eo):
-                    d.out_f8_amax = Fp8.amax[eo["slot"]].data_ptr()
+                eo = Fp8.site(layer._cache, "f8go", x.device, e5m2=True, layer=layer)
+                if eo is not None:
                     d.out_f8_act, d.out_f8_e5m2 = L.ACT_NONE, 1
-                    if Fp8.steps > eo["born"]:
-                        t8 = torch.empty(gx.shape, dtype=torch.uint8, device=x.device)
-                        d.out_f8, d.out_f8_scale = t8.data_ptr(), Fp8.scale[eo["slot"]:].data_ptr()
-                        Fp8.register_grad_copy(gx, {"t": t8, "slot": eo["slot"], "site": eo})
-                        eo["emitted"] = eo.get("emitted", 0) + 1
-                        Fp8.stats["dgrad_copy_out"] += 1
-        _attach_ws(d, x.device)
+                    t8 = _attach_f8_copy(d, eo, gx.shape, x.device, "dgrad_copy_out")
+                    if t8 is not None:
+                        Fp8.register_grad_copy(gx, Fp8.handle(eo, t8))
         assert round8(layer.co) <= g.shape[-1]
-        if KernelTimer.layer == layer.name and KernelTimer.active() and st == 1:
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            L.call("ups_conv_igemm", C.byref(d), L.stream())
-            e1.record()
-            KernelTimer.events.append((e0, e1))
-            KernelTimer.kinds.append("dgrad")
-        else:
-            L.call("ups_conv_igemm", C.byref(d), L.stream())
+        _launch_conv(d, layer, "dgrad" if st == 1 else None)
     return gx if mask_view is None else g_hard
 
 
@@ -1105,21 +1118,11 @@ def deconv_forward(x, layer, fmt=None, one_launch=None):
             for ky, oy in _DECONV_TAPS[py]:
                 for kx, ox in _DECONV_TAPS[px]:
                     dy.append(oy); dx.append(ox); tw.append(3 * ky + kx)
-            d = L.ConvDesc()
-            d.dtype = fcode
-            d.n, d.hi, d.wi, d.ci, d.ldi = n, hi, wi, ci, ldi
-            d.ho, d.wo, d.co, d.co_fill, d.ldo = hi, wi, nf, ldo, ldo
-            d.out_h, d.out_w, d.out_sy, d.out_sx, d.out_oy, d.out_ox = 2 * hi, 2 * wi, 2, 2, py, px
-            d.in_sy = d.in_sx = 1
-            _fill_taps(d, dy + [0] * 9, dx + [0] * 9, tw + [0] * 9, len(dy))
-            d.kh, d.kw = len(_DECONV_TAPS[py]), len(_DECONV_TAPS[px])
-            d.act_in, d.act_slope, d.out_f32, d.dact_kind = L.ACT_NONE, 0.2, 0, 0
-            d.ldr = d.ldd = 0
-            d.in_, d.w, d.out = x.data_ptr(), ent["w_fwd"].data_ptr(), out.data_ptr()
+            d = _conv_desc(fcode, x, (n, hi, wi, ci, ldi), ent["w_fwd"], out, (hi, wi, nf, ldo, ldo), (dy, dx, tw),
+                           len(_DECONV_TAPS[py]), len(_DECONV_TAPS[px]), 0.2, lattice=(2 * hi, 2 * wi, 2, py, px))
             d.bias = layer.b.data_ptr()
             d.coord_tab = ctab[2 * py + px].data_ptr() if ctab is not None else None
-            _attach_ws(d, x.device)
-            L.call("ups_conv_igemm", C.byref(d), L.stream())
+            _launch_conv(d, layer)
     return out
 
 
@@ -1129,21 +1132,10 @@ def deconv_dgrad(g, x, layer, fmt=None):
     n, hi, wi, ldi = x.shape
     ent = _deconv_ent(layer, x, fmt)
     gx = torch.empty_like(x)
-    d = L.ConvDesc()
-    d.dtype = _dx_code(x)
-    d.n, d.hi, d.wi, d.ci, d.ldi = n, 2 * hi, 2 * wi, round8(layer.co), g.shape[-1]
-    d.ho, d.wo, d.co, d.co_fill, d.ldo = hi, wi, layer.ci_log, ldi, ldi
-    d.out_h, d.out_w, d.out_sy, d.out_sx, d.out_oy, d.out_ox = hi, wi, 1, 1, 0, 0
-    d.in_sy = d.in_sx = 2
-    _fill_taps(d, [t // 3 for t in range(9)], [t % 3 for t in range(9)], list(range(9)), 9)     # pad 0 before (even 2hi)
-    d.kh = d.kw = 3
-    d.act_in, d.act_slope, d.out_f32, d.dact_kind = L.ACT_NONE, 0.2, 0, 0
-    d.ldr = d.ldd = 0
-    d.in_, d.w, d.out = g.data_ptr(), ent["w_dx"].data_ptr(), gx.data_ptr()
-    d.bias, d.coord_tab, d.res, d.dact = None, None, None, None
-    _attach_ws(d, x.device)
     assert round8(layer.co) <= g.shape[-1]
-    L.call("ups_conv_igemm", C.byref(d), L.stream())
+    d = _conv_desc(_dx_code(x), g, (n, 2 * hi, 2 * wi, round8(layer.co), g.shape[-1]), ent["w_dx"], gx, (hi, wi, layer.ci_log, ldi, ldi),
+                   ([t // 3 for t in range(9)], [t % 3 for t in range(9)], range(9)), 3, 3, 0.2, in_stride=2)   # pad 0 before (even 2hi)
+    _launch_conv(d, layer)
     return gx
 
 
@@ -1262,18 +1254,12 @@ class BilinearFn(torch.autograd.Function):
                 L.call("ups_bilinear2x_fwd_act", L.ptr(x), L.ptr(y), L.dt(x) if fmt is None else fmt, n, h, w, c, out_act, slope, L.stream())
             SignBits.want = False
             return y
-        f8 = f8_site and fmt != L.F16
-        if f8 and "fwd" not in site:
-            site["fwd"] = {"slot": Fp8.slot(x.device), "born": Fp8.steps}
-        f8 = f8 and Fp8.wanted(site["fwd"])
-        if f8:
-            so = site["fwd"]
-            t8 = torch.empty(y.shape, dtype=torch.uint8, device=x.device) if Fp8.steps > so["born"] else None
-            if t8 is not None:
-                so["emitted"] = so.get("emitted", 0) + 1
-            L.call("ups_bilinear2x_fwd_f8", L.ptr(x), L.ptr(y), n, h, w, c, L.ptr(t8) if t8 is not None else None,
+        so = Fp8.site(site, "fwd", x.device) if (f8_site and fmt != L.F16) else None
+        if so is not None:
+            t8 = Fp8.emit(so, y.shape, x.device)
+            L.call("ups_bilinear2x_fwd_f8", L.ptr(x), L.ptr(y), n, h, w, c, L.ptr(t8),
                    L.ptr(Fp8.scale[so["slot"]:]), L.ptr(Fp8.amax[so["slot"]]), act, slope, 0, L.stream())
-            Fp8.last_out = {"t": t8, "act": act, "slot": so["slot"], "site": so} if t8 is not None else None
+            Fp8.last_out = Fp8.handle(so, t8, act) if t8 is not None else None
         else:
             L.call("ups_bilinear2x_fwd", L.ptr(x), L.ptr(y), L.dt(x) if fmt is None else fmt, n, h, w, c, L.stream())
         return y
@@ -1286,20 +1272,13 @@ class BilinearFn(torch.autograd.Function):
         site = ctx.site
         so = None
         if site is not None and Fp8.GRAD and g.dtype == torch.bfloat16 and h % 16 == 0:
-            so = site.get("bwd")
-            if so is None:
-                so = site["bwd"] = {"slot": Fp8.slot(g.device), "born": Fp8.steps}
-                Fp8.fmax[so["slot"]] = Fp8.E5M2_MAX
-            if not Fp8.wanted(so):
-                so = None
+            so = Fp8.site(site, "bwd", g.device, e5m2=True)
         if so is not None:
-            t8 = torch.empty(gx.shape, dtype=torch.uint8, device=g.device) if Fp8.steps > so["born"] else None
-            if t8 is not None:
-                so["emitted"] = so.get("emitted", 0) + 1
-            L.call("ups_bilinear2x_bwd_f8", L.ptr(g), L.ptr(gx), n, h, w, c, L.ptr(t8) if t8 is not None else None,
+            t8 = Fp8.emit(so, gx.shape, g.device)
+            L.call("ups_bilinear2x_bwd_f8", L.ptr(g), L.ptr(gx), n, h, w, c, L.ptr(t8),
                    L.ptr(Fp8.scale[so["slot"]:]), L.ptr(Fp8.amax[so["slot"]]), 1, L.stream())
             if t8 is not None:
-                Fp8.register_grad_copy(gx, {"t": t8, "slot": so["slot"], "site": so})
+                Fp8.register_grad_copy(gx, Fp8.handle(so, t8))
         else:
             L.call("ups_bilinear2x_bwd", L.ptr(g), L.ptr(gx), L.dt(g), n, h, w, c, L.stream())
         return gx, None, None, None, None, None
@@ -1424,7 +1403,7 @@ class EluFn(torch.autograd.Function):
 
 class MaxPoolFn(torch.autograd.Function):
     """site (fp8 mode): per-call-site state when the pooled tensor feeds an fp8 convolution -- the forward then also writes the
-    e4m3 copy of act(y) (ops.Fp8 hand-off, as BilinearFn); `act` = the activation-on-load of that consumer."""
+    e4m3 copy of act(y) (ops.Fp8 hand-off: Fp8State.site / emit); `act` = the activation-on-load of that consumer."""
 
     @staticmethod
     def forward(ctx, x, site=None, act=0):
@@ -1433,18 +1412,12 @@ class MaxPoolFn(torch.autograd.Function):
         y = torch.empty((n, h // 2, w // 2, c), dtype=x.dtype, device=x.device)
         f8 = (site is not None and Fp8.enabled and Fp8.PRODUCER and x.dtype == torch.bfloat16 and c % 64 == 0
               and (h // 2) % 16 == 0 and (w // 2) % 16 == 0)
-        if f8:
-            so = site.get("fwd")
-            if so is None:
-                so = site["fwd"] = {"slot": Fp8.slot(x.device), "born": Fp8.steps}
-            f8 = Fp8.wanted(so)
-        if f8:
-            t8 = torch.empty(y.shape, dtype=torch.uint8, device=x.device) if Fp8.steps > so["born"] else None
-            if t8 is not None:
-                so["emitted"] = so.get("emitted", 0) + 1
-            L.call("ups_maxpool2_fwd_f8", L.ptr(x), L.ptr(y), n, h, w, c, L.ptr(t8) if t8 is not None else None,
+        so = Fp8.site(site, "fwd", x.device) if f8 else None
+        if so is not None:
+            t8 = Fp8.emit(so, y.shape, x.device)
+            L.call("ups_maxpool2_fwd_f8", L.ptr(x), L.ptr(y), n, h, w, c, L.ptr(t8),
                    L.ptr(Fp8.scale[so["slot"]:]), L.ptr(Fp8.amax[so["slot"]]), act, 0.2, L.stream())
-            Fp8.last_out = {"t": t8, "act": act, "slot": so["slot"], "site": so} if t8 is not None else None
+            Fp8.last_out = Fp8.handle(so, t8, act) if t8 is not None else None
         else:
             L.call("ups_maxpool2_fwd", L.ptr(x), L.ptr(y), L.dt(x), n, h, w, c, L.stream())
         ctx.save_for_backward(x)
