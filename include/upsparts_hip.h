@@ -398,6 +398,13 @@ int ups_mask_parts_fwd(const float* view, const float* hard, void* out, int32_t 
 int ups_mask_parts_bwd(const float* view, const void* g_out, float* g_hard, int32_t dtype, int32_t B, int64_t hw, int32_t P, void* stream);
 /* unpool_features + concat (M:225-249, 482-484): out[b][pix][f] = sum_p hard*feat[b][p][f]; out[..][F+p] = hard; pad zero */
 int ups_unpool_fwd(const float* hard, const float* feat, void* out, int32_t dtype, int32_t B, int64_t hw, int32_t P, int32_t F, int32_t ldo, void* stream);
+/* mixed unpool (appearance transfer; inference only, no backward): hard [n,hw,P], feat [m,P,F] fp32, pose_idx [K], app_idx [K*P]
+ * int32 DEVICE arrays with 0 <= pose_idx < n, 0 <= app_idx < m (the caller validates them: the kernel does not), out [K,hw,ldo]:
+ *   out[k][pix][f] = sum_p hard[pose_idx[k]][pix][p] * feat[app_idx[k*P+p]][p][f];  out[k][pix][F+p] = hard[pose_idx[k]][pix][p];
+ *   channels [F+P, ldo) zero.  Bit-identical to ups_unpool_fwd on explicitly gathered inputs.  K >= 1, ldo % 8 == 0, ldo >= F+P,
+ *   F % 8 == 0, feat and out 16-byte aligned (the feature rows are gathered with 16-byte loads): UPS_E_ARG otherwise. */
+int ups_unpool_mix_fwd(const float* hard, const float* feat, const int32_t* pose_idx, const int32_t* app_idx, void* out, int32_t dtype,
+                       int32_t K, int32_t n, int32_t m, int64_t hw, int32_t P, int32_t F, int32_t ldo, void* stream);
 /* g_hard[b][pix][p] = sum_f g[..f]*feat[b][p][f] + g[..F+p];  g_feat_partial[blk][b][p][f] partial sums (blocks_per_image each) */
 int ups_unpool_bwd(const float* hard, const float* feat, const void* g, float* g_hard, float* g_feat,
                    int32_t dtype, int32_t B, int64_t hw, int32_t P, int32_t F, int32_t ldo, void* stream);

@@ -657,6 +657,76 @@ __global__ __launch_bounds__(256) void unpool_fwd_kernel(const float* __restrict
     }
 }
 
+// Mixed unpool (appearance transfer): output k takes its hard tile from pose image pose_idx[k] and feature row p from
+// appearance image app_idx[k * P + p] -- neither hard[pose_idx] nor a gathered [K, P, F] feature tensor exists in HBM.
+//   out[k][pix][f] = sum_p hard[pose_idx[k]][pix][p] * feat[app_idx[k*P+p]][p][f];  out[k][pix][F+p] = hard[..][p];  pad zero
+// Same form as unpool_fwd_kernel, one block per (k, 256-pixel tile), and the SAME arithmetic statement for statement (hm * feat
+// for a one-hot pixel, ascending-p accumulation from 0 at ties): the result is bit-identical to unpool_fwd_kernel on gathered
+// inputs.  k is the FAST grid index: the blocks that share a pose tile (the m cells of one matrix row) are dispatched together;
+// a block that walked several k over one LDS tile would save the repeated reads of the pose tile (40 of 200 bytes per pixel at P = 10,
+// bf16) but needs the runs of equal pose_idx on the host (this form is 1.4-1.6x the gather path as it is).  The indices are validated on the host (ops.unpool_mix).
+template <typename T>
+__global__ __launch_bounds__(256) void unpool_mix_fwd_kernel(const float* __restrict__ hard, const float* __restrict__ feat,
+                                                             const int* __restrict__ pose_idx, const int* __restrict__ app_idx,
+                                                             T* __restrict__ out, long long hw, int P, int F, int ldo) {
+    extern __shared__ __attribute__((aligned(16))) float ts[];          // hard [256][PP], feat [P][F]
+    const int PP = tile_pitch(P);
+    float* fs = ts + 256 * PP;
+    const int kk = blockIdx.x;
+    const long long q0 = (long long)blockIdx.y * 256;
+    const int cnt = (int)min(256ll, hw - q0);
+    const long long pix0 = (long long)kk * hw + q0;
+    tile_load_f32(hard + ((long long)pose_idx[kk] * hw + q0) * P, cnt, P, PP, ts);      // (block-uniform index: a scalar load)
+    const int F4 = F / 4;                                 // feature rows are gathered in 16-byte pieces (F % 8 == 0)
+    for (int i = threadIdx.x; i < P * F4; i += 256) {
+        const int p = i / F4, c = i - p * F4;
+        ((float4*)fs)[i] = ((const float4*)(feat + ((long long)app_idx[(long long)kk * P + p] * P + p) * F))[c];
+    }
+    int* act = (int*)(fs + P * F);                        // per pixel: its single active part, -1 (none) or -2 (several: ties)
+    __syncthreads();
+    for (int px = threadIdx.x; px < cnt; px += 256) {
+        const float* hrow = ts + px * PP;
+        int a = -1;
+        for (int p = 0; p < P; ++p)
+            if (hrow[p] != 0.f) a = a == -1 ? p : -2;
+        act[px] = a;
+    }
+    __syncthreads();
+    const int cpp = ldo / 8;
+    for (int i = threadIdx.x; i < cnt * cpp; i += 256) {
+        const int px = i / cpp, k = i - px * cpp;
+        float f[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+        const float* hrow = ts + px * PP;
+        if (k * 8 < F) {
+            const int a = act[px];
+            if (a >= 0) {
+                const float hm = hrow[a];
+                const float* fr = fs + a * F + k * 8;
+#pragma unroll
+                for (int e = 0; e < 8; ++e) f[e] = hm * fr[e];
+            } else if (a == -2) {
+                for (int p = 0; p < P; ++p) {
+                    const float hm = hrow[p];
+                    if (hm != 0.f) {
+                        const float* fr = fs + p * F + k * 8;
+#pragma unroll
+                        for (int e = 0; e < 8; ++e) f[e] += hm * fr[e];
+                    }
+                }
+            }
+        } else {
+#pragma unroll
+            for (int e = 0; e < 8; ++e) {
+                const int ch = k * 8 + e - F;
+                if (ch < P) f[e] = hrow[ch];
+            }
+        }
+        T* o = out + (pix0 + px) * ldo + k * 8;
+        if (sizeof(T) == 2) *(uint4*)o = Chunk<bf16>::pack(f);
+        else { *(uint4*)o = Chunk<float>::pack(f); *(uint4*)((float*)o + 4) = Chunk<float>::pack(f + 4); }
+    }
+}
+
 // Backward of unpool_features + concat in ONE pass over the gradient (round 4; it was two kernels, each reading g):
 //   g_hard[b][px][p]  = sum_f g[b][px][f] * feat[b][p][f] + g[b][px][F+p]
 //   g_feat[b][p][f]   = sum_px hard[b][px][p] * g[b][px][f]          (per-slab partials, reduced by unpool_feat_reduce_kernel)
@@ -1198,6 +1268,23 @@ extern "C" int ups_unpool_fwd(const float* hard, const float* feat, void* out, i
     if (!allow_big_lds(unpool_fwd_kernel<float>, a0) || !allow_big_lds(unpool_fwd_kernel<bf16>, a1)) return UPS_E_LAUNCH;
     if (dtype == UPS_F32) hipLaunchKernelGGL(unpool_fwd_kernel<float>, grid, dim3(256), shm, (hipStream_t)stream, hard, feat, (float*)out, (long long)hw, P, F, ldo);
     else hipLaunchKernelGGL(unpool_fwd_kernel<bf16>, grid, dim3(256), shm, (hipStream_t)stream, hard, feat, (bf16*)out, (long long)hw, P, F, ldo);
+    UPS_LAUNCH_CHECK();
+    return UPS_OK;
+}
+
+extern "C" int ups_unpool_mix_fwd(const float* hard, const float* feat, const int32_t* pose_idx, const int32_t* app_idx, void* out,
+                                  int32_t dtype, int32_t K, int32_t n, int32_t m, int64_t hw, int32_t P, int32_t F, int32_t ldo,
+                                  void* stream) {
+    UPS_CHECK_ARG(hard && feat && pose_idx && app_idx && out && K >= 1 && n >= 1 && m >= 1 && hw >= 1);
+    UPS_CHECK_ARG(F >= 8 && F % 8 == 0 && ldo % 8 == 0 && ldo >= F + P && P >= 1 && P <= 64);
+    UPS_CHECK_ARG(ups_cdiv(hw, 256) <= 65535);                  // (tiles ride on grid.y)
+    UPS_CHECK_ARG(((((uintptr_t)feat) | ((uintptr_t)out)) & 15) == 0);     // feature rows are read, items stored, as 16-byte pieces
+    const dim3 grid(K, ups_cdiv(hw, 256));
+    const size_t shm = ((size_t)256 * (P | 1) + (size_t)P * F + 256) * sizeof(float);
+    static UpsPerDevice a0, a1;
+    if (!allow_big_lds(unpool_mix_fwd_kernel<float>, a0) || !allow_big_lds(unpool_mix_fwd_kernel<bf16>, a1)) return UPS_E_LAUNCH;
+    if (dtype == UPS_F32) hipLaunchKernelGGL(unpool_mix_fwd_kernel<float>, grid, dim3(256), shm, (hipStream_t)stream, hard, feat, pose_idx, app_idx, (float*)out, (long long)hw, P, F, ldo);
+    else hipLaunchKernelGGL(unpool_mix_fwd_kernel<bf16>, grid, dim3(256), shm, (hipStream_t)stream, hard, feat, pose_idx, app_idx, (bf16*)out, (long long)hw, P, F, ldo);
     UPS_LAUNCH_CHECK();
     return UPS_OK;
 }

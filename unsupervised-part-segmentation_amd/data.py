@@ -9,6 +9,10 @@
     numpy restatement of the albumentations pipelines in ``augment.py`` (same transforms, defaults and sync rules; the
     sample stream is not albumentations').
 
+  * ``TransferData``     -- final_eval/eval_transfer.py's dataset of the comparison matrix (row csv x column csv, one relative
+    path per line), yielding whole BLOCKS (block_size row images, block_size column images) instead of block_size^2 pairs:
+    ``TrainModel.transfer_matrix`` encodes each image once.
+
 The exact resize filter / cropping of eddata's ``preprocess_image`` is not visible in the reference tree: bilinear resize
 of the whole image is used (UNVERIFIED).  ``batches`` turns a dataset into the ``{"view0", "view1"[, "view0_target"]}``
 float32 NHWC batches ``Trainer.iterate`` consumes, with a small thread pool for decoding.
@@ -123,6 +127,55 @@ class AugmentedPair2(StochasticPairs):
                 view1, = augment.stochastic_shape_augmentation(rng, view1)
         ex.update(view0=view0, view1=view1, view0_target=target)
         return ex
+
+
+class TransferData(object):
+    """Blocks of the comparison matrix.  ``data_row_csv`` / ``data_col_csv`` list one path per line, relative to ``data_root``;
+    block b pairs rows [b * bs, (b + 1) * bs) with columns of the same range, bs = ``data_block_size`` (default ``batch_size``), and
+    there are min(n_rows, n_cols) // bs blocks (the reference's length rule: its dataset has that many times bs * bs pairs).
+    ``get_block(b)`` -> {"matrix": b, "rows" / "cols": float32 [bs,S,S,3] in [-1, 1], "row_paths" / "col_paths": the csv lines}."""
+
+    def __init__(self, config):
+        self.size = config["spatial_size"]
+        self.root = config["data_root"]
+        self.block_size = int(config.get("data_block_size", config["batch_size"]))
+        self.row_paths = self._read_list(config["data_row_csv"])
+        self.col_paths = self._read_list(config["data_col_csv"])
+        self.n_rows, self.n_cols = len(self.row_paths), len(self.col_paths)
+        self.n_blocks = min(self.n_rows, self.n_cols) // self.block_size
+
+    @staticmethod
+    def _read_list(path):
+        with open(path) as f:                   # (a missing csv raises FileNotFoundError: the runner's "data is not there")
+            return [line for line in f.read().splitlines() if line.strip()]
+
+    def __len__(self):
+        """Number of (row, column) cells, as the reference's pair dataset counts them."""
+        return self.n_blocks * self.block_size * self.block_size
+
+    def cell(self, k):
+        """Cell k of the reference's flat ordering -> (matrix, block row, block column, row image index, column image index)."""
+        bs = self.block_size
+        b, r = divmod(int(k), bs * bs)
+        bi, bj = divmod(r, bs)
+        return b, bi, bj, b * bs + bi, b * bs + bj
+
+    def preprocess_image(self, path):
+        from PIL import Image
+        img = Image.open(path).convert("RGB").resize((self.size, self.size), Image.BILINEAR)
+        return np.asarray(img, dtype=np.float32) / 127.5 - 1.0
+
+    def get_block(self, b):
+        if not 0 <= b < self.n_blocks:
+            raise IndexError("block {} of {}".format(b, self.n_blocks))
+        sl = slice(b * self.block_size, (b + 1) * self.block_size)
+        rp, cp = self.row_paths[sl], self.col_paths[sl]
+        return {"matrix": b, "row_paths": rp, "col_paths": cp,
+                "rows": np.stack([self.preprocess_image(os.path.join(self.root, p)) for p in rp]),
+                "cols": np.stack([self.preprocess_image(os.path.join(self.root, p)) for p in cp])}
+
+    def __iter__(self):
+        return (self.get_block(b) for b in range(self.n_blocks))
 
 
 def batches(dataset, batch_size, shuffle=True, workers=8, seed=0, epochs=None, pad_last=False):

@@ -5,7 +5,13 @@ The reference takes these from the un-vendored ``denseposelib`` (``compute_best_
 overlaps best (IoU over the whole evaluation set), the remapped prediction is scored per label, and the reported "overall"
 number averages the labels except ``background`` (cub_semantic_ours.ipynb:615).  NumPy only -- outside the hot path.
 """
+import logging
+import os
+
 import numpy as np
+
+LOG = logging.getLogger("upsparts")
+TRANSFER_META_KEYS = ("view0", "view1", "relative_file_path_", "view1_relative_file_path_", "matrix", "matrix_index")
 
 
 def compute_best_iou_remapping(inferred, gt):
@@ -78,7 +84,6 @@ def write_eval_tables(res, root, global_step, part_names=None, background_label=
     ``best_remapping.yml`` inferred part id -> ground-truth label (eval_01.py:254-258).
     part_names: {ground-truth label: column name} (the sorted keys of the yaml's dp_semantic_remap_dict in the reference);
     default "background" for `background_label`, "part_<label>" otherwise."""
-    import os
     import pandas as pd
     import yaml
     from tabulate import tabulate
@@ -101,3 +106,61 @@ def write_eval_tables(res, root, global_step, part_names=None, background_label=
     with open(os.path.join(root, "best_remapping.yml"), "w") as f:
         yaml.dump({"best_remapping": {int(k): int(v) for k, v in res["mapping"].items()}}, f, default_flow_style=False)
     return df, df_mean
+
+
+def transfer_cells(block, result, generated_key, vis0_key, vis1_key, data=None):
+    """Append one block's cells to the comparison-matrix record: the key set final_eval/eval_transfer.py's MatrixHook leaves in
+    ``data.p`` (the three yaml-named keys plus TRANSFER_META_KEYS), one list entry per cell, row-major within the block.
+    block: ``data.TransferData.get_block``; result: ``TrainModel.transfer_matrix`` as NumPy arrays."""
+    if data is None:
+        data = {k: [] for k in (generated_key, vis0_key, vis1_key) + TRANSFER_META_KEYS}
+    n, m = result["generated"].shape[:2]
+    for i in range(n):
+        for j in range(m):
+            data[generated_key].append(result["generated"][i, j])
+            data[vis0_key].append(result["row_mask_rgb"][i])
+            data[vis1_key].append(result["col_mask_rgb"][j])
+            data["view0"].append(block["rows"][i])
+            data["view1"].append(block["cols"][j])
+            data["relative_file_path_"].append(block["row_paths"][i])
+            data["view1_relative_file_path_"].append(block["col_paths"][j])
+            data["matrix"].append(block["matrix"])
+            data["matrix_index"].append((i, j))
+    return data
+
+
+def write_transfer_matrix(data, out_path, generated_key="generated", vis0_key="vis0", vis1_key="vis1"):
+    """PNG grids of a comparison-matrix record (``transfer_cells``), one per matrix: <dir>/<matrix:06>_<name of out_path>.  Two header
+    columns (row image, its mask visualisation), two header rows (column image, its mask visualisation), the synthesis of
+    (pose i, appearance j) in the body.  Returns the written paths; without matplotlib nothing is written and that is logged."""
+    try:
+        import matplotlib
+        matplotlib.use("Agg")
+        from matplotlib import pyplot as plt
+    except ImportError as e:
+        LOG.warning("comparison matrix image %s not written: matplotlib is not available (%s)", out_path, e)
+        return []
+    written = []
+    for matrix in sorted(set(data["matrix"])):
+        cells = [c for c in range(len(data["matrix"])) if data["matrix"][c] == matrix]
+        at = {tuple(data["matrix_index"][c]): c for c in cells}
+        n = 1 + max(i for i, _ in at)
+        m = 1 + max(j for _, j in at)
+        S = np.asarray(data[generated_key][cells[0]]).shape[0]
+        canvas = np.ones(((n + 2) * S, (m + 2) * S, 3), dtype=np.float32)
+
+        def put(img, r, c):
+            canvas[r * S:(r + 1) * S, c * S:(c + 1) * S] = np.clip((np.asarray(img, dtype=np.float32)[..., :3] + 1.0) / 2.0, 0.0, 1.0)
+        for i in range(n):
+            put(data["view0"][at[(i, 0)]], i + 2, 0)
+            put(data[vis0_key][at[(i, 0)]], i + 2, 1)
+        for j in range(m):
+            put(data["view1"][at[(0, j)]], 0, j + 2)
+            put(data[vis1_key][at[(0, j)]], 1, j + 2)
+        for (i, j), c in at.items():
+            put(data[generated_key][c], i + 2, j + 2)
+        d, name = os.path.split(out_path)
+        path = os.path.join(d, "{:06}_{}".format(int(matrix), name))
+        plt.imsave(path, canvas)
+        written.append(path)
+    return written

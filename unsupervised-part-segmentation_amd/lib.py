@@ -142,6 +142,7 @@ _SIGS = {
     "ups_mask_parts_fwd": ([_P, _P, _P, _I, _I, _L, _I, _P], C.c_int),
     "ups_mask_parts_bwd": ([_P, _P, _P, _I, _I, _L, _I, _P], C.c_int),
     "ups_unpool_fwd": ([_P, _P, _P, _I, _I, _L, _I, _I, _I, _P], C.c_int),
+    "ups_unpool_mix_fwd": ([_P, _P, _P, _P, _P, _I, _I, _I, _I, _L, _I, _I, _I, _P], C.c_int),
     "ups_unpool_bwd": ([_P, _P, _P, _P, _P, _I, _I, _L, _I, _I, _I, _P], C.c_int),
     "ups_unpool_bwd_floats": ([_I, _I, _I], _Z),
     "ups_prior_sums_floats": ([_I, _I], _Z),

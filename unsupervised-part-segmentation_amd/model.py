@@ -156,6 +156,117 @@ class TrainModel(object):
                       "out_parts_soft": soft, "view0_mask00_rgb": mask2rgb(m[:B])}
         return self._last
 
+    # ------------------------------------------------------------------ appearance transfer (final_eval/eval_transfer.py; the
+    # training graph's _cross_generated, SB_model48i/model.py:488-500).  Only unpool_features and the hourglass decoder depend on
+    # the (pose, appearance) pair: n poses and m appearances are encoded once each, K = n * m combinations are decoded.  Test-mode
+    # semantics as forward(batch, noise=None): latent means, no sampling noise, this model's Fp8State active.
+    def _encode(self, *groups):
+        """groups: (views [n_g,S,S,3], want_feat) -> one dict per group.  The pose path (e_pi, dv, soft-max) runs ONCE over all groups
+        concatenated, as ``forward`` runs it over view0 and view1 together: the convolutions' split-K factors depend on the batch, so
+        only the same batch composition gives ``forward``'s bits.  e_alpha runs per group that wants features (forward: view1)."""
+        cfg = self.config
+        ops.Fp8.activate(self.fp8)
+        vs = [g[0].to(self.device, torch.float32).contiguous() for g in groups]
+        v = vs[0] if len(vs) == 1 else torch.cat(vs, 0)
+        n, S = v.shape[0], v.shape[1]
+        Z, A, P = cfg.get("z0_size", 256), cfg.get("local_app_size", 64), self.n_parts
+        img = self.to_act(v)
+        pe = self.nets.e_pi(Act(img, n, S, S, 3)).t.view(n, -1)
+        lm = self.nets.dv(self.latent_act(pe[:, :Z].contiguous())).t
+        _, m, hard, _, bits = ops.part_softmax(lm, None, want_bits=P <= 32)
+        _, soft, _, amax = ops.part_softmax(lm.contiguous(), None, want_hard=False, want_argmax=True)
+        outs, o = [], 0
+        for vg, (_, want_feat) in zip(vs, groups):
+            sl = slice(o, o + vg.shape[0])
+            o += vg.shape[0]
+            out = {"hard": hard[sl].contiguous(), "out_parts_hard": amax[sl], "out_parts_soft": soft[sl], "m0_sample": m[sl]}
+            if want_feat:
+                yp = self.nets.e_alpha(self.part_images(img[sl], vg, out["hard"], None if bits is None else bits[sl].contiguous())).t
+                out["feat"] = yp.float().view(P, vg.shape[0], A).permute(1, 0, 2).contiguous()
+            outs.append(out)
+        return outs
+
+    @torch.no_grad()
+    def encode_pose(self, views):
+        """views [n,S,S,3] -> {"hard" [n,S,S,P] (the test-mode hard masks decode_mixed takes), "out_parts_hard", "out_parts_soft",
+        "m0_sample"}: what ``forward`` computes for view0, bit for bit.  ``forward`` runs the pose path of n pairs on 2n images and the
+        convolutions plan by the batch (``_encode``), so the views stand in for the view1 half as well: the pose path is paid twice
+        here (transfer_matrix, which encodes rows and columns together, pays it once)."""
+        return self._encode((views, False), (views, False))[0]
+
+    @torch.no_grad()
+    def encode_appearance(self, views):
+        """views [m,S,S,3] -> part appearances [m,P,A] fp32: each view masked by ITS OWN test-mode hard masks, through part_images /
+        e_alpha as ``forward`` does for view1 (the second half of a pose batch of 2m, as there: see encode_pose)."""
+        return self._encode((views, False), (views, True))[1]["feat"]
+
+    @torch.no_grad()
+    def decode_mixed(self, hard, feat, pose_idx, app_idx, chunk=None):
+        """generated [K,S,S,3] fp32: image k has the masks hard[pose_idx[k]] and, for part p, the appearance feat[app_idx[k][p]][p].
+        pose_idx [K], app_idx [K,P]: host integers.  Decoded in chunks of at most `chunk` images (default: the config's batch_size;
+        the last chunk may be shorter), so the memory in flight is that of one ordinary forward."""
+        ops.Fp8.activate(self.fp8)
+        pi = torch.as_tensor(pose_idx, device="cpu").reshape(-1)
+        P, A = self.n_parts, feat.shape[-1]
+        ai = torch.as_tensor(app_idx, device="cpu").reshape(-1, P)
+        K, S = pi.numel(), hard.shape[1]
+        chunk = int(chunk or self.config["batch_size"])
+        if K == 0 or ai.shape[0] != K or chunk < 1:
+            raise L.UpsError("decode_mixed: pose_idx [K >= 1], app_idx [K,{}], chunk >= 1 (got K = {}, {} index rows, chunk {})".format(
+                P, K, ai.shape[0], chunk))
+        out = torch.empty((K, S, S, 3), dtype=torch.float32, device=self.device)
+        for c0 in range(0, K, chunk):
+            c1 = min(K, c0 + chunk)
+            inj = ops.unpool_mix(hard, feat, pi[c0:c1], ai[c0:c1], self.act_dtype)
+            out[c0:c1] = self.nets.dd(Act(inj, c1 - c0, S, S, A + P)).t[..., :3].float()
+        return out
+
+    @torch.no_grad()
+    def transfer_matrix(self, row_views, col_views, parts=None):
+        """The comparison matrix of eval_transfer.py from one pass: generated [n,m,S,S,3], cell (i, j) = pose of row image i with the
+        part appearances of column image j.  parts=None: every part from j.  parts=[..]: only those parts from j, the others from
+        the row image's own appearance (the rows are then appearance-encoded too).  Index layout: ``transfer_indices``."""
+        n, m = row_views.shape[0], col_views.shape[0]
+        rows, cols = self._encode((row_views, parts is not None), (col_views, True))
+        feat = cols["feat"] if parts is None else torch.cat([rows["feat"], cols["feat"]], 0)
+        pi, ai = transfer_indices(n, m, self.n_parts, parts)
+        gen = self.decode_mixed(rows["hard"], feat, pi, ai)
+        return {"generated": gen.view(n, m, *gen.shape[1:]),
+                "row_parts_hard": rows["out_parts_hard"], "col_parts_hard": cols["out_parts_hard"],
+                "row_mask_rgb": mask2rgb(rows["m0_sample"]), "col_mask_rgb": mask2rgb(cols["m0_sample"])}
+
+    @torch.no_grad()
+    def cross_generated(self, batch):
+        """_cross_generated (SB_model48i/model.py:488-500) in test mode: pose of view0[k] with the appearance of view1[B-1-k]."""
+        rows, cols = self._encode((batch["view0"], False), (batch["view1"], True))
+        feat = cols["feat"]
+        pi, ai = reversed_indices(feat.shape[0], self.n_parts)
+        return self.decode_mixed(rows["hard"], feat, pi, ai)
+
+
+def transfer_indices(n_rows, n_cols, n_parts, parts=None):
+    """(pose_idx [K], app_idx [K,P]) int64 host tensors of an n_rows x n_cols transfer matrix, K = n_rows * n_cols, cell
+    k = i * n_cols + j (row-major).  pose_idx[k] = i.  The appearance table the indices point into is
+      parts=None : the column images alone             -> app_idx[k, :] = j
+      parts=[..] : the row images, then the column ones -> app_idx[k, p] = n_rows + j for p in parts, i (the row's own) otherwise."""
+    n, m, P = int(n_rows), int(n_cols), int(n_parts)
+    i = torch.arange(n, dtype=torch.int64).repeat_interleave(m)
+    j = torch.arange(m, dtype=torch.int64).repeat(n)
+    if parts is None:
+        return i, j[:, None].expand(n * m, P).contiguous()
+    parts = sorted(set(int(p) for p in parts))
+    if any(p < 0 or p >= P for p in parts):
+        raise ValueError("parts {} out of range for {} parts".format(parts, P))
+    app = i[:, None].expand(n * m, P).clone()
+    app[:, parts] = (n + j)[:, None]
+    return i, app
+
+
+def reversed_indices(batch, n_parts):
+    """_cross_generated: image k keeps its pose and takes every part appearance from image batch-1-k."""
+    k = torch.arange(int(batch), dtype=torch.int64)
+    return k, (int(batch) - 1 - k)[:, None].expand(int(batch), int(n_parts)).contiguous()
+
 
 def mask_colors(n_parts):
     """nn.py:2118-2120 (inferno colour table); needs matplotlib, falls back to a grey ramp."""

@@ -1752,6 +1752,35 @@ def part_softmax(mean, eps=None, want_hard=True, want_argmax=False, want_bits=No
     return out + (stats,) if moments_gamma is not None else out
 
 
+def unpool_mix(hard, feat, pose_idx, app_idx, act_dtype):
+    """Mixed unpool of appearance transfer (ups_unpool_mix_fwd; inference only, no backward): hard [n,H,W,P] and feat [m,P,F] fp32 on
+    the device, pose_idx [K] and app_idx [K,P] integer HOST tensors (or sequences) -> [K,H,W,round8(F+P)] in `act_dtype` with
+    out[k] = unpool(hard[pose_idx[k]], rows p of feat[app_idx[k,p]]).  The kernel trusts its indices, so they are checked here, on
+    the host values they are uploaded from: an index out of range raises before anything is launched."""
+    n, H, W, P = hard.shape
+    m, Pf, F = feat.shape
+    pi = torch.as_tensor(pose_idx, device="cpu").reshape(-1).to(torch.int64)
+    ai = torch.as_tensor(app_idx, device="cpu").reshape(-1).to(torch.int64)
+    K = pi.numel()
+    if Pf != P or hard.dtype != torch.float32 or feat.dtype != torch.float32:
+        raise L.UpsError("unpool_mix: hard [n,H,W,P] and feat [m,P,F] must be fp32 with the same P (got {} {}, {} {})".format(
+            tuple(hard.shape), hard.dtype, tuple(feat.shape), feat.dtype))
+    if K == 0 or ai.numel() != K * P:
+        raise L.UpsError("unpool_mix: pose_idx [K] with K >= 1 and app_idx [K,{}] expected (got {} and {} indices)".format(
+            P, K, ai.numel()))
+    if int(pi.min()) < 0 or int(pi.max()) >= n or int(ai.min()) < 0 or int(ai.max()) >= m:
+        raise L.UpsError("unpool_mix: index out of range: pose_idx in [{}, {}] for {} poses, app_idx in [{}, {}] for {} appearances"
+                         .format(int(pi.min()), int(pi.max()), n, int(ai.min()), int(ai.max()), m))
+    dev = hard.device
+    hard, feat = hard.contiguous(), feat.contiguous()
+    pd, ad = pi.to(torch.int32).to(dev), ai.to(torch.int32).to(dev)
+    ldo = round8(F + P)
+    out = torch.empty((K, H, W, ldo), dtype=act_dtype, device=dev)
+    L.call("ups_unpool_mix_fwd", L.ptr(hard), L.ptr(feat), L.ptr(pd), L.ptr(ad), L.ptr(out), L.dt(out),
+           K, n, m, H * W, P, F, ldo, L.stream())
+    return out
+
+
 def spatial_moments(x, gamma, rect_px=None, half=0, kl_sums=None):
     """kl_sums (fp32 [>= 16] device buffer): the same pass also writes sum x * log(P x + 1e-20) -- the categorical KL of the map,
     view 1's other prior term -- to kl_sums[0] (ups_spatial_moments_kl)."""

@@ -12,6 +12,10 @@ Data: ``dataset: src.data.data.AugmentedPair2`` / ``eddata.stochastic_pair.Stoch
 datasets of ``data.py``; when the csv / images are NOT THERE (FileNotFoundError / ImportError, nothing else) the runner falls back
 to ``SyntheticPairs`` (U(-1,1) views), says SYNTHETIC DATA at WARNING level and with every logged step, unless ``--strict-dataset``
 is given (then it raises).
+
+``--transfer <yaml> -c <ckpt> [--parts 0,3,..]`` is the work-alike of final_eval/eval_transfer.py: one ``TrainModel.transfer_matrix``
+call per block of ``data.TransferData``, the cells pickled to <root>/comparison_matrix/<global_step:06>/data.p with the reference
+MatrixHook's key set (its plotting script reads the file) and drawn by ``evalutil.write_transfer_matrix``.
 """
 import argparse
 import importlib
@@ -96,6 +100,9 @@ def main(argv=None):
     ap.add_argument("-t", "--train", nargs="+", default=None, help="training yaml(s)")
     ap.add_argument("-e", "--eval", nargs="+", default=None,
                     help="evaluation yaml(s): test-mode forward over the dataset, outputs pickled (edflow -e work-alike)")
+    ap.add_argument("--transfer", nargs="+", default=None,
+                    help="transfer yaml(s): pose i x appearance j comparison matrices (final_eval/eval_transfer.py work-alike)")
+    ap.add_argument("--parts", default=None, help="--transfer: comma-separated part ids taken from the column image (default: all)")
     ap.add_argument("--eval-batches", type=int, default=None, help="number of batches to evaluate (default: one epoch)")
     ap.add_argument("-c", "--checkpoint", default=None)
     ap.add_argument("-p", "--project", default=None, help="log root (default logs/<timestamp>)")
@@ -103,8 +110,10 @@ def main(argv=None):
     ap.add_argument("--set", nargs="*", default=[], help="key=value overrides (yaml-parsed)")
     ap.add_argument("--strict-dataset", action="store_true")
     args = ap.parse_args(argv)
-    if (args.train is None) == (args.eval is None):
-        ap.error("exactly one of -t / -e is required")
+    if (args.train is not None) + (args.eval is not None) + (args.transfer is not None) != 1:
+        ap.error("exactly one of -t / -e / --transfer is required")
+    if args.transfer is not None:
+        return transfer(args)
     if args.eval is not None:
         return evaluate(args)
     cfg = load_config(args.train)
@@ -196,6 +205,65 @@ def evaluate(args):
         names = cfg.get("part_names")
         evalutil.write_eval_tables(res, odir, it.global_step, {int(k): str(v) for k, v in names.items()} if names else None)
     print("[INFO] evaluation outputs written to", odir)
+    return data
+
+
+class SyntheticTransfer(object):
+    """One block of U(-1, 1) row / column images in ``data.TransferData``'s block format (the data is not there)."""
+
+    def __init__(self, config, seed=1234):
+        self.config, self.seed = config, seed
+        self.block_size = int(config.get("data_block_size", config["batch_size"]))
+
+    def __iter__(self):
+        gen = torch.Generator().manual_seed(self.seed)
+        bs, S = self.block_size, self.config["spatial_size"]
+        yield {"matrix": 0, "rows": (torch.rand(bs, S, S, 3, generator=gen) * 2 - 1).numpy(),
+               "cols": (torch.rand(bs, S, S, 3, generator=gen) * 2 - 1).numpy(),
+               "row_paths": ["synthetic/row_{:03}.png".format(i) for i in range(bs)],
+               "col_paths": ["synthetic/col_{:03}.png".format(i) for i in range(bs)]}
+
+
+def transfer(args):
+    """``--transfer``: the comparison matrices of final_eval/eval_transfer.py.  Per block ONE transfer_matrix call (block_size poses
+    and block_size appearances encoded once, block_size^2 images decoded) where the reference feeds block_size^2 pairs."""
+    import pickle
+    from . import evalutil
+    cfg = load_config(args.transfer)
+    for kv in args.set:
+        k, v = kv.split("=", 1)
+        cfg[k] = yaml.safe_load(v)
+    cfg["test_mode"] = True
+    parts = None if args.parts is None else [int(p) for p in args.parts.split(",") if p.strip() != ""]
+    dist_setup()
+    root = args.project or os.path.join("logs", time.strftime("%Y-%m-%dT%H-%M-%S") + "_transfer")
+    try:
+        blocks = _data.TransferData(cfg)
+        if blocks.n_blocks:                     # the csvs without the image tree (or without PIL) are "data not there" as well
+            blocks.preprocess_image(os.path.join(blocks.root, blocks.row_paths[0]))
+    except (FileNotFoundError, NotADirectoryError, ImportError) as e:
+        if args.strict_dataset:
+            raise
+        LOG.warning("SYNTHETIC DATA: transfer data is not available (%s: %s); one block of U(-1, 1) noise images. "
+                    "Pass --strict-dataset to make this an error.", type(e).__name__, e)
+        blocks = SyntheticTransfer(cfg)
+    Model, Iterator = get_obj_from_str(cfg["model"]), get_obj_from_str(cfg["iterator"])
+    model = Model(cfg)
+    it = Iterator(cfg, root, model)
+    it.initialize(args.checkpoint)
+    gk, k0, k1 = cfg.get("generated_key", "generated"), cfg.get("vis0_key", "vis0"), cfg.get("vis1_key", "vis1")
+    data = None
+    for block in blocks:
+        res = model.transfer_matrix(torch.from_numpy(block["rows"]), torch.from_numpy(block["cols"]), parts=parts)
+        data = evalutil.transfer_cells(block, {k: v.cpu().numpy() for k, v in res.items()}, gk, k0, k1, data)
+    if data is None:
+        raise ValueError("--transfer: no block (fewer than data_block_size = {} rows or columns)".format(blocks.block_size))
+    odir = os.path.join(root, "comparison_matrix", "{:06}".format(it.global_step))
+    os.makedirs(odir, exist_ok=True)
+    with open(os.path.join(odir, "data.p"), "wb") as f:
+        pickle.dump(data, f)
+    evalutil.write_transfer_matrix(data, os.path.join(odir, "comparison_matrix.png"), gk, k0, k1)
+    print("[INFO] comparison matrix data written to", os.path.join(odir, "data.p"))
     return data
 
 
