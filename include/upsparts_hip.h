@@ -411,6 +411,45 @@ int ups_unpool_bwd(const float* hard, const float* feat, const void* g, float* g
 /* `g_feat` must hold B*P*F floats of result followed by scratch; total = ups_unpool_bwd_floats(B,P,F). */
 size_t ups_unpool_bwd_floats(int32_t B, int32_t P, int32_t F);
 
+/* ---------------------------------------------------------------- training image logs (M:968-1053), csrc/canvas.hip
+ * uint8 canvases of the reference's img_ops.  Every entry writes a caller-owned canvas [rows*H, cols*W, C] (C = 3 RGB, 1 gray;
+ * 16-byte aligned) completely -- blank tiles included -- with 16-byte stores, one run of 16 bytes per thread.
+ *   quantisation (edflow save_image, re-derived, UNVERIFIED): byte = (uint8) clamp((v + 1) * 127.5, 0, 255), truncating; value 0
+ *     (blank tiles, masked-out pixels) is byte 127, and maps the reference leaves in [0,1] come out between 127 and 255;
+ *   tiling (tf_batch_to_canvas, re-derived, UNVERIFIED): tile n at row n / cols, column n % cols; tiles n >= N are blank;
+ *   every decision (truncation, thresholds, half-to-even rounding) is taken in fp64 on the fp32 / bf16 source values.
+ * Sources are NHWC; images are UPS_F32 or UPS_BF16 with `ld` physical channels (ld >= 3: the first three are R, G, B), masks are
+ * fp32 [..][P] or the sign-packed hard bits of ups_part_softmax_fwd (uint32 per pixel, P <= 32).  UPS_E_ARG on anything else. */
+/* ceil(sqrt(n)): the side of the square grid tf_batch_to_canvas(cols=None) lays n tiles out in */
+int ups_canvas_grid_side(int32_t n);
+/* img [N,H,W,ld] in [-1,1] -> canvas [rows*H, cols*W, 3]; rows * cols >= N */
+int ups_canvas_images(const void* img, int32_t dtype, int32_t N, int32_t H, int32_t W, int32_t ld, int32_t rows, int32_t cols,
+                      uint8_t* canvas, void* stream);
+/* mask2rgb (N:2067-2089) -> canvas [rows*H, cols*W, 3]: colors[3 p ..] (uint8 [P,3], DEVICE, already quantised by the host) of the
+ * pixel's part.  Exactly one of mask [N,H,W,P] fp32 / bits [N,H,W] is given.  mask, one_hot = 0: arg-max over P, the lowest index
+ * wins ties (tf.argmax); one_hot = 1 (make_hot=False): the mask is one-hot already, the first non-zero entry names the part;
+ * bits: the lowest set bit.  A pixel without a part (all-zero one-hot / bits) is value 0, byte 127. */
+int ups_canvas_mask_rgb(const float* mask, const uint32_t* bits, int32_t one_hot, const uint8_t* colors, int32_t N, int32_t H, int32_t W,
+                        int32_t P, int32_t rows, int32_t cols, uint8_t* canvas, void* stream);
+/* assigned_parts (M:990-1006) in one launch: for part p the g x g grid (g = ups_canvas_grid_side(2B)) of the 2B images
+ * hard0[b][..][p] * view0[b] (b < B), then hard1[b][..][p] * view1[b]; the P grids in 5 columns ->
+ * canvas [ceil(P/5)*g*H, 5*g*W, 3].  Masks: hard0 / hard1 [B,H,W,P] fp32, or bits0 / bits1 [B,H,W] (the other pair NULL);
+ * views [B,H,W,ld] of `dtype`. */
+int ups_canvas_assigned_parts(const float* hard0, const float* hard1, const uint32_t* bits0, const uint32_t* bits1, const void* view0,
+                              const void* view1, int32_t dtype, int32_t ld, int32_t B, int32_t H, int32_t W, int32_t P, uint8_t* canvas,
+                              void* stream);
+/* The four canvases of batch item 0 (M:986-988, 1009-1032) in one launch, from m [H,W,P] fp32 (m0_sample[0]) and the hard mask of
+ * the same image (hard [H,W,P] fp32 or bits [H,W], the other NULL); gp = ups_canvas_grid_side(P):
+ *   c_levels [P*H, n_levels*W, 1]  row p, column k: m[..][p] > levels[k]                                   (M:1009-1017)
+ *   c_edges  [P*H, n_ratios*W, 1]  row p, column k: gx^2 + gy^2 > ratios[k], gx = (m[y][x] - m[y][x+1]) / 4, gy likewise along y,
+ *                                  zero beyond the border: edge_set(m, 1, r) (N:1401-1404) on the stencil of N:1366-1390
+ *   c_heat   [gp*H, gp*W, 3]       p_heatmap: table[rint(255 m)] (half to even, clamped to 0..255), P tiles (N:2051-2062)
+ *   c_masks  [gp*H, gp*W, 1]       masks: the hard mask, P tiles
+ * levels / ratios: HOST arrays of at most 8 floats; table: uint8 [256,3] DEVICE, already quantised by the host (viridis). */
+int ups_canvas_first_item(const float* m, const float* hard, const uint32_t* bits, int32_t H, int32_t W, int32_t P, const float* levels,
+                          int32_t n_levels, const float* ratios, int32_t n_ratios, const uint8_t* table, uint8_t* c_levels,
+                          uint8_t* c_edges, uint8_t* c_heat, uint8_t* c_masks, void* stream);
+
 /* ---------------------------------------------------------------- mask priors (M:652-797), fused
  * One pass over l/m per view producing the partial sums, one fused backward producing dl.
  * See csrc/priors.hip for the slot layout of `sums`. */

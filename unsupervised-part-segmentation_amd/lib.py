@@ -145,6 +145,11 @@ _SIGS = {
     "ups_unpool_mix_fwd": ([_P, _P, _P, _P, _P, _I, _I, _I, _I, _L, _I, _I, _I, _P], C.c_int),
     "ups_unpool_bwd": ([_P, _P, _P, _P, _P, _I, _I, _L, _I, _I, _I, _P], C.c_int),
     "ups_unpool_bwd_floats": ([_I, _I, _I], _Z),
+    "ups_canvas_grid_side": ([_I], C.c_int),
+    "ups_canvas_images": ([_P, _I, _I, _I, _I, _I, _I, _I, _P, _P], C.c_int),
+    "ups_canvas_mask_rgb": ([_P, _P, _I, _P, _I, _I, _I, _I, _I, _I, _P, _P], C.c_int),
+    "ups_canvas_assigned_parts": ([_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P], C.c_int),
+    "ups_canvas_first_item": ([_P, _P, _P, _I, _I, _I, C.POINTER(_F), _I, C.POINTER(_F), _I, _P, _P, _P, _P, _P, _P], C.c_int),
     "ups_prior_sums_floats": ([_I, _I], _Z),
     "ups_prior_fwd": ([C.POINTER(PriorDesc), _P], C.c_int),
     "ups_prior_bwd": ([C.POINTER(PriorDesc), _P], C.c_int),

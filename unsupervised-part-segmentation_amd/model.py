@@ -30,6 +30,7 @@ from . import nets as N
 from . import ops
 from . import dist as D
 from . import tps as TPS
+from . import imglog as IL
 from .nets import Act
 from .schedules import make_var, make_linear_var
 
@@ -423,6 +424,11 @@ class Trainer(object):
         self._graph_enabled = bool(config.get("hip_graph", SW.flag("UPS_GRAPH")))
         self._g = None
         self._cap = None                # set while the step is being captured into HIP graphs (_capture_step)
+        # `log_images` (default off): the reference's img_ops (model.py:968-1053) as uint8 canvases on the steps that log scalars
+        self.log_images = bool(config.get("log_images", False))
+        self._want_images = False       # set for the duration of a train_step(..., images=True)
+        self._img = None                # side stream, colour tables, writer: created by the first image step
+        self._img_hold = None           # (sources, event) of canvases still being rendered: released when the next step begins
 
     # ------------------------------------------------------------------ losses / log scalars, materialised on first use
     def _set_logs(self, losses, log):
@@ -666,18 +672,23 @@ class Trainer(object):
         L.call("ups_prior_bwd" if bwd else "ups_prior_fwd", C.byref(d), L.stream())
 
     # ------------------------------------------------------------------ one session.run(train_op)
-    def train_step(self, batch, noise=None):
-        """One session.run(train_op).  With ``hip_graph: True`` the whole step -- ~1 000 kernel launches on three streams -- is
+    def train_step(self, batch, noise=None, images=False):
+        """One session.run(train_op).  images=True: the step's image logs are rendered into ``img_ops`` as well (``_render_images``;
+        ``iterate`` asks for them on the steps it logs scalars when the config sets ``log_images``).  With ``hip_graph: True`` the whole step -- ~1 000 kernel launches on three streams -- is
         captured once into HIP graphs and replayed (one graph on a single GPU; under data parallelism a sequence of graphs cut
         at the collectives); see ``_graph_step`` / ``_capture_step``."""
         ops.Fp8.activate(self.model.fp8)
         if self._poisoned:
             raise RuntimeError("this trainer's state is inconsistent: " + self._poisoned + " -- restore a checkpoint (Trainer.initialize)")
+        self._release_images()
+        self._want_images = bool(images)
         try:
             return self._train_step(batch, noise)
         except BaseException as e:
             self._after_failed_step(e)
             raise
+        finally:
+            self._want_images = False
 
     def _after_failed_step(self, exc):
         """A step that raises after some optimizer keys have already taken their Adam step on the weight-gradient stream
@@ -761,6 +772,8 @@ class Trainer(object):
             g["graph"], g["sig"] = self._capture_step(g), sig   # (capturing does not execute: the replay below runs the step)
         self._replay_step(g["graph"])
         self._after_graph_step()
+        if self._want_images:           # outside the captured graphs, after the replay, from the buffers the capture owns
+            self._render_images(g["graph"]["img_src"], self.global_step - 1)
         return _LazyLosses(self)
 
     # Data parallel: a collective cannot sit inside a captured region on every backend (gloo reduces on the host), and the
@@ -854,6 +867,7 @@ class Trainer(object):
         if model.use_tps:           # model.py:334-337, 282-311
             tu = None if noise is None or "tps_u" not in noise else noise["tps_u"].to(dev, torch.float32)
             aug = TPS.make_tps([v0, v1] if df else [v0, v1, vt], model.tps_parameters, uniforms=tu, generator=self._gen)
+            c.raw_views = (v0, v1, vt)          # the inputs as they came (img_ops view0 / view1 / view0_target)
             v0, v1 = aug[0], aug[1]
             vt = v0 if df else aug[2]
             model._tps = {"tps_view0": v0, "tps_view1": v1, "tps_view0_target": vt}
@@ -1399,6 +1413,10 @@ class Trainer(object):
         self._debug = {"l_mean": c.lm, "l": c.l, "m": c.m, "hard": c.hard, "px": c.px, "generated": c.gen.detach(),
                        "feat": c.feat.detach(), "dl_tot": c.dl_tot, "dl_rec": c.dl_rec, "g_hard0": c.g_hard0, "g_hard1": c.g_hard1,
                        "pe": c.pe2}
+        if self._cap is not None:       # the capture owns these buffers: every replay refills them, _graph_step renders from them
+            self._cap["img_src"] = self._image_sources(c)
+        elif self._want_images:
+            self._render_images(self._image_sources(c), c.step)
         return _LazyLosses(self)
 
     def _hook_early_reduce(self):
@@ -1569,6 +1587,131 @@ class Trainer(object):
                 out[key] = out.get(key, 0.0) + evs[1 + i].elapsed_time(evs[2 + i])
         return OrderedDict((k, round(v / n, 4)) for k, v in out.items())
 
+    # ------------------------------------------------------------------ image logs (model.py:968-1053; SB_model48c:1038-1094)
+    def _image_sources(self, c):
+        """References to the step's tensors the canvases are rendered from (nothing is launched or allocated here)."""
+        raw = getattr(c, "raw_views", None) or (c.v0, c.v1, c.vt)
+        src = {"B": c.B, "P": c.P, "df": c.df, "inputs": raw, "views": (c.v0, c.v1, c.vt), "tps": self.model.use_tps,
+               "lm": c.lm, "m": c.m, "hard": c.hard, "bits": c.hbits, "gen": c.gen.detach(), "feat": c.feat.detach()}
+        if c.df:        # SB_model48c:1057-1059
+            src["single"] = OrderedDict((nm, c.crit[k][1].detach()) for nm, k in
+                                        (("global_generated", "d_single"), ("alpha_generated", "d_alpha"), ("pi_generated", "d_pi")))
+        return src
+
+    def _image_state(self):
+        if self._img is None:
+            dev = self.device
+            side = torch.cuda.Stream(dev)
+            with torch.cuda.stream(side):
+                colors = torch.from_numpy(IL.mask_color_bytes(IL.mask_colors01(self.model.n_parts))).to(dev)
+                table = torch.from_numpy(IL.viridis_bytes()).to(dev)
+            self._img = {"stream": side, "colors": colors, "table": table, "writer": None}
+        return self._img
+
+    def _release_images(self):
+        """The canvases of the previous image step read tensors of that step (and, under hip_graph, buffers the next replay refills)
+        on the side stream: the launching stream is ordered behind them -- an event wait on the device, no host synchronisation --
+        before those tensors are released.  Nothing to do after a step that rendered no images."""
+        if self._img_hold is not None:
+            _, done = self._img_hold
+            torch.cuda.current_stream(self.device).wait_event(done)
+            self._img_hold = None
+
+    @torch.no_grad()
+    def _render_images(self, src, step):
+        """Fill ``img_ops`` with the reference's image logs of this step as uint8 device canvases [H, W, 3 | 1] -- what edflow's logging
+        hook writes as PNG files: 4-D img_ops with more than one image tiled (cols=None), values quantised by
+        uint8(clamp((v + 1) * 127.5, 0, 255)) (UNVERIFIED, see csrc/canvas.hip; maps in [0,1] -- level sets, edge sets, masks,
+        p_heatmap -- therefore lie between gray and white).  Reporting only: no generator draw, no optimizer or state update, no host
+        synchronisation.  `cross` (model.py:488-500) is decoded on the launching stream -- the decoder's workspaces are not shared
+        between streams -- with the weights as the step left them; everything else runs on a side stream behind an event."""
+        model, dev = self.model, self.device
+        st = self._image_state()
+        B, P, df = src["B"], src["P"], src["df"]
+        main, side = torch.cuda.current_stream(dev), st["stream"]
+        hard, bits, m = src["hard"], src["bits"], src["m"]
+        cross = None
+        if ops.Fp8.enabled:       # a further forward pass would feed the delayed activation scales of the training step
+            IL.warn_once(self.logger, "cross-fp8", "log_images: `cross` is not rendered under precision: fp8")
+        else:
+            pi, ai = reversed_indices(B, P)
+            cross = model.decode_mixed(hard[:B], src["feat"], pi, ai, chunk=B)
+        side.wait_stream(main)
+        out = OrderedDict()
+        with torch.cuda.stream(side):
+            soft = ops.part_softmax(src["lm"][:B], None, want_hard=False)[1]          # out_parts_soft (model.py:468-469)
+            out["out_parts_soft_visualization"] = ops.canvas_mask_rgb(st["colors"], mask=soft)
+            out["m0_sample_visualization"] = ops.canvas_mask_rgb(st["colors"], mask=m[:B])
+            for name, sl in (("encoding_masks_visualization", slice(B, 2 * B)), ("decoding_masks_visualization", slice(0, B))):
+                if bits is not None:
+                    out[name] = ops.canvas_mask_rgb(st["colors"], bits=bits[sl], n_parts=P, cols=B)
+                else:
+                    out[name] = ops.canvas_mask_rgb(st["colors"], mask=hard[sl], one_hot=True, cols=B)
+            first = ops.canvas_first_item(m[0], st["table"], hard=hard[0] if bits is None else None, bits=None if bits is None else bits[0])
+            out["masks"] = first[3]
+            v0, v1, _ = src["views"]
+            if bits is not None:
+                out["assigned_parts"] = ops.canvas_assigned_parts(v0, v1, bits0=bits[:B], bits1=bits[B:], n_parts=P)
+            else:
+                out["assigned_parts"] = ops.canvas_assigned_parts(v0, v1, hard0=hard[:B], hard1=hard[B:])
+            if df:
+                for name, g_img in src["single"].items():
+                    out[name] = ops.canvas_images(g_img)
+            else:
+                out["mumford_sha_edges"], out["p_heatmap"], out[IL.LEVELS_TITLE] = first[1], first[2], first[0]
+            for name, v in zip(("view0", "view1") if df else ("view0", "view1", "view0_target"), src["inputs"]):
+                out[name] = ops.canvas_images(v)
+            if cross is not None:
+                out["cross"] = ops.canvas_images(cross)
+            out["generated"] = ops.canvas_images(src["gen"])
+            if src["tps"] and not df:       # model.py:1046-1053
+                for name, v in zip(("tps_view0", "tps_view1", "tps_view0_target"), src["views"]):
+                    out[name] = ops.canvas_images(v)
+            # the step's own outputs, as TrainModel.outputs names them (views of the step's tensors: valid until the next step)
+            model._last = {"generated": src["gen"][..., :3].float(), "m0_sample": m[:B], "out_parts_soft": soft,
+                           "encoding_mask": hard[B:], "decoding_mask": hard[:B]}
+            if cross is not None:
+                model._last["cross"] = cross
+            done = side.record_event()
+        self.img_ops = out
+        self._img_step = step
+        self._img_hold = (src, done)
+
+    def fetch_images(self):
+        """{name: uint8 array [H,W,3] or [H,W,1]} of the most recent image step (empty before the first)."""
+        if self._img is None:
+            return OrderedDict()
+        self._img["stream"].synchronize()
+        return OrderedDict((k, v.cpu().numpy()) for k, v in self.img_ops.items())
+
+    def _write_images(self, step):
+        """<root>/train/<name>_<step:07>.png for every canvas (rank 0): device-to-host copies on the side stream into pinned buffers,
+        PNG encoding on the writer's thread (imglog.ImageWriter: bounded queue, blocks when full)."""
+        if not self.root or self.rank != 0 or not self.img_ops:
+            return
+        if not IL.have_pil():
+            IL.warn_once(self.logger, "no-pil", "log_images: PIL is not installed: no image logs are written")
+            return
+        st = self._image_state()
+        if st["writer"] is None:
+            st["writer"] = IL.ImageWriter(self.root)
+        with torch.cuda.stream(st["stream"]):
+            host = OrderedDict()
+            for k, v in self.img_ops.items():
+                host[k] = torch.empty(v.shape, dtype=torch.uint8, pin_memory=True)
+                host[k].copy_(v, non_blocking=True)
+            ready = st["stream"].record_event()
+        st["writer"].submit(step, host, ready)
+
+    def _flush_images(self, close=False):
+        w = self._img["writer"] if self._img is not None else None
+        if w is not None:
+            if close:
+                w.close()
+                self._img["writer"] = None
+            else:
+                w.flush()
+
     # ------------------------------------------------------------------ edflow iterate(): log cadence of LoggingHook
     def fetch_logs(self):
         out = OrderedDict()
@@ -1590,8 +1733,13 @@ class Trainer(object):
             if self.global_step >= num_steps:
                 break
             s = self.global_step
-            self.train_step(batch)
-            if s % interval == 0:
+            log_now = s % interval == 0
+            if log_now and self.log_images:     # images on exactly the steps that log scalars
+                self.train_step(batch, images=True)
+                self._write_images(s)
+            else:
+                self.train_step(batch)
+            if log_now:
                 interval = min(2 * interval, max(1, log_freq))
                 logs = self.fetch_logs()
                 logs["global_step"] = s
@@ -1610,7 +1758,9 @@ class Trainer(object):
                         ", ".join(bad) if bad else "loss on another rank", s, int(float(flag))))
             # edflow CheckpointHook: the file is named after the global step the restored run continues FROM
             if ckpt_freq and self.global_step % ckpt_freq == 0:
+                self._flush_images()      # a checkpoint is reported only once the images of the steps before it are on disk
                 self._checkpoint()
+        self._flush_images(close=True)
         self._checkpoint()                # final state at loop exit
 
     def _checkpoint(self):

@@ -1781,6 +1781,144 @@ def unpool_mix(hard, feat, pose_idx, app_idx, act_dtype):
     return out
 
 
+# --------------------------------------------------------------------------- training image logs (csrc/canvas.hip): uint8 canvases
+def canvas_grid(n, cols=None):
+    """(rows, cols) of tf_batch_to_canvas for n tiles (re-derived, UNVERIFIED): cols=None -> the square grid of side ceil(sqrt(n)),
+    else ceil(n / cols) rows."""
+    n = int(n)
+    if n < 1 or (cols is not None and int(cols) < 1):
+        raise L.UpsError("canvas_grid: n >= 1 tiles in cols >= 1 columns (got {} in {})".format(n, cols))
+    if cols is None:
+        g = L.load().ups_canvas_grid_side(n)
+        return g, g
+    return -(-n // int(cols)), int(cols)
+
+
+def _canvas_src(what, t, ndim, dtypes, last=None):
+    """The sources the canvas kernels take: device, contiguous (the channel stride is the last extent), of one of `dtypes`."""
+    if not torch.is_tensor(t) or not t.is_cuda or t.dim() != ndim or t.dtype not in dtypes or not t.is_contiguous() or t.numel() == 0 \
+            or (last is not None and t.shape[-1] < last):
+        raise L.UpsError("{}: a contiguous {}-D device tensor of {}{} expected (got {})".format(
+            what, ndim, " / ".join(str(d) for d in dtypes), "" if last is None else " with >= {} channels".format(last),
+            "{} {} contiguous={}".format(tuple(t.shape), t.dtype, t.is_contiguous()) if torch.is_tensor(t) else type(t).__name__))
+    return t
+
+
+def _canvas_out(what, out, shape, device):
+    if out is None:
+        return torch.empty(shape, dtype=torch.uint8, device=device)
+    if out.dtype != torch.uint8 or tuple(out.shape) != tuple(shape) or not out.is_cuda or not out.is_contiguous() or out.data_ptr() % 16:
+        raise L.UpsError("{}: out must be a contiguous 16-byte aligned uint8 device tensor {} (got {} {})".format(
+            what, tuple(shape), tuple(out.shape), out.dtype))
+    return out
+
+
+_IMG_DTYPES = (torch.float32, torch.bfloat16)
+
+
+def canvas_images(x, cols=None, out=None):
+    """x [N,H,W,ld >= 3] fp32 / bf16 in [-1,1] (channels 0..2 are R, G, B; `generated` comes with 8) -> uint8 [rows*H, cols*W, 3]
+    (ups_canvas_images).  Bytes: uint8(clamp((v + 1) * 127.5, 0, 255)), truncating; missing tiles 127."""
+    x = _canvas_src("canvas_images: x [N,H,W,ld]", x, 4, _IMG_DTYPES, last=3)
+    N, H, W, ld = x.shape
+    rows, cols = canvas_grid(N, cols)
+    out = _canvas_out("canvas_images", out, (rows * H, cols * W, 3), x.device)
+    L.call("ups_canvas_images", L.ptr(x), L.dt(x), N, H, W, ld, rows, cols, L.ptr(out), L.stream())
+    return out
+
+
+def canvas_mask_rgb(colors, mask=None, bits=None, n_parts=None, one_hot=False, cols=None, out=None):
+    """mask2rgb as a canvas (ups_canvas_mask_rgb): colors uint8 [P,3] on the device (quantised by the host); exactly one of
+    mask [N,H,W,P] fp32 (arg-max, lowest index on ties; one_hot=True: taken as one-hot already, nn.mask2rgb(make_hot=False)) and
+    bits [N,H,W] int32 (the hard bits of part_softmax, n_parts <= 32) -> uint8 [rows*H, cols*W, 3]."""
+    if (mask is None) == (bits is None):
+        raise L.UpsError("canvas_mask_rgb: exactly one of mask and bits")
+    if mask is not None:
+        mask = _canvas_src("canvas_mask_rgb: mask [N,H,W,P]", mask, 4, (torch.float32,))
+        N, H, W, P = mask.shape
+    else:
+        bits = _canvas_src("canvas_mask_rgb: bits [N,H,W]", bits, 3, (torch.int32,))
+        N, H, W = bits.shape
+        P = int(n_parts or 0)
+        if not 1 <= P <= 32:
+            raise L.UpsError("canvas_mask_rgb: bits need 1 <= n_parts <= 32 (got {})".format(n_parts))
+    colors = _canvas_src("canvas_mask_rgb: colors [P,3]", colors, 2, (torch.uint8,))
+    if tuple(colors.shape) != (P, 3):
+        raise L.UpsError("canvas_mask_rgb: colors must be uint8 [{},3] (got {})".format(P, tuple(colors.shape)))
+    rows, cols = canvas_grid(N, cols)
+    src = mask if mask is not None else bits
+    out = _canvas_out("canvas_mask_rgb", out, (rows * H, cols * W, 3), src.device)
+    L.call("ups_canvas_mask_rgb", L.ptr(mask), L.ptr(bits), int(bool(one_hot)), L.ptr(colors), N, H, W, P, rows, cols, L.ptr(out),
+           L.stream())
+    return out
+
+
+def canvas_assigned_parts(view0, view1, hard0=None, hard1=None, bits0=None, bits1=None, n_parts=None, out=None):
+    """assigned_parts (model.py:990-1006) in one launch (ups_canvas_assigned_parts): views [B,H,W,ld >= 3] fp32 / bf16 (same dtype
+    and shape), the hard masks of view 0 and view 1 as hard0 / hard1 [B,H,W,P] fp32 or bits0 / bits1 [B,H,W] int32 (n_parts <= 32)
+    -> uint8 [ceil(P/5)*g*H, 5*g*W, 3], g = ceil(sqrt(2B))."""
+    view0 = _canvas_src("canvas_assigned_parts: view0 [B,H,W,ld]", view0, 4, _IMG_DTYPES, last=3)
+    view1 = _canvas_src("canvas_assigned_parts: view1 [B,H,W,ld]", view1, 4, _IMG_DTYPES, last=3)
+    if view0.shape != view1.shape or view0.dtype != view1.dtype:
+        raise L.UpsError("canvas_assigned_parts: the two views must agree in shape and dtype (got {} {}, {} {})".format(
+            tuple(view0.shape), view0.dtype, tuple(view1.shape), view1.dtype))
+    B, H, W, ld = view0.shape
+    by_bits = bits0 is not None
+    if by_bits == (hard0 is not None) or (bits1 is None) != (bits0 is None) or (hard1 is None) != (hard0 is None):
+        raise L.UpsError("canvas_assigned_parts: either hard0 and hard1 or bits0 and bits1")
+    if by_bits:
+        P = int(n_parts or 0)
+        if not 1 <= P <= 32:
+            raise L.UpsError("canvas_assigned_parts: bits need 1 <= n_parts <= 32 (got {})".format(n_parts))
+        for nm, b in (("bits0", bits0), ("bits1", bits1)):
+            if tuple(_canvas_src("canvas_assigned_parts: " + nm + " [B,H,W]", b, 3, (torch.int32,)).shape) != (B, H, W):
+                raise L.UpsError("canvas_assigned_parts: {} must be [{},{},{}] (got {})".format(nm, B, H, W, tuple(b.shape)))
+    else:
+        P = hard0.shape[-1] if torch.is_tensor(hard0) and hard0.dim() == 4 else 0
+        for nm, h in (("hard0", hard0), ("hard1", hard1)):
+            if tuple(_canvas_src("canvas_assigned_parts: " + nm + " [B,H,W,P]", h, 4, (torch.float32,)).shape) != (B, H, W, P):
+                raise L.UpsError("canvas_assigned_parts: {} must be [{},{},{},{}] (got {})".format(nm, B, H, W, P, tuple(h.shape)))
+    g = canvas_grid(2 * B)[0]
+    out = _canvas_out("canvas_assigned_parts", out, (-(-P // 5) * g * H, 5 * g * W, 3), view0.device)
+    L.call("ups_canvas_assigned_parts", L.ptr(hard0), L.ptr(hard1), L.ptr(bits0), L.ptr(bits1), L.ptr(view0), L.ptr(view1), L.dt(view0),
+           ld, B, H, W, P, L.ptr(out), L.stream())
+    return out
+
+
+CANVAS_LEVELS = (0.01, 0.05, 0.1, 0.25, 0.5, 0.75, 0.9)        # model.py:1009
+CANVAS_RATIOS = (1.0e-3, 5 * 1.0e-3, 1.0e-2, 5 * 1.0e-2)       # model.py:1021
+
+
+def canvas_first_item(m, table, hard=None, bits=None, levels=CANVAS_LEVELS, ratios=CANVAS_RATIOS, out=None):
+    """The four canvases of batch item 0 in one launch (ups_canvas_first_item): m [H,W,P] fp32 (m0_sample[0]), its hard mask as
+    hard [H,W,P] fp32 or bits [H,W] int32 (P <= 32), table uint8 [256,3] on the device (viridis, quantised by the host) ->
+    (levels [P*H, 7*W, 1], edges [P*H, 4*W, 1], p_heatmap [g*H, g*W, 3], masks [g*H, g*W, 1]), g = ceil(sqrt(P)).  The maps are in
+    [0,1] and go through the quantisation of every other image: gray (127) to white (255)."""
+    m = _canvas_src("canvas_first_item: m [H,W,P]", m, 3, (torch.float32,))
+    H, W, P = m.shape
+    if (hard is None) == (bits is None):
+        raise L.UpsError("canvas_first_item: exactly one of hard and bits")
+    if hard is not None:
+        if tuple(_canvas_src("canvas_first_item: hard [H,W,P]", hard, 3, (torch.float32,)).shape) != (H, W, P):
+            raise L.UpsError("canvas_first_item: hard must be [{},{},{}] (got {})".format(H, W, P, tuple(hard.shape)))
+    else:
+        if tuple(_canvas_src("canvas_first_item: bits [H,W]", bits, 2, (torch.int32,)).shape) != (H, W) or P > 32:
+            raise L.UpsError("canvas_first_item: bits must be [{},{}] with P <= 32 (got {}, P = {})".format(H, W, tuple(bits.shape), P))
+    table = _canvas_src("canvas_first_item: table [256,3]", table, 2, (torch.uint8,))
+    if tuple(table.shape) != (256, 3):
+        raise L.UpsError("canvas_first_item: table must be uint8 [256,3] (got {})".format(tuple(table.shape)))
+    nl, nr = len(levels), len(ratios)
+    if not (1 <= nl <= 8 and 1 <= nr <= 8):
+        raise L.UpsError("canvas_first_item: 1..8 levels and 1..8 ratios (got {} and {})".format(nl, nr))
+    g = canvas_grid(P)[0]
+    shapes = ((P * H, nl * W, 1), (P * H, nr * W, 1), (g * H, g * W, 3), (g * H, g * W, 1))
+    out = [None] * 4 if out is None else list(out)
+    out = [_canvas_out("canvas_first_item", o, sh, m.device) for o, sh in zip(out, shapes)]
+    L.call("ups_canvas_first_item", L.ptr(m), L.ptr(hard), L.ptr(bits), H, W, P, (C.c_float * nl)(*levels), nl, (C.c_float * nr)(*ratios), nr,
+           L.ptr(table), L.ptr(out[0]), L.ptr(out[1]), L.ptr(out[2]), L.ptr(out[3]), L.stream())
+    return tuple(out)
+
+
 def spatial_moments(x, gamma, rect_px=None, half=0, kl_sums=None):
     """kl_sums (fp32 [>= 16] device buffer): the same pass also writes sum x * log(P x + 1e-20) -- the categorical KL of the map,
     view 1's other prior term -- to kl_sums[0] (ups_spatial_moments_kl)."""

@@ -97,7 +97,8 @@ def load_config(paths):
 
 def main(argv=None):
     ap = argparse.ArgumentParser(prog="upsparts-run")
-    ap.add_argument("-t", "--train", nargs="+", default=None, help="training yaml(s)")
+    ap.add_argument("-t", "--train", nargs="+", default=None,
+                    help="training yaml(s); --set log_images=true also writes the image logs, train/<name>_<step:07>.png")
     ap.add_argument("-e", "--eval", nargs="+", default=None,
                     help="evaluation yaml(s): test-mode forward over the dataset, outputs pickled (edflow -e work-alike)")
     ap.add_argument("--transfer", nargs="+", default=None,
