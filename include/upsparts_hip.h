@@ -27,8 +27,9 @@ extern "C" {
 
 /* 2: ups_conv_desc grew by out_act / res_act, ups_wgrad_desc by in_f16, UPS_F16 was added (round 3) -- a stale library
  * built against the older structs ignores those fields silently, so the loader also compares ups_struct_sizes().
- * 3: ups_wgrad_desc grew by dout_f8 / dout_f8_scale / in_f8_scale / in_f8_amax (the fp8 weight gradient, round 5). */
-#define UPS_ABI_VERSION 4
+ * 3: ups_wgrad_desc grew by dout_f8 / dout_f8_scale / in_f8_scale / in_f8_amax (the fp8 weight gradient, round 5).
+ * 5: ups_gather_views was added (device-resident training data): a binding that expects it refuses an older library by number. */
+#define UPS_ABI_VERSION 5
 
 /* UPS_F16 (IEEE half): element type of FORWARD tensors of precision-critical scopes (the mask decoder): ups_conv_igemm,
  * ups_weight_prep(_batch), ups_bilinear2x_fwd, ups_convert / ups_pad_convert accept it; gradients are never fp16 (range): the
@@ -449,6 +450,22 @@ int ups_canvas_assigned_parts(const float* hard0, const float* hard1, const uint
 int ups_canvas_first_item(const float* m, const float* hard, const uint32_t* bits, int32_t H, int32_t W, int32_t P, const float* levels,
                           int32_t n_levels, const float* ratios, int32_t n_ratios, const uint8_t* table, uint8_t* c_levels,
                           uint8_t* c_edges, uint8_t* c_heat, uint8_t* c_masks, void* stream);
+
+/* ---------------------------------------------------------------- device-resident training data (csrc/dataset.hip)
+ * The batch views of eddata's StochasticPairs / AugmentedPair2 (cub/code/data/data.py:157-175) gathered from a uint8 image store that
+ * stays in device memory, instead of decoded, flipped, normalised and stacked on the host every step.
+ *   images [n_images, S, S, 3] uint8 (every image already resized to S x S);  plan [B, 3] int32, DEVICE: source image of view0, source
+ *   image of view1, flip bits (bit 0 horizontal, bit 1 vertical: one draw flips both views);  view0, view1, target [B, S, S, 3] fp32.
+ *     view0[b][y][x][c] = target[b][y][x][c] = lut(images[plan[b][0]][fv ? S-1-y : y][fh ? S-1-x : x][c])
+ *     view1[b][y][x][c] =                      lut(images[plan[b][1]][the same source pixel][c])
+ *     lut(u) = float(u) / 127.5f - 1.0f in fp32, two correctly rounded operations: NumPy's `np.float32(u) / 127.5 - 1.0` bit for bit.
+ * Channels are never reversed.  target may be NULL (StochasticPairs has no view0_target); it is stored from view0's registers.
+ * UPS_E_ARG, nothing launched: B <= 0, S <= 0, n_images <= 0, a NULL required pointer, B * S * S * 3 > 2^31 - 1.  The caller
+ * validates the plan's indices (it wrote them); an index outside [0, n_images) reads nothing and writes that item as NaN.
+ * S % 4 == 0 with a 4-byte aligned store and 16-byte aligned outputs runs four pixels per lane (dword loads, float4 stores); any other
+ * shape or alignment one pixel per lane.  No scratch, no atomics: the same plan gives the same bits. */
+int ups_gather_views(const uint8_t* images, int64_t n_images, const int32_t* plan, int32_t B, int32_t S, float* view0, float* view1,
+                     float* target, void* stream);
 
 /* ---------------------------------------------------------------- mask priors (M:652-797), fused
  * One pass over l/m per view producing the partial sums, one fused backward producing dl.

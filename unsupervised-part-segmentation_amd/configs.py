@@ -7,6 +7,12 @@ with n_parts / batch_size / use_tps overridable (BASELINE configs use P=10, use_
 """
 import copy
 
+# yaml keys of the device-resident data path (data.device_batches): key -> default.
+#   data_on_device         decode the csv's images once into a uint8 store in device memory and gather the batches there
+#   data_cache             path of an on-disk copy of that store (<path>.npy + <path>.json), rebuilt whenever the csv or the size changes
+#   data_on_device_max_gb  refuse (ValueError) a store of more than this many GB (10^9 bytes)
+DATA_ON_DEVICE = {"data_on_device": False, "data_cache": None, "data_on_device_max_gb": 16}
+
 
 def _stair(start, start_value, step_size, stair_factor, cmin, cmax):
     return {"var_type": "staircase", "options": {"start": start, "start_value": start_value,

@@ -16,12 +16,23 @@
 The exact resize filter / cropping of eddata's ``preprocess_image`` is not visible in the reference tree: bilinear resize
 of the whole image is used (UNVERIFIED).  ``batches`` turns a dataset into the ``{"view0", "view1"[, "view0_target"]}``
 float32 NHWC batches ``Trainer.iterate`` consumes, with a small thread pool for decoding.
+
+Device-resident data (yaml ``data_on_device: True``; docs/design/surroundings.md 8c).  ``batches`` decodes and resizes 2 B files per
+step.  ``preprocess_image`` is ``uint8 -> / 127.5 - 1``, so nothing is lost by decoding every file ONCE into a uint8 array
+``[N,S,S,3]`` (``build_u8_store``, optionally cached on disk under ``data_cache``) and keeping it in device memory.
+``device_batches`` then draws the SAME pairs, flips and order as ``batches`` -- ``StochasticPairs.plan_example`` is the decision half
+of ``get_example`` -- sends B x 3 int32 per step and lets ``ups_gather_views`` (csrc/dataset.hip) write the float32 views: the same
+bits as the host path.  The albumentations-style augmentations and the label maps stay host-only.
 """
 import concurrent.futures as cf
+import hashlib
+import json
 import os
 
 import numpy as np
 import torch
+
+from .configs import DATA_ON_DEVICE
 
 
 def add_choices(character_ids):
@@ -59,10 +70,14 @@ class StochasticPairs(object):
     def __len__(self):
         return len(self.labels["character_id"])
 
-    def preprocess_image(self, path):
+    def preprocess_u8(self, path):
+        """The decoded, resized image as uint8 [S,S,3]: what ``preprocess_image`` normalises and what the device store keeps."""
         from PIL import Image
         img = Image.open(path).convert("RGB").resize((self.size, self.size), Image.BILINEAR)
-        return np.asarray(img, dtype=np.float32) / 127.5 - 1.0
+        return np.asarray(img, dtype=np.uint8)
+
+    def preprocess_image(self, path):
+        return self.preprocess_u8(path).astype(np.float32) / 127.5 - 1.0
 
     def _rng(self, i):
         """Per-index, per-draw generator: examples are decoded by a thread pool, so partner and flip decisions must not
@@ -82,13 +97,20 @@ class StochasticPairs(object):
         from PIL import Image
         return np.asarray(Image.open(path).resize((self.size, self.size), Image.NEAREST), dtype=np.int64)
 
-    def get_example(self, i):
+    def plan_example(self, i):
+        """The decisions of example i without its pixels: (i, partner j, flip_h, flip_v).  Draws from ``_rng(i)`` in a fixed order --
+        the partner, the horizontal draw (only with ``data_flip_h``), the vertical draw (only with ``data_flip_v``) -- so the host
+        path (``get_example``) and the device path (``device_batches``) see the same examples."""
         rng = self._rng(i)
         j = self.pick_partner(i, rng)
+        flip_h = bool(self.flip_h and rng.rand() < 0.5)
+        flip_v = bool(self.flip_v and rng.rand() < 0.5)
+        return int(i), j, flip_h, flip_v
+
+    def get_example(self, i):
+        i, j, flip_h, flip_v = self.plan_example(i)
         view0 = self.preprocess_image(self.labels["file_path_"][i])
         view1 = self.preprocess_image(self.labels["file_path_"][j])
-        flip_h = self.flip_h and rng.rand() < 0.5
-        flip_v = self.flip_v and rng.rand() < 0.5
         if flip_h:
             view0, view1 = view0[:, ::-1].copy(), view1[:, ::-1].copy()
         if flip_v:
@@ -196,5 +218,136 @@ def batches(dataset, batch_size, shuffle=True, workers=8, seed=0, epochs=None, p
             out = {k: torch.from_numpy(np.stack([e[k] for e in exs])) for k in exs[0]}
             if pad_last:
                 out["valid"] = valid
+            yield out
+        ep += 1
+
+
+# ------------------------------------------------------------------ device-resident data
+MAX_STORE_WORKERS = 16          # decoding threads of build_u8_store: a fixed cap, never the machine's CPU count
+
+
+def _store_key(dataset):
+    """What a cached store must have been built from: row count, size and the csv's path column."""
+    paths = "\n".join(str(p) for p in dataset.labels["relative_file_path_"])
+    return {"N": len(dataset), "spatial_size": int(dataset.size), "sha1": hashlib.sha1(paths.encode("utf-8")).hexdigest()}
+
+
+def _cache_paths(cache):
+    npy = cache if cache.endswith(".npy") else cache + ".npy"
+    return npy, npy[:-len(".npy")] + ".json"
+
+
+def check_on_device(dataset):
+    """The refusals of ``data_on_device`` (ValueError, before a file or the device is touched): host-only transforms, and a store
+    that would not fit ``data_on_device_max_gb``.  There is no silent fall-back to the host path."""
+    cfg = dataset.config
+    host_only = [k for k in ("data_augment_appearance", "data_augment_shape") if cfg.get(k, False)]
+    if dataset.gt_column:
+        host_only.append("data_gt_segmentation_column")
+    if host_only:
+        raise ValueError("data_on_device cannot be combined with {}: those transforms / label maps exist on the host path only "
+                         "(set data_on_device: False, or drop them)".format(", ".join(host_only)))
+    nbytes = len(dataset) * int(dataset.size) ** 2 * 3
+    max_gb = float(cfg.get("data_on_device_max_gb", DATA_ON_DEVICE["data_on_device_max_gb"]))
+    if nbytes > max_gb * 1e9:
+        raise ValueError("data_on_device: the uint8 store of {} images at {}x{} is {:.6g} GB, more than data_on_device_max_gb = {:g} GB"
+                         .format(len(dataset), dataset.size, dataset.size, nbytes / 1e9, max_gb))
+
+
+def build_u8_store(dataset, cache=None, workers=8):
+    """Every row of the dataset's csv decoded ONCE: uint8 [N,S,S,3] (``dataset.preprocess_u8``, a pool of at most 16 threads).
+    ``cache`` (yaml ``data_cache``): the array is kept as ``<cache>.npy`` beside ``<cache>.json`` = {N, spatial_size, sha1 of the joined
+    ``relative_file_path_`` column}; a cache whose sidecar matches is loaded without opening an image, any other is rebuilt, never used."""
+    key = _store_key(dataset)
+    shape = (key["N"], key["spatial_size"], key["spatial_size"], 3)
+    if cache:
+        npy, side = _cache_paths(cache)
+        try:
+            with open(side) as f:
+                found = json.load(f)
+            if found == key:
+                store = np.load(npy)
+                if store.dtype == np.uint8 and store.shape == shape:
+                    return store
+        except (OSError, ValueError):
+            pass                    # no cache, or an unreadable one: build it
+    paths = dataset.labels["file_path_"]
+    workers = max(1, min(int(workers), MAX_STORE_WORKERS))
+    store = np.empty(shape, dtype=np.uint8)
+    with cf.ThreadPoolExecutor(max_workers=workers) as pool:
+        for i, img in enumerate(pool.map(dataset.preprocess_u8, paths)):
+            store[i] = img
+    if cache:
+        # the sidecar goes first and comes back last: whatever interrupts the two writes leaves no sidecar that vouches for the
+        # wrong array.  Both are written under a temporary name and renamed (several ranks may build the same cache at once).
+        if os.path.dirname(npy):
+            os.makedirs(os.path.dirname(npy), exist_ok=True)
+        if os.path.exists(side):
+            os.remove(side)
+        tmp = "{}.tmp-{}".format(npy, os.getpid())
+        with open(tmp, "wb") as f:
+            np.save(f, store)
+        os.replace(tmp, npy)
+        with open(tmp, "w") as f:
+            json.dump(key, f)
+        os.replace(tmp, side)
+    return store
+
+
+def fill_plan(dataset, idx, plan):
+    """plan [B,3] int32 (a NumPy view) <- (view0 source, view1 source, flip bits: 1 horizontal | 2 vertical) of the examples `idx`,
+    drawn in order by ``plan_example``.  Every index is checked against the store's row count here, on the host."""
+    n = len(dataset)
+    for r, i in enumerate(idx):
+        i, j, fh, fv = dataset.plan_example(i)
+        if not (0 <= i < n and 0 <= j < n):
+            raise ValueError("data_on_device: example ({}, {}) is outside the store of {} images".format(i, j, n))
+        plan[r, 0], plan[r, 1], plan[r, 2] = i, j, int(fh) | (int(fv) << 1)
+
+
+PLAN_RING = 4                   # pinned plan buffers in flight (a copy is waited for only when its buffer comes round again)
+
+
+def device_batches(dataset, batch_size, device, shuffle=True, seed=0, epochs=None):
+    """``batches`` fed from device memory: the same ``RandomState(seed).permutation`` per epoch, the ragged last batch dropped, the
+    same per-index draw counters -- and so the same tensors, bit for bit -- but float32 NHWC DEVICE tensors, freshly allocated per
+    batch.  Per step the host draws the plan (``fill_plan``), copies its B x 3 int32 from a pinned buffer (non-blocking) and launches
+    ``ups_gather_views`` on the current stream of `device`; nothing is decoded and the host never waits for the device.
+    The store is built (or loaded from ``data_cache``) and uploaded HERE, not at the first ``next()``: the refusals of
+    ``check_on_device`` and a missing image tree raise at construction."""
+    from . import lib as L
+    check_on_device(dataset)
+    if batch_size < 1 or len(dataset) < batch_size:
+        raise ValueError("data_on_device: batch_size {} with {} images gives no batch".format(batch_size, len(dataset)))
+    device = torch.device(device)
+    store = build_u8_store(dataset, cache=dataset.config.get("data_cache", DATA_ON_DEVICE["data_cache"]))
+    images = torch.from_numpy(store).to(device)
+    with_target = dataset.n_images == 3          # AugmentedPair2: view0_target = a copy of view0 (cub/code/data/data.py:164)
+    return _device_batches(L, dataset, images, batch_size, device, shuffle, seed, epochs, with_target)
+
+
+def _device_batches(L, dataset, images, batch_size, device, shuffle, seed, epochs, with_target):
+    N, S = images.shape[0], images.shape[1]
+    rng = np.random.RandomState(seed)
+    ring = [torch.empty((batch_size, 3), dtype=torch.int32).pin_memory() for _ in range(PLAN_RING)]
+    copied = [None] * PLAN_RING
+    k, ep = 0, 0
+    while epochs is None or ep < epochs:
+        order = rng.permutation(N) if shuffle else np.arange(N)
+        for b in range(len(order) // batch_size):
+            slot = k % PLAN_RING
+            k += 1
+            if copied[slot] is not None:
+                copied[slot].synchronize()       # (four batches old: long done)
+            fill_plan(dataset, order[b * batch_size:(b + 1) * batch_size], ring[slot].numpy())
+            with torch.cuda.device(device):
+                plan = torch.empty((batch_size, 3), dtype=torch.int32, device=device)
+                plan.copy_(ring[slot], non_blocking=True)
+                copied[slot] = torch.cuda.Event()
+                copied[slot].record()
+                out = {key: torch.empty((batch_size, S, S, 3), dtype=torch.float32, device=device)
+                       for key in (("view0", "view1", "view0_target") if with_target else ("view0", "view1"))}
+                L.call("ups_gather_views", L.ptr(images), N, L.ptr(plan), batch_size, S, L.ptr(out["view0"]), L.ptr(out["view1"]),
+                       L.ptr(out.get("view0_target")), L.stream())
             yield out
         ep += 1

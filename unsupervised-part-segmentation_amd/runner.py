@@ -69,14 +69,21 @@ class SyntheticPairs(object):
             yield {k: torch.rand(B, S, S, 3, generator=self.gen) * 2 - 1 for k in ("view0", "view1", "view0_target")}
 
 
-def make_dataset(cfg, rank=0, strict=False):
+def make_dataset(cfg, rank=0, strict=False, device=None):
     """The yaml's `dataset:` class on this rank's shard seed.  Returns (dataset, None), or (SyntheticPairs, reason) when the data is
     NOT THERE -- the csv / image root does not exist or the dataset's package cannot be imported -- and `strict` is off; that fallback
     is logged at WARNING level here and again with every logged step (main).  Any other exception is a bug and propagates: a run with
-    a wrong key must not quietly train on noise (round-5 verdict)."""
+    a wrong key must not quietly train on noise (round-5 verdict).
+    `data_on_device: True`: the csv pair datasets are fed by `data.device_batches` from a uint8 store on `device` (default: the
+    current HIP device) -- same seeds, same batches; every rank holds its own copy of the store."""
     try:
         cls = DATA_ALIASES.get(cfg["dataset"]) or get_obj_from_str(cfg["dataset"])
         ds = cls(dict(cfg, data_seed=D.shard_seed(cfg.get("data_seed", 1), rank)))
+        if cfg.get("data_on_device", False):
+            if not isinstance(ds, _data.StochasticPairs):
+                raise ValueError("data_on_device: {} is not one of the csv pair datasets of data.py".format(cfg["dataset"]))
+            dev = device if device is not None else torch.device("cuda", torch.cuda.current_device())
+            return _data.device_batches(ds, cfg["batch_size"], dev, seed=D.shard_seed(0, rank)), None
         return (_data.batches(ds, cfg["batch_size"], seed=D.shard_seed(0, rank)) if isinstance(ds, _data.StochasticPairs) else ds), None
     except (FileNotFoundError, NotADirectoryError, ImportError) as e:
         if strict:
@@ -128,7 +135,8 @@ def main(argv=None):
     Model, Iterator = get_obj_from_str(cfg["model"]), get_obj_from_str(cfg["iterator"])
     # data parallel: `batch_size` is the per-GPU batch (the graph is static in it, model.py:320); every rank draws its own
     # shard order / partners / noise from rank-offset seeds, the weights come from the same seed on every rank
-    dataset, synthetic_why = make_dataset(cfg, rank, args.strict_dataset)
+    dataset, synthetic_why = make_dataset(cfg, rank, args.strict_dataset,
+                                          device=torch.device("cuda", local) if torch.cuda.is_available() else None)
     model = Model(cfg) if Model is not TrainModel else Model(cfg, device=torch.device("cuda", local))
     kw = {"world_size": world, "rank": rank} if Iterator is Trainer else {}
     it = Iterator(cfg, root, model, **kw)
