@@ -3,8 +3,10 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
+#include <type_traits>
 
 #include "../../include/upsparts_hip.h"
+#include "env.h"
 
 typedef __bf16 bf16;
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
@@ -31,6 +33,33 @@ struct UpsPerDevice {
     bool operator!() const { return !((bits >> cur()) & 1ull); }
     UpsPerDevice& operator=(bool v) { if (v) bits |= 1ull << cur(); else bits &= ~(1ull << cur()); return *this; }
 };
+
+// The one launcher of a kernel that may need more than the 64 KB default of dynamic LDS: raises the kernel's limit to `lds_max`
+// bytes once per device (the first caller's value stands: a site whose launches differ in size passes the largest), then launches
+// with `lds` bytes.  UPS_OK, or UPS_E_LAUNCH with a message when the limit cannot be raised; the launch itself is checked by the
+// caller's UPS_LAUNCH_CHECK as after any other launch.  `what` names the kernel in that message.
+template <auto Kernel, typename... A>
+inline int ups_launch_lds(const char* what, size_t lds_max, dim3 grid, dim3 block, size_t lds, hipStream_t s, A... args) {
+    static UpsPerDevice raised;
+    if (!raised) {
+        const hipError_t e = hipFuncSetAttribute((const void*)Kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_max);
+        if (e != hipSuccess) {
+            ups_set_error("ups_launch_lds: cannot raise the LDS limit of %s to %d: %s", what, (int)lds_max, hipGetErrorString(e));
+            return UPS_E_LAUNCH;
+        }
+        raised = true;
+    }
+    hipLaunchKernelGGL(Kernel, grid, block, lds, s, args...);
+    return UPS_OK;
+}
+// f(std::integral_constant<int, V>) -> int for the V of VS... that equals v: a launcher's run-time value picks a template instance.
+// UPS_E_UNSUPPORTED when none does (the caller has checked its eligibility before: not reached).
+template <int... VS, typename F>
+inline int ups_pick(int v, F&& f) {
+    int rc = UPS_E_UNSUPPORTED;
+    (void)((v == VS && ((rc = f(std::integral_constant<int, VS>{})), true)) || ...);
+    return rc;
+}
 
 #define UPS_CHECK_ARG(cond)                                                        \
     do {                                                                           \

@@ -199,7 +199,7 @@ __global__ __launch_bounds__(256) void conv3x3_first_kernel(const FirstK p) {
 
 // Internal entry of ups_conv_igemm's dispatcher.  Returns 1 if the problem is not a first-layer problem, 0 when launched.
 int ups_conv3x3_first_try(const ups_conv_desc* d, hipStream_t s) {
-    { const char* e = getenv("UPS_FIRST_LAYER"); if (e && e[0] == '0') return 1; }     // (read per call: the parity test toggles it)
+    if (!ups_env_on_now("UPS_FIRST_LAYER")) return 1;     // (read per call: the parity test toggles it)
     if (d->dtype != UPS_BF16 || d->ntaps != 9 || d->ci != 8 || d->in_sy != 1 || d->in_sx != 1 || d->out_sy != 1 || d->out_sx != 1 ||
         d->out_oy || d->out_ox || d->hi != d->ho || d->wi != d->wo || d->out_h != d->ho || d->out_w != d->wo)
         return 1;

@@ -1308,35 +1308,17 @@ int launch_bn(const PatchK& k, hipStream_t s) {
     if (kk.res_patch == 2 && !(rp2_ok && kk.sgn_res)) kk.res_patch = 0;    // (this instance has no such path: the residual in the epilogue)
     kk.sgn_off = (int)shmem;
     if (kk.sgn_res) shmem += sgn_bytes;
-    static UpsPerDevice attr_set;
-    if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute((const void*)conv3x3_patch_kernel<T, BN, OCC, SUB, F8, PRE, TAPS, DMAP, CSTD>,
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)((epi > shmem_max ? epi : shmem_max) + sgn_bytes));
-        if (e != hipSuccess) return UPS_E_LAUNCH;
-        attr_set = true;
-    }
-    hipLaunchKernelGGL((conv3x3_patch_kernel<T, BN, OCC, SUB, F8, PRE, TAPS, DMAP, CSTD>), dim3(nblocks), dim3(512), shmem, s, kk, tiles_x, tiles_y, ntn,
-                       kchunks, nblocks);
-    return UPS_OK;
+    return ups_launch_lds<conv3x3_patch_kernel<T, BN, OCC, SUB, F8, PRE, TAPS, DMAP, CSTD>>(
+        "conv3x3_patch_kernel", (epi > shmem_max ? epi : shmem_max) + sgn_bytes, dim3(nblocks), dim3(512), shmem, s, kk, tiles_x, tiles_y, ntn,
+        kchunks, nblocks);
 }
 
-static int static_taps_on() {   // UPS_PATCH_STATIC=0: the descriptor-driven tap loop everywhere (A/B runs)
-    static int v = -1;
-    if (v < 0) { const char* e = getenv("UPS_PATCH_STATIC"); v = (e && e[0] == '0') ? 0 : 1; }
-    return v;
-}
-
-static int dma_patch_on() {   // UPS_PATCH_DMA=0: register-staged patch everywhere (A/B runs)
-    static int v = -1;
-    if (v < 0) { const char* e = getenv("UPS_PATCH_DMA"); v = (e && e[0] == '0') ? 0 : 1; }
-    return v;
-}
-
-static int patch_occ() {   // UPS_PATCH_OCC=1 forces the one-block-per-CU configuration (A/B runs)
-    static int v = -1;
-    if (v < 0) { const char* e = getenv("UPS_PATCH_OCC"); v = (e && e[0] == '1') ? 1 : 2; }
-    return v;
-}
+// UPS_PATCH_STATIC=0: the descriptor-driven tap loop everywhere (A/B runs)
+static int static_taps_on() { return UPS_ENV_ON_CACHED("UPS_PATCH_STATIC"); }
+// UPS_PATCH_DMA=0: register-staged patch everywhere (A/B runs)
+static int dma_patch_on() { return UPS_ENV_ON_CACHED("UPS_PATCH_DMA"); }
+// UPS_PATCH_OCC=1 forces the one-block-per-CU configuration (A/B runs)
+static int patch_occ() { return UPS_ENV_OFF_CACHED("UPS_PATCH_OCC") ? 1 : 2; }
 
 template <typename T, int SUB>
 int launch_small(const PatchK& k, hipStream_t s) {
@@ -1372,8 +1354,7 @@ int launch_t(const PatchK& k, hipStream_t s) {
             const bool big128 = patch_occ() == 2 && tiles8 * ups_cdiv(k.co_fill, 128) >= 512;
             const bool big64 = patch_occ() == 2 && tiles8 * ups_cdiv(k.co_fill, 64) >= 512;
             // whole 128-channel double chunks on a grid of two blocks per CU: the block-scaled K = 128 MFMA (UPS_F8_SCALED=0: off)
-            static int scaled = -1;
-            if (scaled < 0) { const char* e = getenv("UPS_F8_SCALED"); scaled = (e && e[0] == '0') ? 0 : 1; }
+            const bool scaled = UPS_ENV_ON_CACHED("UPS_F8_SCALED");
             if (scaled && k.ci % 128 == 0) {
                 if (k.co_fill > 64 && big128) return k.f8_e5m2 ? launch_bn<T, 128, 2, TS, 4, true>(k, s) : launch_bn<T, 128, 2, TS, 3, true>(k, s);
                 if (k.co_fill <= 64 && big64) return k.f8_e5m2 ? launch_bn<T, 64, 2, TS, 4, true>(k, s) : launch_bn<T, 64, 2, TS, 3, true>(k, s);
@@ -1402,12 +1383,10 @@ int launch_t(const PatchK& k, hipStream_t s) {
         if (k.co_fill > 64 && k.ci > 32) {
             if (patch_occ() == 2 && !k.out_f8_amax && tiles * ups_cdiv(k.co_fill, 128) >= 512) return launch_v<T, 128, 2>(k, s);
             // a grid of one 128-wide block per CU: 64-wide tiles put two blocks on every CU instead (4 waves per SIMD)
-            static int mid = -1;
-            if (mid < 0) { const char* e = getenv("UPS_PATCH_MID"); mid = (e && e[0] == '0') ? 0 : 1; }
+            const bool mid = UPS_ENV_ON_CACHED("UPS_PATCH_MID");
             if (mid && patch_occ() == 2 && tiles * ups_cdiv(k.co_fill, 64) >= 512) return launch_v<T, 64, 2>(k, s);
             {   // at most one 128-wide block per CU, many channel chunks: 64-wide tiles with chunk-granular weight stages (CSTD)
-                static int cst = -1;
-                if (cst < 0) { const char* e = getenv("UPS_PATCH_CST"); cst = (e && e[0] == '0') ? 0 : 1; }
+                const bool cst = UPS_ENV_ON_CACHED("UPS_PATCH_CST");
                 const bool dmap = dma_patch_on() && k.act_in == UPS_ACT_NONE && !k.mask && !k.mask_grad && k.ci % 32 == 0;
                 if (cst && static_taps_on() && dmap && !k.out_f8_amax && k.ci >= 128 && tiles * ups_cdiv(k.co_fill, 128) <= 256) {
                     if (k.taps_static == 1) return launch_bn<T, 64, 1, TS, 0, false, 1, true, true>(k, s);
@@ -1419,8 +1398,7 @@ int launch_t(const PatchK& k, hipStream_t s) {
         if (k.co_fill > 32) {
             // a single input chunk with many outputs (the input gradient of the P-channel logit convolution: 16 -> 256 channels,
             // a store-bound launch): 128-wide tiles halve the number of blocks and patch loads (0.55 -> 0.48 ms; UPS_PATCH_THIN128=0: off)
-            static int thin128 = -1;
-            if (thin128 < 0) { const char* e = getenv("UPS_PATCH_THIN128"); thin128 = (e && e[0] == '0') ? 0 : 1; }
+            const bool thin128 = UPS_ENV_ON_CACHED("UPS_PATCH_THIN128");
             // (not when the launch has to write an fp8 copy of its output: the 128-wide two-blocks-per-CU instance cannot -- EMITS)
             if (thin128 && k.co_fill > 64 && patch_occ() == 2 && tiles * ups_cdiv(k.co_fill, 128) >= 512) {
                 // a launch that writes an fp8 copy takes the descriptor-tap form of the 128-wide instance (the one that emits)
@@ -1433,8 +1411,7 @@ int launch_t(const PatchK& k, hipStream_t s) {
         {   // few outputs over many input chunks (the P-channel logit convolution: 256 -> 10 at 128x128): the 32-wide instance keeps one
             // block per CU busy with one exposed patch round trip per chunk; UPS_PATCH_THINOUT=64 / 128 tries the two-blocks-per-CU
             // instances on it (three quarters / seven eighths of their MFMA columns idle, but the launch is latency-bound)
-            static int thinout = -1;
-            if (thinout < 0) { const char* e = getenv("UPS_PATCH_THINOUT"); thinout = e ? atoi(e) : 0; }
+            const int thinout = (int)UPS_ENV_INT_CACHED("UPS_PATCH_THINOUT", 0);
             if (thinout == 64 && k.ci > 32 && patch_occ() == 2 && tiles >= 512) return launch_v<T, 64, 2>(k, s);
             if (thinout == 128 && k.ci > 32 && patch_occ() == 2 && tiles >= 512 && !k.out_f8_amax) return launch_v<T, 128, 2>(k, s);
         }
@@ -1470,13 +1447,11 @@ int ups_conv3x3_patch_try(const ups_conv_desc* d, hipStream_t s) {
     }
     const bool small = d->hi == d->wi && (d->hi == 8 || d->hi == 4) && d->n % ((TS / d->hi) * (TS / d->hi)) == 0;
     {
-        static int small_on = -1;
-        if (small_on < 0) { const char* e = getenv("UPS_NO_SMALL_PATCH"); small_on = (e && e[0] == '1') ? 0 : 1; }
+        const bool small_on = !UPS_ENV_OFF_CACHED("UPS_NO_SMALL_PATCH");
         // ragged tiles (UPS_PATCH_RAGGED=0: off): plain forward / input-gradient launches only -- no depth-to-space output, part
         // masks, fp8 operands or copies (their store loops and scale maxima assume whole tiles), at least one whole tile row's worth
         // of pixels so that the launch is not mostly padding
-        static int ragged_on = -1;
-        if (ragged_on < 0) { const char* e = getenv("UPS_PATCH_RAGGED"); ragged_on = (e && e[0] == '0') ? 0 : 1; }
+        const bool ragged_on = UPS_ENV_ON_CACHED("UPS_PATCH_RAGGED");
         const bool ragged_ok = ragged_on && d->hi >= 12 && d->wi >= 12 && !d->d2s && !d->mask_bits && !d->mask_grad && !d->f8_deq &&
                                !d->in_f8 && !d->out_f8 && !d->out_f8_amax;
         if ((d->hi % TS || d->wi % TS) && !(small && small_on) && !ragged_ok) return 1;
@@ -1543,15 +1518,13 @@ int ups_conv3x3_patch_try(const ups_conv_desc* d, hipStream_t s) {
     k.out_act = d->out_act; k.res_act = d->res_act;
     {   // residual block: res == in, channel chunk c <-> output channels 32c.. (no CoordConv channels are part of `in`), whole chunks,
         // 16-bit, one tile per image, an N-tile of at least two 16-channel blocks per wave (BN >= 64 in launch_t's choice below)
-        static int rp_on = -1;
-        if (rp_on < 0) { const char* e = getenv("UPS_RES_PATCH"); rp_on = (e && e[0] == '0') ? 0 : 1; }
+        const bool rp_on = UPS_ENV_ON_CACHED("UPS_RES_PATCH");
         k.res_patch = rp_on && d->res && d->res == d->in && d->ldr == d->ldi && d->ci == d->co_fill && d->co == d->co_fill && d->ci % 32 == 0 &&
                       d->dtype != UPS_F32 && !small && !d->dact && !d->mask_bits && !d->mask_grad && !d->d2s && !d->f8_deq && !d->out_f32 &&
                       d->act_in == UPS_ACT_NONE &&    // (with activation-on-load the patch holds act(x), the residual wants x)
                       dma_patch_on() && static_taps_on() && (fwd || flip);       // ... and only the DMA-patch instances implement it
         // round 6: the input gradient of a residual block whose act' arrives as sign bytes (leaky ReLU: 1 / slope exists)
-        static int rp2_on = -1;
-        if (rp2_on < 0) { const char* e = getenv("UPS_RES_PATCH_DGRAD"); rp2_on = (e && e[0] == '0') ? 0 : 1; }
+        const bool rp2_on = UPS_ENV_ON_CACHED("UPS_RES_PATCH_DGRAD");
         if (rp_on && rp2_on && !k.res_patch && d->res && d->res == d->in && d->ldr == d->ldi && d->ci == d->co_fill && d->co == d->co_fill &&
             d->ci % 32 == 0 && d->dtype == UPS_BF16 && !small && d->dact && k.dact_bits && d->dact_kind == UPS_ACT_LRELU && d->act_slope > 0.f &&
             (d->ldd & 63) == 0 && (((uintptr_t)k.dact_bits) & 7) == 0 && !d->mask_bits && !d->mask_grad && !d->d2s && !d->f8_deq && !d->out_f32 &&

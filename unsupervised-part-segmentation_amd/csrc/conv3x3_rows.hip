@@ -420,14 +420,7 @@ template <typename T, int CI, int LW, int NR, bool FLIP>
 int launch_rows2(const RowsK& k, hipStream_t s) {
     constexpr int W = 1 << LW, KC = CI / 32;
     constexpr size_t smem = (size_t)NR * KC * (W + 2) * 64 + 8 * 16 * 80 + 256;
-    static UpsPerDevice attr_set;
-    if (!attr_set) {
-        if (hipFuncSetAttribute((const void*)conv3x3_rows2_kernel<T, CI, LW, NR, FLIP>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) != hipSuccess)
-            return UPS_E_LAUNCH;
-        attr_set = true;
-    }
-    hipLaunchKernelGGL((conv3x3_rows2_kernel<T, CI, LW, NR, FLIP>), dim3(k.n * k.bands), dim3(512), smem, s, k);
-    return UPS_OK;
+    return ups_launch_lds<conv3x3_rows2_kernel<T, CI, LW, NR, FLIP>>("conv3x3_rows2_kernel", smem, dim3(k.n * k.bands), dim3(512), smem, s, k);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------
@@ -777,28 +770,14 @@ template <int CI, int LWI, int NR>
 int launch_rows_s2x2(const RowsK& k, hipStream_t s) {
     constexpr int WI = 1 << LWI, KC = CI / 32;
     constexpr size_t smem = (size_t)NR * KC * 2 * (WI / 2 + 1) * 64 + 8 * 16 * 80 + 512;
-    static UpsPerDevice attr_set;
-    if (!attr_set) {
-        if (hipFuncSetAttribute((const void*)conv3x3_rows_s2x2_kernel<CI, LWI, NR>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) != hipSuccess)
-            return UPS_E_LAUNCH;
-        attr_set = true;
-    }
-    hipLaunchKernelGGL((conv3x3_rows_s2x2_kernel<CI, LWI, NR>), dim3(k.n * k.bands), dim3(512), smem, s, k);
-    return UPS_OK;
+    return ups_launch_lds<conv3x3_rows_s2x2_kernel<CI, LWI, NR>>("conv3x3_rows_s2x2_kernel", smem, dim3(k.n * k.bands), dim3(512), smem, s, k);
 }
 
 template <int CI, int LWI, int NR>
 int launch_rows_s2(const RowsK& k, hipStream_t s) {
     constexpr int WI = 1 << LWI, KC = CI / 32;
     constexpr size_t smem = (size_t)NR * KC * 2 * (WI / 2 + 1) * 64 + 8 * 16 * 80 + 512;
-    static UpsPerDevice attr_set;
-    if (!attr_set) {
-        if (hipFuncSetAttribute((const void*)conv3x3_rows_s2_kernel<CI, LWI, NR>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) != hipSuccess)
-            return UPS_E_LAUNCH;
-        attr_set = true;
-    }
-    hipLaunchKernelGGL((conv3x3_rows_s2_kernel<CI, LWI, NR>), dim3(k.n * k.bands), dim3(512), smem, s, k);
-    return UPS_OK;
+    return ups_launch_lds<conv3x3_rows_s2_kernel<CI, LWI, NR>>("conv3x3_rows_s2_kernel", smem, dim3(k.n * k.bands), dim3(512), smem, s, k);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------
@@ -998,18 +977,11 @@ template <typename T, int SW>
 int launch_thinout(const ThinK& k, hipStream_t s) {
     constexpr int NR = SW == 16 ? 6 : 7;
     constexpr size_t smem = (size_t)NR * 8 * (SW + 2) * 64 + 2 * 8 * SW * 20 * 4;
-    static UpsPerDevice attr_set;
-    if (!attr_set) {
-        if (hipFuncSetAttribute((const void*)conv3x3_thinout_kernel<T, NR, SW>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) != hipSuccess)
-            return UPS_E_LAUNCH;
-        attr_set = true;
-    }
-    hipLaunchKernelGGL((conv3x3_thinout_kernel<T, NR, SW>), dim3(k.n * k.bands * k.strips), dim3(512), smem, s, k);
-    return UPS_OK;
+    return ups_launch_lds<conv3x3_thinout_kernel<T, NR, SW>>("conv3x3_thinout_kernel", smem, dim3(k.n * k.bands * k.strips), dim3(512), smem, s, k);
 }
 
 static int rows_on() {       // UPS_ROWS_KERNEL=0: these layers through the patch kernel (A/B runs); "force": also small batches (parity
-    const char* e = getenv("UPS_ROWS_KERNEL");      // tests); read per call
+    const char* e = ups_env_raw_now("UPS_ROWS_KERNEL");      // tests); read per call
     return (e && e[0] == '0') ? 0 : ((e && e[0] == 'f') ? 2 : 1);
 }
 
@@ -1018,14 +990,7 @@ int launch_rows(const RowsK& k, hipStream_t s) {
     constexpr int W = 1 << LW, KC = CI / 32, NCT = W / 16, NCG = 8 / NCT;
     constexpr size_t smem = (size_t)NR * KC * (W + 2) * 64 + (DG == 1 ? (size_t)(NR - 2) * NCG * W * 64 : (DG == 3 ? (size_t)(NR - 2) * 8 * 256 : 0)) +
                             8 * 16 * 80 + 256;
-    static UpsPerDevice attr_set;
-    if (!attr_set) {
-        if (hipFuncSetAttribute((const void*)conv3x3_rows_kernel<T, CI, LW, NR, FLIP, DG>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) != hipSuccess)
-            return UPS_E_LAUNCH;
-        attr_set = true;
-    }
-    hipLaunchKernelGGL((conv3x3_rows_kernel<T, CI, LW, NR, FLIP, DG>), dim3(k.n * k.bands), dim3(512), smem, s, k);
-    return UPS_OK;
+    return ups_launch_lds<conv3x3_rows_kernel<T, CI, LW, NR, FLIP, DG>>("conv3x3_rows_kernel", smem, dim3(k.n * k.bands), dim3(512), smem, s, k);
 }
 
 template <typename T>
@@ -1162,8 +1127,7 @@ int ups_conv3x3_thinout_try(const ups_conv_desc* d, hipStream_t s) {
     k.strips = d->wi / 32; k.band_rows = 32; k.bands = d->hi / 32;
     // UPS_THIN_SW=16: 16-column strips, two blocks per CU (measured equal to the 32-column form at one block per CU: 0.43 ms both;
     // the 64-byte pieces at a 512-byte pixel pitch, not occupancy or prefetch depth, are what the launch is short of)
-    const char* e = getenv("UPS_THIN_SW");
-    if (e && e[0] == '1') {
+    if (ups_env_off_now("UPS_THIN_SW")) {
         k.strips = d->wi / 16;
         return d->dtype == UPS_F16 ? launch_thinout<f16, 16>(k, s) : launch_thinout<bf16, 16>(k, s);
     }
@@ -1194,22 +1158,8 @@ int ups_conv3x3_rows_maskgrad_try(const ups_conv_desc* d, hipStream_t s) {
     constexpr int NR = 8;
     if (d->wi == 128) {
         constexpr size_t smem = (size_t)NR * 130 * 64;
-        static UpsPerDevice attr_set;
-        if (!attr_set) {
-            if (hipFuncSetAttribute((const void*)conv3x3_rows_maskgrad_kernel<NR, 7, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) != hipSuccess)
-                return UPS_E_LAUNCH;
-            attr_set = true;
-        }
-        hipLaunchKernelGGL((conv3x3_rows_maskgrad_kernel<NR, 7, 1>), dim3(k.n * k.bands), dim3(512), smem, s, k);
-    } else {
-        constexpr size_t smem = (size_t)NR * 258 * 64;
-        static UpsPerDevice attr_set;
-        if (!attr_set) {
-            if (hipFuncSetAttribute((const void*)conv3x3_rows_maskgrad_kernel<NR, 8, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) != hipSuccess)
-                return UPS_E_LAUNCH;
-            attr_set = true;
-        }
-        hipLaunchKernelGGL((conv3x3_rows_maskgrad_kernel<NR, 8, 2>), dim3(k.n * k.bands), dim3(512), smem, s, k);
+        return ups_launch_lds<conv3x3_rows_maskgrad_kernel<NR, 7, 1>>("conv3x3_rows_maskgrad_kernel", smem, dim3(k.n * k.bands), dim3(512), smem, s, k);
     }
-    return UPS_OK;
+    constexpr size_t smem = (size_t)NR * 258 * 64;
+    return ups_launch_lds<conv3x3_rows_maskgrad_kernel<NR, 8, 2>>("conv3x3_rows_maskgrad_kernel", smem, dim3(k.n * k.bands), dim3(512), smem, s, k);
 }

@@ -192,7 +192,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_s2_kernel(const S2K p) {
 
 // Internal entry of ups_conv_igemm's dispatcher.  Returns 1 if the problem is not one of these, 0 when launched, < 0 on a set-up error.
 int ups_conv3x3_s2_try(const ups_conv_desc* d, hipStream_t s) {
-    const char* env = getenv("UPS_S2_KERNEL");              // (read per call) "0": off (A/B runs); "force": also small launches (tests)
+    const char* env = ups_env_raw_now("UPS_S2_KERNEL");             // (read per call) "0": off (A/B runs); "force": also small launches (tests)
     if (env && env[0] == '0') return 1;
     const bool force = env && env[0] == 'f';
     if (d->dtype != UPS_BF16 || d->ntaps != 9 || d->kh != 3 || d->kw != 3 || d->in_sy != 2 || d->in_sx != 2 || d->out_sy != 1 ||
@@ -227,13 +227,6 @@ int ups_conv3x3_s2_try(const ups_conv_desc* d, hipStream_t s) {
     if (blocks >= (1ll << 31)) return 1;
     const int KC = d->ci / 32;
     const size_t shm = (size_t)9 * KC * 64 * 64 + 4 * 2048;
-    static UpsPerDevice a1, a2;
-    if (KC == 1) {
-        if (!a1) { if (hipFuncSetAttribute((const void*)conv3x3_s2_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) return UPS_E_LAUNCH; a1 = true; }
-        hipLaunchKernelGGL((conv3x3_s2_kernel<1>), dim3((unsigned)blocks), dim3(256), shm, s, k);
-    } else {
-        if (!a2) { if (hipFuncSetAttribute((const void*)conv3x3_s2_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) return UPS_E_LAUNCH; a2 = true; }
-        hipLaunchKernelGGL((conv3x3_s2_kernel<2>), dim3((unsigned)blocks), dim3(256), shm, s, k);
-    }
-    return 0;
+    if (KC == 1) return ups_launch_lds<conv3x3_s2_kernel<1>>("conv3x3_s2_kernel", 160 * 1024, dim3((unsigned)blocks), dim3(256), shm, s, k);
+    return ups_launch_lds<conv3x3_s2_kernel<2>>("conv3x3_s2_kernel", 160 * 1024, dim3((unsigned)blocks), dim3(256), shm, s, k);
 }

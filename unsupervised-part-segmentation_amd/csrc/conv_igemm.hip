@@ -393,11 +393,10 @@ int launch(const ups_conv_desc& dd, hipStream_t s) {
     if (bn == 128 && mtiles * ups_cdiv(ctot, 128) < 256) bn = 64;
     if (bn == 64 && mtiles * ups_cdiv(ctot, 64) < 256) bn = 32;
     // UPS_IGEMM_FORCE="<bn>,<cps>": tuning override (one of 128,1 / 64,2 / 64,1 / 32,4 / 32,1), read once
-    static int fbn = -1, fcps = 0;
-    if (fbn < 0) {
-        const char* e = getenv("UPS_IGEMM_FORCE");
+    int fbn = 0, fcps = 0;
+    if (const char* e = UPS_ENV_RAW_CACHED("UPS_IGEMM_FORCE")) {
         int a = 0, b = 0;
-        if (e && sscanf(e, "%d,%d", &a, &b) == 2 && b > 0) fcps = b;
+        if (sscanf(e, "%d,%d", &a, &b) == 2 && b > 0) fcps = b;
         fbn = a > 0 ? a : 0;
     }
     if (fbn > 0) bn = fbn;
@@ -408,8 +407,7 @@ int launch(const ups_conv_desc& dd, hipStream_t s) {
     // split-K for latency-bound problems: few tiles, long K loop, workspace supplied.  Wider tiles + more blocks.
     d.ws = nullptr; d.splits = 1; d.stages_per_split = 0; d.ldw = 0;
     {
-        static int sk_on = -1;
-        if (sk_on < 0) { const char* e = getenv("UPS_NO_SPLITK"); sk_on = (e && e[0] == '1') ? 0 : 1; }
+        const bool sk_on = !UPS_ENV_OFF_CACHED("UPS_NO_SPLITK");
         const int chunks = d.ntaps * kchunks;
         const int bn_sk = ctot > 32 ? 64 : 32;
         const int blocks_sk = mtiles * ups_cdiv(ctot, bn_sk);
@@ -436,15 +434,9 @@ int launch(const ups_conv_desc& dd, hipStream_t s) {
 #define UPS_LAUNCH_IG(BNV, CPSV)                                                                                      \
     do {                                                                                                              \
         const size_t shmem = 2 * (size_t)(CPSV) * (BM + (BNV)) * RS + BM * 20;                                        \
-        static UpsPerDevice attr_done;                                                                                \
-        if (!attr_done) {                                                                                             \
-            if (hipFuncSetAttribute((const void*)conv_igemm_kernel<T, BNV, CPSV>,                                     \
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem) != hipSuccess)           \
-                return UPS_E_LAUNCH;                                                                                  \
-            attr_done = true;                                                                                         \
-        }                                                                                                             \
-        hipLaunchKernelGGL((conv_igemm_kernel<T, BNV, CPSV>), dim3(mtiles * ntn_l, d.splits), dim3(256), shmem, s, d,  \
-                           (int)M, ntn_l, kchunks);                                                                   \
+        const int rc_ = ups_launch_lds<conv_igemm_kernel<T, BNV, CPSV>>("conv_igemm_kernel", shmem, dim3(mtiles * ntn_l, d.splits),      \
+                                                                        dim3(256), shmem, s, d, (int)M, ntn_l, kchunks);                \
+        if (rc_ != UPS_OK) return rc_;                                                                                \
     } while (0)
     if (bn == 128) UPS_LAUNCH_IG(128, 1);
     else if (bn == 64 && cps_l == 2) UPS_LAUNCH_IG(64, 2);
@@ -501,20 +493,20 @@ extern "C" int ups_conv_igemm(const ups_conv_desc* d, void* stream) {
         UPS_CHECK_ARG(d->out_sy == 1 && d->out_sx == 1 && !d->out_oy && !d->out_ox && d->out_h == d->ho && d->out_w == d->wo);
     }
     // 3x3 / stride-1 problems on 16-aligned images go to the patch-tiled kernel (halo reuse across the 9 taps)
-    const char* force = getenv("UPS_FORCE_GENERIC_CONV");
-    if (!(force && force[0] == '1')) {
+    // (a negative result that is UPS_E_LAUNCH keeps its message: ups_launch_lds has said which kernel and how many bytes)
+    if (!ups_env_off_now("UPS_FORCE_GENERIC_CONV")) {
         // first layers (<= 8 input channels, 32 / 64 outputs): the im2col-in-the-fragment kernel, an output-write stream
         if (ups_conv3x3_first_try(d, (hipStream_t)stream) == 0) { UPS_LAUNCH_CHECK(); return UPS_OK; }
         // the large 3x3 / stride-2 `downsample` forwards (32 / 64 input channels): taps straight from global memory, no gather
         {
             const int rr = ups_conv3x3_rows_s2_try(d, (hipStream_t)stream);      // (the two encoder shapes as row streams)
             if (rr == 0) { UPS_LAUNCH_CHECK(); return UPS_OK; }
-            if (rr < 0) { ups_set_error("ups_conv_igemm: row-streaming stride-2 kernel launch setup failed"); return rr; }
+            if (rr < 0) { if (rr != UPS_E_LAUNCH) ups_set_error("ups_conv_igemm: row-streaming stride-2 kernel launch setup failed"); return rr; }
         }
         {
             const int sr = ups_conv3x3_s2_try(d, (hipStream_t)stream);
             if (sr == 0) { UPS_LAUNCH_CHECK(); return UPS_OK; }
-            if (sr < 0) { ups_set_error("ups_conv_igemm: stride-2 kernel launch setup failed"); return sr; }
+            if (sr < 0) { if (sr != UPS_E_LAUNCH) ups_set_error("ups_conv_igemm: stride-2 kernel launch setup failed"); return sr; }
         }
         // thin residual blocks on large batches of full-width rows: the row-streaming kernel; the K-deep logit convolution: its
         // strip form
@@ -523,11 +515,11 @@ extern "C" int ups_conv_igemm(const ups_conv_desc* d, void* stream) {
             if (rr == 1) rr = ups_conv3x3_rows_try(d, (hipStream_t)stream);
             if (rr == 1) rr = ups_conv3x3_rows_maskgrad_try(d, (hipStream_t)stream);
             if (rr == 0) { UPS_LAUNCH_CHECK(); return UPS_OK; }
-            if (rr < 0) { ups_set_error("ups_conv_igemm: row-streaming kernel launch setup failed"); return rr; }
+            if (rr < 0) { if (rr != UPS_E_LAUNCH) ups_set_error("ups_conv_igemm: row-streaming kernel launch setup failed"); return rr; }
         }
         const int pr = ups_conv3x3_patch_try(d, (hipStream_t)stream);
         if (pr == 0) { UPS_LAUNCH_CHECK(); if (d->sign_out && ups_conv3x3_patch_signs(d)) g_ups_sign_written = 1; return UPS_OK; }
-        if (pr < 0) { ups_set_error("ups_conv_igemm: patch kernel launch setup failed"); return pr; }
+        if (pr < 0) { if (pr != UPS_E_LAUNCH) ups_set_error("ups_conv_igemm: patch kernel launch setup failed"); return pr; }
     }
     if (d->d2s) {
         ups_set_error("ups_conv_igemm: the depth-to-space output needs the bf16 3x3 / stride-1 patch kernel (16-aligned lattice, 4 x 2^k channels)");

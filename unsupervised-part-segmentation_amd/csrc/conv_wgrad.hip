@@ -393,17 +393,18 @@ extern "C" int ups_conv_wgrad(const ups_wgrad_desc* d, void* stream) {
     }
     if (ups_wgrad3x3_f8_plan(d, &sk3, &slabs3) == 0) {
         UPS_CHECK_ARG(d->splitk == sk3 && d->dout_f8_scale && d->in_f8_scale && ((uintptr_t)d->dout_f8 & 15) == 0);
-        if (ups_wgrad3x3_f8_run(d, s) != UPS_OK) { ups_set_error("ups_conv_wgrad: fp8 kernel launch setup failed"); return UPS_E_LAUNCH; }
+        const int rc = ups_wgrad3x3_f8_run(d, s);        // (UPS_E_LAUNCH: ups_launch_lds has said why)
+        if (rc != UPS_OK) { if (rc != UPS_E_LAUNCH) ups_set_error("ups_conv_wgrad: fp8 kernel launch setup failed"); return UPS_E_LAUNCH; }
         nslabs = slabs3;
     } else if (ups_wgrad3x3_plan(d, &sk3, &slabs3) == 0) {
         UPS_CHECK_ARG(d->splitk == sk3);
-        if (ups_wgrad3x3_run(d, s) != UPS_OK) { ups_set_error("ups_conv_wgrad: patch kernel launch setup failed"); return UPS_E_LAUNCH; }
+        const int rc = ups_wgrad3x3_run(d, s);
+        if (rc != UPS_OK) { if (rc != UPS_E_LAUNCH) ups_set_error("ups_conv_wgrad: patch kernel launch setup failed"); return UPS_E_LAUNCH; }
         nslabs = slabs3;
     } else {
         // a single split writes exactly the elements the reduction would (rows < ci_log of every tap, the bias): straight into the
         // gradient, no slab and no second launch (the critics' 30 dense layers; UPS_WGRAD_DIRECT=0: off)
-        static int direct = -1;
-        if (direct < 0) { const char* e = getenv("UPS_WGRAD_DIRECT"); direct = (e && e[0] == '0') ? 0 : 1; }
+        const bool direct = UPS_ENV_ON_CACHED("UPS_WGRAD_DIRECT");
         const bool one = direct && d->splitk == 1;
         if (one) { k.ws = d->grad; k.bias_direct = d->grad_bias; }
         if (d->dtype == UPS_F32) launch_m<float>(k, (int)M, d->splitk, s);

@@ -450,8 +450,7 @@ bool eligible(const ups_wgrad_desc* d) {
         seen[(dy + 1) * 3 + dx + 1] = true;
     }
     for (int t = 0; t < 9; ++t) if (!seen[t]) return false;
-    const char* force = getenv("UPS_FORCE_GENERIC_CONV");
-    return !(force && force[0] == '1');
+    return !ups_env_off_now("UPS_FORCE_GENERIC_CONV");
 }
 
 template <int CB, int BN, int TH, bool SLIDE = false>
@@ -461,14 +460,8 @@ int launch3(const Wg3K& k, int cit, int cot, int splitk, hipStream_t s) {
     size_t shmem = 2 * (size_t)(PPIX * RSX + TH * TW * RSD);
     constexpr size_t red = (size_t)(8 / ((CB / 32) * (BN / 32)) - 1) * (CB / 32) * (BN / 32) * 4096;   // K-part reduction scratch
     if (shmem < red) shmem = red;
-    static UpsPerDevice attr_set;
-    if (!attr_set) {
-        if (hipFuncSetAttribute((const void*)conv_wgrad3x3_kernel<CB, BN, TH, SLIDE>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)shmem) != hipSuccess) return UPS_E_LAUNCH;
-        attr_set = true;
-    }
-    hipLaunchKernelGGL((conv_wgrad3x3_kernel<CB, BN, TH, SLIDE>), dim3(cit * cot * splitk), dim3(512), shmem, s, k, cit, cot, splitk);
-    return UPS_OK;
+    return ups_launch_lds<conv_wgrad3x3_kernel<CB, BN, TH, SLIDE>>("conv_wgrad3x3_kernel", shmem, dim3(cit * cot * splitk), dim3(512), shmem, s,
+                                                                   k, cit, cot, splitk);
 }
 
 }  // namespace
@@ -502,7 +495,7 @@ int ups_wgrad3x3_run(const ups_wgrad_desc* d, hipStream_t s) {
     k.in_f16 = d->in_f16;
     k.taps_std = 1;
     for (int t = 0; t < 9; ++t) if (d->tap_dy[t] != t / 3 - 1 || d->tap_dx[t] != t % 3 - 1) k.taps_std = 0;
-    { const char* e = getenv("UPS_WGRAD_SLIDE"); if (e && e[0] == '0') k.taps_std = 0; }      // A/B switch
+    if (!ups_env_on_now("UPS_WGRAD_SLIDE")) k.taps_std = 0;      // A/B switch
     k.tap_off = 0; k.tap_wi = 0;
     for (int t = 0; t < 9; ++t) {
         k.tap_off |= (unsigned long long)(((d->tap_dy[t] + 1) << 2) | (d->tap_dx[t] + 1)) << (4 * t);

@@ -343,18 +343,10 @@ int ups_wgrad3x3_f8_run(const ups_wgrad_desc* d, hipStream_t s) {
     const int cit = d->ci / CB, cot = d->co / BN;
     constexpr size_t shmem = 2 * (size_t)XB + 3 * (size_t)DB;
 #define UPS_W8_LAUNCH(F16V, ACTV)                                                                                                   \
-    do {                                                                                                                              \
-        static UpsPerDevice attr_set;                                                                                                 \
-        if (!attr_set) {                                                                                                              \
-            if (hipFuncSetAttribute((const void*)conv_wgrad3x3_f8_kernel<F16V, ACTV>, hipFuncAttributeMaxDynamicSharedMemorySize,      \
-                                    (int)shmem) != hipSuccess) return UPS_E_LAUNCH;                                                   \
-            attr_set = true;                                                                                                          \
-        }                                                                                                                             \
-        hipLaunchKernelGGL((conv_wgrad3x3_f8_kernel<F16V, ACTV>), dim3(cit * cot * d->splitk), dim3(512), shmem, s, k, cit, cot, d->splitk); \
-    } while (0)
+    ups_launch_lds<conv_wgrad3x3_f8_kernel<F16V, ACTV>>("conv_wgrad3x3_f8_kernel", shmem, dim3(cit * cot * d->splitk), dim3(512), shmem, s, k, \
+                                                        cit, cot, d->splitk)
     const bool act = d->act_in != UPS_ACT_NONE;
-    if (d->in_f16) { if (act) UPS_W8_LAUNCH(true, true); else UPS_W8_LAUNCH(true, false); }
-    else { if (act) UPS_W8_LAUNCH(false, true); else UPS_W8_LAUNCH(false, false); }
+    if (d->in_f16) return act ? UPS_W8_LAUNCH(true, true) : UPS_W8_LAUNCH(true, false);
+    return act ? UPS_W8_LAUNCH(false, true) : UPS_W8_LAUNCH(false, false);
 #undef UPS_W8_LAUNCH
-    return UPS_OK;
 }

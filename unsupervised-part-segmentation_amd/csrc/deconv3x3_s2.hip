@@ -398,16 +398,10 @@ extern "C" int ups_deconv3x3_s2_fwd(const void* x, int32_t dtype, int32_t n, int
         ups_set_error("ups_deconv3x3_s2_fwd: tile does not fit in LDS");
         return UPS_E_UNSUPPORTED;
     }
-    static UpsPerDevice raised_b, raised_h;
-    UpsPerDevice& raised = dtype == UPS_BF16 ? raised_b : raised_h;
-    if (!raised) {
-        if (dtype == UPS_BF16) (void)hipFuncSetAttribute((const void*)deconv_fwd_kernel<bf16>, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024);
-        else (void)hipFuncSetAttribute((const void*)deconv_fwd_kernel<f16>, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024);
-        raised = true;
-    }
     const dim3 grid(w / (16 * k.sub), h, n);
-    if (dtype == UPS_BF16) hipLaunchKernelGGL(deconv_fwd_kernel<bf16>, grid, dim3(256), bytes, (hipStream_t)stream, k);
-    else hipLaunchKernelGGL(deconv_fwd_kernel<f16>, grid, dim3(256), bytes, (hipStream_t)stream, k);
+    const int rc = dtype == UPS_BF16 ? ups_launch_lds<deconv_fwd_kernel<bf16>>("deconv_fwd_kernel", 64 * 1024, grid, dim3(256), bytes, (hipStream_t)stream, k)
+                                     : ups_launch_lds<deconv_fwd_kernel<f16>>("deconv_fwd_kernel", 64 * 1024, grid, dim3(256), bytes, (hipStream_t)stream, k);
+    if (rc != UPS_OK) return rc;
     UPS_LAUNCH_CHECK();
     return UPS_OK;
 }

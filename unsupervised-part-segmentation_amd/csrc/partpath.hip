@@ -1052,15 +1052,8 @@ __global__ void unpool_feat_reduce_kernel(const float* __restrict__ partial, int
 
 constexpr int UNPOOL_SLABS = 32;
 
-// kernels whose LDS images can exceed the 64 KB default at P = 64: raise the limit once per kernel
-template <typename K>
-bool allow_big_lds(K kernel, UpsPerDevice& done) {
-    if (!done) {
-        if (hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) return false;
-        done = true;
-    }
-    return true;
-}
+// the limit the kernels ask for whose LDS images can exceed the 64 KB default at P = 64
+constexpr size_t BIG_LDS = 160 * 1024;
 
 }  // namespace
 
@@ -1069,8 +1062,7 @@ bool allow_big_lds(K kernel, UpsPerDevice& done) {
 // Returns blocks per image (> 0) when launched, 0 when the caller has to take the generic kernel.
 static int part_softmax_px_launch(const float* mean, const float* eps, float* l, float* m, float* hard, int64_t* argmax,
                                   uint32_t* hard_bits, long long pixels, int P, int img_w, long long img_hw, int* mom, hipStream_t s) {
-    const char* e = getenv("UPS_SOFTMAX_PX");
-    if ((e && e[0] == '0') || P != 10 || pixels % 256 != 0) return 0;
+    if (!ups_env_on_now("UPS_SOFTMAX_PX") || P != 10 || pixels % 256 != 0) return 0;
     if (((((uintptr_t)mean) | ((uintptr_t)eps) | ((uintptr_t)l) | ((uintptr_t)m) | ((uintptr_t)hard)) & 15) != 0) return 0;
     if (eps && !l) return 0;
     if (!mom) { img_w = 128; img_hw = pixels % 16384 == 0 ? 16384 : 256; }
@@ -1083,13 +1075,9 @@ static int part_softmax_px_launch(const float* mean, const float* eps, float* l,
     while ((n * bpi < 512 || tiles_img / bpi > 32) && tiles_img % (2 * bpi) == 0 && 2 * bpi * 512 <= img_hw) bpi *= 2;
     if (tiles_img / bpi > 32 || (mom && img_hw / img_w > 256)) return 0;      // (int32 sums of iy^2: rows < 256, <= 8192 pixels per block)
     constexpr size_t shm = (2 * 2 + 3) * (size_t)(256 * 10 * 4) + 10 * 5 * sizeof(int);
-    static UpsPerDevice at;
-    if (!at) {
-        if (hipFuncSetAttribute((const void*)part_softmax_px_kernel<10>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm) != hipSuccess) return 0;
-        at = true;
-    }
-    hipLaunchKernelGGL((part_softmax_px_kernel<10>), dim3((unsigned)(n * bpi)), dim3(256), shm, s, mean, eps, l, m, hard,
-                       (long long*)argmax, (unsigned*)hard_bits, tiles_img, tiles_img / bpi, mom, img_w);
+    if (ups_launch_lds<part_softmax_px_kernel<10>>("part_softmax_px_kernel", shm, dim3((unsigned)(n * bpi)), dim3(256), shm, s, mean, eps, l, m, hard,
+                                                   (long long*)argmax, (unsigned*)hard_bits, tiles_img, tiles_img / bpi, mom, img_w) != UPS_OK)
+        return 0;       // (as before: the generic kernel takes the launch; the message ups_launch_lds left is informational here)
     return bpi;
 }
 
@@ -1155,31 +1143,21 @@ static int spatial_moments_launch(const float* x, int32_t n, int32_t h, int32_t 
     // the stats buffer doubles as the workspace: n*P*8 floats of result, then n*MOMENT_SLABS*P*8 floats of per-slab partials and
     // n*MOMENT_SLABS floats of KL partials (ups_spatial_moments_floats)
     {   // pixel-per-lane form (round 5): P = 10, 128- / 256-wide maps in whole 512-pixel tiles
-        const char* e = getenv("UPS_MOMENTS_PX");
         const long long hwp = (long long)h * w;
-        if (!(e && e[0] == '0') && P == 10 && (w == 128 || w == 256) && hwp % 512 == 0 && (((uintptr_t)x) & 15) == 0) {
+        if (ups_env_on_now("UPS_MOMENTS_PX") && P == 10 && (w == 128 || w == 256) && hwp % 512 == 0 && (((uintptr_t)x) & 15) == 0) {
             const int tiles_img = (int)(hwp / 512);
             int bpi = 1;          // two blocks per CU over the batch; at most MOMENT_SLABS records per image
-            const char* eb = getenv("UPS_MOMENTS_PX_BLOCKS");
-            const long long want_blocks = eb ? atoll(eb) : 512;
+            const long long want_blocks = ups_env_int_now("UPS_MOMENTS_PX_BLOCKS", 512);
             while (2 * bpi <= MOMENT_SLABS && (long long)n * bpi < want_blocks && tiles_img % (2 * bpi) == 0) bpi *= 2;
             float* partial_px = stats + (long long)n * P * 8;
             float* klp_px = kl_sum ? partial_px + (long long)n * MOMENT_SLABS * P * 8 : nullptr;
             constexpr size_t shm_max = 3 * (size_t)(512 * 10 * 4) + (4 * 10 * 7 + 4) * sizeof(float);
             const size_t shm_px = (size_t)(tiles_img / bpi < 3 ? tiles_img / bpi : 3) * (512 * 10 * 4) + (4 * 10 * 7 + 4) * sizeof(float);
-            static UpsPerDevice a7;
-            if (!a7) {
-                if (hipFuncSetAttribute((const void*)moments_px_kernel<10, 7>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm_max) != hipSuccess ||
-                    hipFuncSetAttribute((const void*)moments_px_kernel<10, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm_max) != hipSuccess)
-                    return UPS_E_LAUNCH;
-                a7 = true;
-            }
-            if (w == 128)
-                hipLaunchKernelGGL((moments_px_kernel<10, 7>), dim3(n * bpi), dim3(256), shm_px, s, x, h, gamma, rect_c, half_h, half_w,
-                                   tiles_img / bpi, partial_px, klp_px);
-            else
-                hipLaunchKernelGGL((moments_px_kernel<10, 8>), dim3(n * bpi), dim3(256), shm_px, s, x, h, gamma, rect_c, half_h, half_w,
-                                   tiles_img / bpi, partial_px, klp_px);
+            const int rc = ups_pick<7, 8>(w == 128 ? 7 : 8, [&](auto LW) {
+                return ups_launch_lds<moments_px_kernel<10, LW()>>("moments_px_kernel", shm_max, dim3(n * bpi), dim3(256), shm_px, s, x, h, gamma,
+                                                                   rect_c, half_h, half_w, tiles_img / bpi, partial_px, klp_px);
+            });
+            if (rc != UPS_OK) return rc;
             UPS_LAUNCH_CHECK();
             hipLaunchKernelGGL(moments_combine_kernel, dim3(ups_cdiv(n * P, 4) + 1), dim3(256), 0, s, partial_px, n, bpi, P, stats, klp_px, kl_sum);
             UPS_LAUNCH_CHECK();
@@ -1238,10 +1216,9 @@ extern "C" int ups_mask_parts_fwd(const float* view, const float* hard, void* ou
     UPS_CHECK_ARG(view && hard && out && P >= 1 && P <= 64);
     const int grid = ups_cdiv((long long)B * hw, 256);
     const size_t shm = (size_t)256 * (P | 1) * sizeof(float);
-    static UpsPerDevice a0, a1;
-    if (!allow_big_lds(mask_parts_fwd_kernel<float>, a0) || !allow_big_lds(mask_parts_fwd_kernel<bf16>, a1)) return UPS_E_LAUNCH;
-    if (dtype == UPS_F32) hipLaunchKernelGGL(mask_parts_fwd_kernel<float>, dim3(grid), dim3(256), shm, (hipStream_t)stream, view, hard, (float*)out, B, (long long)hw, P);
-    else hipLaunchKernelGGL(mask_parts_fwd_kernel<bf16>, dim3(grid), dim3(256), shm, (hipStream_t)stream, view, hard, (bf16*)out, B, (long long)hw, P);
+    const int rc = dtype == UPS_F32 ? ups_launch_lds<mask_parts_fwd_kernel<float>>("mask_parts_fwd_kernel", BIG_LDS, dim3(grid), dim3(256), shm, (hipStream_t)stream, view, hard, (float*)out, B, (long long)hw, P)
+                                    : ups_launch_lds<mask_parts_fwd_kernel<bf16>>("mask_parts_fwd_kernel", BIG_LDS, dim3(grid), dim3(256), shm, (hipStream_t)stream, view, hard, (bf16*)out, B, (long long)hw, P);
+    if (rc != UPS_OK) return rc;
     UPS_LAUNCH_CHECK();
     return UPS_OK;
 }
@@ -1251,10 +1228,9 @@ extern "C" int ups_mask_parts_bwd(const float* view, const void* g_out, float* g
     UPS_CHECK_ARG(P >= 1 && P <= 64);
     const int grid = ups_cdiv((long long)B * hw, 256);
     const size_t shm = (size_t)256 * (P | 1) * sizeof(float);
-    static UpsPerDevice a0, a1;
-    if (!allow_big_lds(mask_parts_bwd_kernel<float>, a0) || !allow_big_lds(mask_parts_bwd_kernel<bf16>, a1)) return UPS_E_LAUNCH;
-    if (dtype == UPS_F32) hipLaunchKernelGGL(mask_parts_bwd_kernel<float>, dim3(grid), dim3(256), shm, (hipStream_t)stream, view, (const float*)g_out, g_hard, B, (long long)hw, P);
-    else hipLaunchKernelGGL(mask_parts_bwd_kernel<bf16>, dim3(grid), dim3(256), shm, (hipStream_t)stream, view, (const bf16*)g_out, g_hard, B, (long long)hw, P);
+    const int rc = dtype == UPS_F32 ? ups_launch_lds<mask_parts_bwd_kernel<float>>("mask_parts_bwd_kernel", BIG_LDS, dim3(grid), dim3(256), shm, (hipStream_t)stream, view, (const float*)g_out, g_hard, B, (long long)hw, P)
+                                    : ups_launch_lds<mask_parts_bwd_kernel<bf16>>("mask_parts_bwd_kernel", BIG_LDS, dim3(grid), dim3(256), shm, (hipStream_t)stream, view, (const bf16*)g_out, g_hard, B, (long long)hw, P);
+    if (rc != UPS_OK) return rc;
     UPS_LAUNCH_CHECK();
     return UPS_OK;
 }
@@ -1264,10 +1240,9 @@ extern "C" int ups_unpool_fwd(const float* hard, const float* feat, void* out, i
     UPS_CHECK_ARG(hard && feat && out && F % 8 == 0 && ldo % 8 == 0 && ldo >= F + P && P >= 1 && P <= 64);
     const dim3 grid(ups_cdiv(hw, 256), B);
     const size_t shm = ((size_t)256 * (P | 1) + (size_t)P * F + 256) * sizeof(float);
-    static UpsPerDevice a0, a1;
-    if (!allow_big_lds(unpool_fwd_kernel<float>, a0) || !allow_big_lds(unpool_fwd_kernel<bf16>, a1)) return UPS_E_LAUNCH;
-    if (dtype == UPS_F32) hipLaunchKernelGGL(unpool_fwd_kernel<float>, grid, dim3(256), shm, (hipStream_t)stream, hard, feat, (float*)out, (long long)hw, P, F, ldo);
-    else hipLaunchKernelGGL(unpool_fwd_kernel<bf16>, grid, dim3(256), shm, (hipStream_t)stream, hard, feat, (bf16*)out, (long long)hw, P, F, ldo);
+    const int rc = dtype == UPS_F32 ? ups_launch_lds<unpool_fwd_kernel<float>>("unpool_fwd_kernel", BIG_LDS, grid, dim3(256), shm, (hipStream_t)stream, hard, feat, (float*)out, (long long)hw, P, F, ldo)
+                                    : ups_launch_lds<unpool_fwd_kernel<bf16>>("unpool_fwd_kernel", BIG_LDS, grid, dim3(256), shm, (hipStream_t)stream, hard, feat, (bf16*)out, (long long)hw, P, F, ldo);
+    if (rc != UPS_OK) return rc;
     UPS_LAUNCH_CHECK();
     return UPS_OK;
 }
@@ -1281,13 +1256,15 @@ extern "C" int ups_unpool_mix_fwd(const float* hard, const float* feat, const in
     UPS_CHECK_ARG(((((uintptr_t)feat) | ((uintptr_t)out)) & 15) == 0);     // feature rows are read, items stored, as 16-byte pieces
     const dim3 grid(K, ups_cdiv(hw, 256));
     const size_t shm = ((size_t)256 * (P | 1) + (size_t)P * F + 256) * sizeof(float);
-    static UpsPerDevice a0, a1;
-    if (!allow_big_lds(unpool_mix_fwd_kernel<float>, a0) || !allow_big_lds(unpool_mix_fwd_kernel<bf16>, a1)) return UPS_E_LAUNCH;
-    if (dtype == UPS_F32) hipLaunchKernelGGL(unpool_mix_fwd_kernel<float>, grid, dim3(256), shm, (hipStream_t)stream, hard, feat, pose_idx, app_idx, (float*)out, (long long)hw, P, F, ldo);
-    else hipLaunchKernelGGL(unpool_mix_fwd_kernel<bf16>, grid, dim3(256), shm, (hipStream_t)stream, hard, feat, pose_idx, app_idx, (bf16*)out, (long long)hw, P, F, ldo);
+    const int rc = dtype == UPS_F32 ? ups_launch_lds<unpool_mix_fwd_kernel<float>>("unpool_mix_fwd_kernel", BIG_LDS, grid, dim3(256), shm, (hipStream_t)stream, hard, feat, pose_idx, app_idx, (float*)out, (long long)hw, P, F, ldo)
+                                    : ups_launch_lds<unpool_mix_fwd_kernel<bf16>>("unpool_mix_fwd_kernel", BIG_LDS, grid, dim3(256), shm, (hipStream_t)stream, hard, feat, pose_idx, app_idx, (bf16*)out, (long long)hw, P, F, ldo);
+    if (rc != UPS_OK) return rc;
     UPS_LAUNCH_CHECK();
     return UPS_OK;
 }
+
+// the (P, row pitch) pairs unpool_bwd_mfma_kernel is instantiated for: round8(64 + P) channels; 0: no instance
+constexpr int unpool_mfma_ld(int P) { return (P == 10 || P == 16) ? 80 : (P == 20 ? 88 : (P == 25 ? 96 : 0)); }
 
 // g_feat: caller provides B*P*F floats followed by B*UNPOOL_SLABS*P*F floats of workspace.
 extern "C" int ups_unpool_bwd(const float* hard, const float* feat, const void* g, float* g_hard, float* g_feat, int32_t dtype,
@@ -1298,30 +1275,22 @@ extern "C" int ups_unpool_bwd(const float* hard, const float* feat, const void* 
     const size_t esz = dtype == UPS_F32 ? 4 : 2;
     {   // matrix-core form (round 5; round 6: P = 16 / 20 / 25 too): bf16 gradient, 64 features + P parts in round8(64 + P)-channel rows,
         // whole 128-pixel tiles
-        const char* e = getenv("UPS_UNPOOL_MFMA");          // (read at every call: the unit test compares both forms)
-        const bool mf_on = !(e && e[0] == '0');
+        const bool mf_on = ups_env_on_now("UPS_UNPOOL_MFMA");          // (read at every call: the unit test compares both forms)
         const bool al16 = ((((uintptr_t)hard) | ((uintptr_t)g) | ((uintptr_t)g_hard)) & 15) == 0;
-        const bool shape = (P == 10 && ldo == 80) || (P == 16 && ldo == 80) || (P == 20 && ldo == 88) || (P == 25 && ldo == 96);
+        const bool shape = unpool_mfma_ld(P) != 0 && ldo == unpool_mfma_ld(P);
         if (mf_on && dtype == UPS_BF16 && shape && F == UB_F && hw % UB_TP == 0 && al16) {
             const int tiles_img = (int)(hw / UB_TP);
             // blocks per image: two per CU over the batch, a power of two dividing the tiles and the slab records
             int bpi = 1;
             while (2 * bpi <= UNPOOL_SLABS && (long long)B * bpi < 512 && tiles_img % (2 * bpi) == 0) bpi *= 2;
             // (one record per block, `bpi` records per image: the reduction walks 8 records instead of UNPOOL_SLABS = 32)
-#define UPS_UB_LAUNCH(PV, LDV) do { \
-                static UpsPerDevice am; \
-                if (!am) { \
-                    if (hipFuncSetAttribute((const void*)unpool_bwd_mfma_kernel<PV, LDV>, hipFuncAttributeMaxDynamicSharedMemorySize, \
-                                            (int)UB<PV, LDV>::SHMEM) != hipSuccess) return UPS_E_LAUNCH; \
-                    am = true; \
-                } \
-                hipLaunchKernelGGL((unpool_bwd_mfma_kernel<PV, LDV>), dim3(B, bpi), dim3(256), (UB<PV, LDV>::SHMEM), s, hard, feat, (const bf16*)g, \
-                                   g_hard, partial, (long long)hw, tiles_img / bpi, 1, bpi); } while (0)
-            if (P == 10) UPS_UB_LAUNCH(10, 80);
-            else if (P == 16) UPS_UB_LAUNCH(16, 80);
-            else if (P == 20) UPS_UB_LAUNCH(20, 88);
-            else UPS_UB_LAUNCH(25, 96);
-#undef UPS_UB_LAUNCH
+            const int rc = ups_pick<10, 16, 20, 25>(P, [&](auto PC) {
+                constexpr int PV = PC(), LDV = unpool_mfma_ld(PV);      // (`shape` above: ldo is this P's)
+                return ups_launch_lds<unpool_bwd_mfma_kernel<PV, LDV>>("unpool_bwd_mfma_kernel", UB<PV, LDV>::SHMEM, dim3(B, bpi), dim3(256),
+                                                                       UB<PV, LDV>::SHMEM, s, hard, feat, (const bf16*)g, g_hard, partial,
+                                                                       (long long)hw, tiles_img / bpi, 1, bpi);
+            });
+            if (rc != UPS_OK) return rc;
             UPS_LAUNCH_CHECK();
             const int total = B * P * F;
             hipLaunchKernelGGL(unpool_feat_reduce_kernel, dim3(ups_cdiv(total, 256)), dim3(256), 0, s, partial, B, bpi, P * F, g_feat);
@@ -1340,14 +1309,11 @@ extern "C" int ups_unpool_bwd(const float* hard, const float* feat, const void* 
     const size_t shmem = lds_bytes(tpx);
     UPS_CHECK_ARG(shmem <= 160 * 1024);
     const dim3 grid(B, UNPOOL_SLABS);
-    static UpsPerDevice ah0, ah1;
-    if (!allow_big_lds(unpool_bwd_kernel<float>, ah0) || !allow_big_lds(unpool_bwd_kernel<bf16>, ah1)) return UPS_E_LAUNCH;
-    if (dtype == UPS_F32)
-        hipLaunchKernelGGL(unpool_bwd_kernel<float>, grid, dim3(256), shmem, s, hard, feat, (const float*)g, g_hard, partial, (long long)hw,
-                           P, F, ldo, slab_px, tpx);
-    else
-        hipLaunchKernelGGL(unpool_bwd_kernel<bf16>, grid, dim3(256), shmem, s, hard, feat, (const bf16*)g, g_hard, partial, (long long)hw,
-                           P, F, ldo, slab_px, tpx);
+    const int rc = dtype == UPS_F32 ? ups_launch_lds<unpool_bwd_kernel<float>>("unpool_bwd_kernel", BIG_LDS, grid, dim3(256), shmem, s, hard, feat, (const float*)g,
+                                                                               g_hard, partial, (long long)hw, P, F, ldo, slab_px, tpx)
+                                    : ups_launch_lds<unpool_bwd_kernel<bf16>>("unpool_bwd_kernel", BIG_LDS, grid, dim3(256), shmem, s, hard, feat, (const bf16*)g,
+                                                                              g_hard, partial, (long long)hw, P, F, ldo, slab_px, tpx);
+    if (rc != UPS_OK) return rc;
     UPS_LAUNCH_CHECK();
     hipLaunchKernelGGL(unpool_feat_reduce_kernel, dim3(ups_cdiv(B * P * F, 256)), dim3(256), 0, s, partial, B, UNPOOL_SLABS, P * F, g_feat);
     UPS_LAUNCH_CHECK();

@@ -18,6 +18,7 @@
 // per_np (view 0) [n][P][8]: 0 S = sum m, 1 R = sum r, 2 Rsmooth, 3 Rcontour
 // per_np (view 1) = stats of ups_spatial_moments: 0 max, 1 Z, 2 S0, 3 Sy, 4 Sx, 5 Q
 #include <stdlib.h>
+#include <initializer_list>
 
 #include "common.h"
 #include "tile.h"
@@ -1439,8 +1440,8 @@ __global__ __launch_bounds__(256) void prior_bwd0_cpl_kernel(const PriorK p, con
 }
 
 // Test hook: UPS_PRIOR_PX_BPI caps the blocks per image of the pixel-per-lane kernels, so that a three-image test walks the multi-tile
-// loops (ring slots, counted waits) the 64-image benchmark shape walks.  Read at every call (a getenv, microseconds).
-int px_bpi_cap() { const char* e = getenv("UPS_PRIOR_PX_BPI"); const int v = e ? atoi(e) : 0; return v > 0 ? v : (1 << 30); }
+// loops (ring slots, counted waits) the 64-image benchmark shape walks.  Read at every call (microseconds).
+int px_bpi_cap() { const int v = (int)ups_env_int_now("UPS_PRIOR_PX_BPI", 0); return v > 0 ? v : (1 << 30); }
 int gp_of(int P) { int g = 2; while (g < P) g *= 2; return g; }
 
 PriorK to_k(const ups_prior_desc* d, float* ws) {
@@ -1456,36 +1457,42 @@ PriorK to_k(const ups_prior_desc* d, float* ws) {
 
 }  // namespace
 
-// Launch KERNEL<PC, LW> for the descriptor's (P, w): specialised instances for the part counts of the shipped / benchmark configs and
-// 128- / 256-wide images, the generic <0, -1> instance otherwise.  (Every instance may need more than the 64 KB default of LDS.)
-template <typename K, typename... A>
-static int prior_launch_one(K kernel, UpsPerDevice& attr, dim3 grid, size_t shm, hipStream_t s, A... args) {
-    if (!attr) {
-        if (hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) return UPS_E_LAUNCH;
-        attr = true;
-    }
-    hipLaunchKernelGGL(kernel, grid, dim3(256), shm, s, args...);
-    return UPS_OK;
+// (P, w, variant) -> template arguments, here and nowhere else: every launcher below names its kernel in a lambda over the
+// std::integral_constants these two hand it.  Every instance with dynamic LDS may need more than the 64 KB default.
+constexpr size_t PRIOR_LDS = 160 * 1024;
+
+// The staged kernels KERNEL<PC, LW>: specialised instances for the part counts of the shipped / benchmark configs and 128- / 256-wide
+// images, the generic <0, -1> instance otherwise.
+template <typename F>
+static int prior_dispatch_staged(const ups_prior_desc* d, F&& f) {
+    const int lw = d->w == 128 ? 7 : (d->w == 256 ? 8 : -1);
+    if (lw < 0 || !(d->P == 10 || d->P == 16 || d->P == 20 || d->P == 25)) return f(std::integral_constant<int, 0>{}, std::integral_constant<int, -1>{});
+    return ups_pick<10, 16, 20, 25>(d->P, [&](auto PC) { return ups_pick<7, 8>(lw, [&](auto LW) { return f(PC, LW); }); });
 }
-#define UPS_PRIOR_CASE(KERNEL, PCV, LWV, ...)                                                            \
-    do { static UpsPerDevice at_; const int rc_ = prior_launch_one(KERNEL<PCV, LWV>, at_, __VA_ARGS__); if (rc_ != UPS_OK) return rc_; } while (0)
-#define UPS_PRIOR_DISPATCH(KERNEL, grid, shm, ...)                                                       \
-    do {                                                                                                 \
-        const int lw_ = d->w == 128 ? 7 : (d->w == 256 ? 8 : -1);                                        \
-        const int pc_ = (d->P == 10 || d->P == 16 || d->P == 20 || d->P == 25) ? d->P : 0;              \
-        if (lw_ < 0 || pc_ == 0) UPS_PRIOR_CASE(KERNEL, 0, -1, grid, shm, s, __VA_ARGS__);               \
-        else if (lw_ == 7) {                                                                             \
-            if (pc_ == 10) UPS_PRIOR_CASE(KERNEL, 10, 7, grid, shm, s, __VA_ARGS__);                     \
-            else if (pc_ == 16) UPS_PRIOR_CASE(KERNEL, 16, 7, grid, shm, s, __VA_ARGS__);                \
-            else if (pc_ == 20) UPS_PRIOR_CASE(KERNEL, 20, 7, grid, shm, s, __VA_ARGS__);                \
-            else UPS_PRIOR_CASE(KERNEL, 25, 7, grid, shm, s, __VA_ARGS__);                               \
-        } else {                                                                                         \
-            if (pc_ == 10) UPS_PRIOR_CASE(KERNEL, 10, 8, grid, shm, s, __VA_ARGS__);                     \
-            else if (pc_ == 16) UPS_PRIOR_CASE(KERNEL, 16, 8, grid, shm, s, __VA_ARGS__);                \
-            else if (pc_ == 20) UPS_PRIOR_CASE(KERNEL, 20, 8, grid, shm, s, __VA_ARGS__);                \
-            else UPS_PRIOR_CASE(KERNEL, 25, 8, grid, shm, s, __VA_ARGS__);                               \
-        }                                                                                                \
-    } while (0)
+// The pixel-per-lane (PS = 10) and chunk-per-lane (PS = 16, 20, 25) kernels KERNEL<P, LW, VAR> of a descriptor their `eligible` took.
+template <int... PS, typename F>
+static int prior_dispatch(const ups_prior_desc* d, F&& f) {
+    return ups_pick<PS...>(d->P, [&](auto PC) {
+        return ups_pick<7, 8>(d->w == 128 ? 7 : 8, [&](auto LW) {
+            return ups_pick<0, 1>(d->variant == 0 ? 0 : 1, [&](auto VAR) { return f(PC, LW, VAR); });
+        });
+    });
+}
+// What both of those forms ask of a descriptor: the view, 128- / 256-wide images in whole 256-pixel tiles, and every map the kernel
+// touches present and 16-byte aligned.
+static bool prior_tiles_ok(const ups_prior_desc* d, int view, std::initializer_list<const void*> maps) {
+    uintptr_t all = 0;
+    for (const void* m : maps) { if (!m) return false; all |= (uintptr_t)m; }
+    return d->view == view && (d->w == 128 || d->w == 256) && ((long long)d->h * d->w) % 256 == 0 && (all & 15) == 0;
+}
+// pixel-per-lane form (round 5): P = 10 (UPS_PRIOR_PX=0: off)
+static bool px_eligible(const ups_prior_desc* d, int view, std::initializer_list<const void*> maps) {
+    return UPS_ENV_ON_CACHED("UPS_PRIOR_PX") && d->P == 10 && prior_tiles_ok(d, view, maps);
+}
+// chunk-per-lane, direct-from-global form (round 6): the part counts the rings cannot hold (UPS_PRIOR_DIRECT=0: off)
+static bool cpl_eligible(const ups_prior_desc* d, int view, std::initializer_list<const void*> maps) {
+    return UPS_ENV_ON_CACHED("UPS_PRIOR_DIRECT") && (d->P == 16 || d->P == 20 || d->P == 25) && prior_tiles_ok(d, view, maps);
+}
 
 extern "C" size_t ups_prior_sums_floats(int32_t n, int32_t P) { return 16 + (size_t)n * NSLAB * 4 + (size_t)n * NSLAB * P * 4 + (size_t)n * 8; }
 
@@ -1495,70 +1502,43 @@ extern "C" int ups_prior_fwd(const ups_prior_desc* d, void* stream) {
     UPS_CHECK_ARG(d->view == 1 || (d->l && d->l_mean && d->hard && (d->px || d->variant == 1) && d->per_np));
     hipStream_t s = (hipStream_t)stream;
     PriorK k = to_k(d, d->sums + 16);
-    {   // pixel-per-lane form (round 5): view 0, P = 10, 128- / 256-wide images whose tiles deal evenly onto the slab records
-        static int px_on = -1;
-        if (px_on < 0) { const char* e = getenv("UPS_PRIOR_PX"); px_on = (e && e[0] == '0') ? 0 : 1; }
-        const long long hw = (long long)d->h * d->w;
-        const bool aligned = ((((uintptr_t)d->m) | ((uintptr_t)d->l_mean) | ((uintptr_t)d->l) | ((uintptr_t)d->hard)) & 15) == 0;
-        if (px_on && d->view == 0 && d->P == 10 && (d->w == 128 || d->w == 256) && hw % 256 == 0 && aligned) {
-            const int tiles_img = (int)(hw / 256);
-            // blocks per image: enough blocks for one per CU, a power of two that divides both the tiles and the NSLAB slab records
-            int bpi = 1;
-            const int cap = px_bpi_cap();
-            while (2 * bpi <= cap && bpi < NSLAB && bpi < tiles_img && (long long)d->n * bpi < 256 && tiles_img % (2 * bpi) == 0) bpi *= 2;
-            if (tiles_img % bpi == 0 && NSLAB % bpi == 0) {
-                constexpr size_t shm_px = 7 * 2 * (size_t)(256 * 10 * 4) + 4 * (4 + 4 * 10) * sizeof(float);
-                const dim3 grid(d->n * bpi);
-                const int tpb = tiles_img / bpi, spb = NSLAB / bpi;
-#define UPS_PRIOR_PX(LWV, VARV)                                                                                                          \
-                do {                                                                                                                      \
-                    static UpsPerDevice at_;                                                                                              \
-                    if (!at_) {                                                                                                           \
-                        if (hipFuncSetAttribute((const void*)prior_fwd_px_kernel<10, LWV, VARV>, hipFuncAttributeMaxDynamicSharedMemorySize, \
-                                                (int)shm_px) != hipSuccess) return UPS_E_LAUNCH;                                           \
-                        at_ = true;                                                                                                       \
-                    }                                                                                                                     \
-                    hipLaunchKernelGGL((prior_fwd_px_kernel<10, LWV, VARV>), grid, dim3(256), shm_px, s, k, tpb, spb);                     \
-                } while (0)
-                if (d->w == 128) { if (d->variant == 0) UPS_PRIOR_PX(7, 0); else UPS_PRIOR_PX(7, 1); }
-                else { if (d->variant == 0) UPS_PRIOR_PX(8, 0); else UPS_PRIOR_PX(8, 1); }
-#undef UPS_PRIOR_PX
-                UPS_LAUNCH_CHECK();
-                hipLaunchKernelGGL(prior_finalize_px_kernel, dim3(1), dim3(1024), 0, s, k, bpi, spb);
-                UPS_LAUNCH_CHECK();
-                return UPS_OK;
-            }
-        }
-    }
-    {   // direct-from-global form (round 6): view 0, the part counts the rings cannot hold; one slab record per block
-        static int dr_on = -1;
-        if (dr_on < 0) { const char* e = getenv("UPS_PRIOR_DIRECT"); dr_on = (e && e[0] == '0') ? 0 : 1; }
-        const long long hw = (long long)d->h * d->w;
-        const uintptr_t all = ((uintptr_t)d->m) | ((uintptr_t)d->l_mean) | ((uintptr_t)d->l) | ((uintptr_t)d->hard);
-        if (dr_on && d->view == 0 && (d->P == 16 || d->P == 20 || d->P == 25) && (d->w == 128 || d->w == 256) &&
-            hw % 256 == 0 && (all & 15) == 0) {
-            // blocks per image: a power of two that divides the tiles and the NSLAB slab records, two blocks per CU: every record is one more
-            // row for the one-block finalize, whose round trips to the other XCDs' records are what a finer grid pays for (measured:
-            // 2 048 / 1 024 / 512 blocks = 0.43 / 0.46 / 0.51 of the HBM roof at P = 25, B = 64)
-            const int tiles_img = (int)(hw / 256);
-            int bpi = 1;
-            while (bpi < NSLAB && (long long)d->n * bpi < 512 && tiles_img % (2 * bpi) == 0) bpi *= 2;
+    const int tiles_img = (int)((long long)d->h * d->w / 256);     // (of the two tiled forms)
+    if (px_eligible(d, 0, {d->m, d->l_mean, d->l, d->hard})) {   // pixel-per-lane form: tiles that deal evenly onto the slab records
+        // blocks per image: enough blocks for one per CU, a power of two that divides both the tiles and the NSLAB slab records
+        int bpi = 1;
+        const int cap = px_bpi_cap();
+        while (2 * bpi <= cap && bpi < NSLAB && bpi < tiles_img && (long long)d->n * bpi < 256 && tiles_img % (2 * bpi) == 0) bpi *= 2;
+        if (tiles_img % bpi == 0 && NSLAB % bpi == 0) {
+            constexpr size_t shm_px = 7 * 2 * (size_t)(256 * 10 * 4) + 4 * (4 + 4 * 10) * sizeof(float);
             const dim3 grid(d->n * bpi);
             const int tpb = tiles_img / bpi, spb = NSLAB / bpi;
-#define UPS_PRIOR_F0(PV, LWV, VARV) hipLaunchKernelGGL((prior_fwd_cpl_kernel<PV, LWV, VARV>), grid, dim3(256), 0, s, k, tpb, bpi, spb)
-#define UPS_PRIOR_F0P(PV)                                                                                  \
-            do {                                                                                          \
-                if (d->w == 128) { if (d->variant == 0) UPS_PRIOR_F0(PV, 7, 0); else UPS_PRIOR_F0(PV, 7, 1); } \
-                else { if (d->variant == 0) UPS_PRIOR_F0(PV, 8, 0); else UPS_PRIOR_F0(PV, 8, 1); }         \
-            } while (0)
-            if (d->P == 16) UPS_PRIOR_F0P(16); else if (d->P == 20) UPS_PRIOR_F0P(20); else UPS_PRIOR_F0P(25);
-#undef UPS_PRIOR_F0P
-#undef UPS_PRIOR_F0
+            const int rc = prior_dispatch<10>(d, [&](auto PC, auto LW, auto VAR) {
+                return ups_launch_lds<prior_fwd_px_kernel<PC(), LW(), VAR()>>("prior_fwd_px_kernel", shm_px, grid, dim3(256), shm_px, s, k, tpb, spb);
+            });
+            if (rc != UPS_OK) return rc;
             UPS_LAUNCH_CHECK();
             hipLaunchKernelGGL(prior_finalize_px_kernel, dim3(1), dim3(1024), 0, s, k, bpi, spb);
             UPS_LAUNCH_CHECK();
             return UPS_OK;
         }
+    }
+    if (cpl_eligible(d, 0, {d->m, d->l_mean, d->l, d->hard})) {   // direct-from-global form: one slab record per block
+        // blocks per image: a power of two that divides the tiles and the NSLAB slab records, two blocks per CU: every record is one more
+        // row for the one-block finalize, whose round trips to the other XCDs' records are what a finer grid pays for (measured:
+        // 2 048 / 1 024 / 512 blocks = 0.43 / 0.46 / 0.51 of the HBM roof at P = 25, B = 64)
+        int bpi = 1;
+        while (bpi < NSLAB && (long long)d->n * bpi < 512 && tiles_img % (2 * bpi) == 0) bpi *= 2;
+        const dim3 grid(d->n * bpi);
+        const int tpb = tiles_img / bpi, spb = NSLAB / bpi;
+        const int rc = prior_dispatch<16, 20, 25>(d, [&](auto PC, auto LW, auto VAR) {
+            hipLaunchKernelGGL((prior_fwd_cpl_kernel<PC(), LW(), VAR()>), grid, dim3(256), 0, s, k, tpb, bpi, spb);
+            return UPS_OK;
+        });
+        if (rc != UPS_OK) return rc;
+        UPS_LAUNCH_CHECK();
+        hipLaunchKernelGGL(prior_finalize_px_kernel, dim3(1), dim3(1024), 0, s, k, bpi, spb);
+        UPS_LAUNCH_CHECK();
+        return UPS_OK;
     }
     const int rows = ups_cdiv(d->h, NSLAB);
     const int PP = d->P | 1, NS = 256 / d->P;
@@ -1569,7 +1549,10 @@ extern "C" int ups_prior_fwd(const ups_prior_desc* d, void* stream) {
     while (tpx > 32 && lds_fl(tpx) * 4 > 48 * 1024) tpx >>= 1;
     const size_t shm = lds_fl(tpx) * sizeof(float);
     UPS_CHECK_ARG(shm <= 160 * 1024);
-    UPS_PRIOR_DISPATCH(prior_fwd_kernel, dim3(d->n * NSLAB), shm, k, rows, tpx);
+    const int rc = prior_dispatch_staged(d, [&](auto PC, auto LW) {
+        return ups_launch_lds<prior_fwd_kernel<PC(), LW()>>("prior_fwd_kernel", PRIOR_LDS, dim3(d->n * NSLAB), dim3(256), shm, s, k, rows, tpx);
+    });
+    if (rc != UPS_OK) return rc;
     UPS_LAUNCH_CHECK();
     hipLaunchKernelGGL(prior_finalize_img_kernel, dim3(d->n), dim3(256), 0, s, k);
     UPS_LAUNCH_CHECK();
@@ -1583,102 +1566,59 @@ extern "C" int ups_prior_bwd(const ups_prior_desc* d, void* stream) {
     UPS_CHECK_ARG(d->view == 1 || (d->l && d->l_mean && d->hard));
     hipStream_t s = (hipStream_t)stream;
     PriorK k = to_k(d, nullptr);
-    {   // pixel-per-lane form of the view-1 backward (round 5): P = 10, 128- / 256-wide images, both result maps asked for
-        static int px_on = -1;
-        if (px_on < 0) { const char* e = getenv("UPS_PRIOR_PX"); px_on = (e && e[0] == '0') ? 0 : 1; }
-        const long long hw = (long long)d->h * d->w;
-        const bool aligned = d->g_hard && d->dl_rec &&
-                             ((((uintptr_t)d->m) | ((uintptr_t)d->g_hard) | ((uintptr_t)d->dl) | ((uintptr_t)d->dl_rec)) & 15) == 0;
-        if (px_on && d->view == 1 && d->P == 10 && (d->w == 128 || d->w == 256) && hw % 256 == 0 && aligned) {
-            const int tiles_img = (int)(hw / 256);
-            int bpi = 1;          // ~two blocks per CU
-            const int cap = px_bpi_cap();
-            while (2 * bpi <= cap && bpi < tiles_img && (long long)d->n * bpi < 512 && tiles_img % (2 * bpi) == 0) bpi *= 2;
-            constexpr size_t shm_px = 3 * 2 * (size_t)(256 * 10 * 4) + 10 * 8 * sizeof(float);
-            const dim3 grid(d->n * bpi);
-            const int tpb = tiles_img / bpi;
-#define UPS_PRIOR_B1(LWV, VARV)                                                                                                          \
-            do {                                                                                                                          \
-                static UpsPerDevice at_;                                                                                                  \
-                if (!at_) {                                                                                                               \
-                    if (hipFuncSetAttribute((const void*)prior_bwd1_px_kernel<10, LWV, VARV>, hipFuncAttributeMaxDynamicSharedMemorySize,   \
-                                            (int)shm_px) != hipSuccess) return UPS_E_LAUNCH;                                               \
-                    at_ = true;                                                                                                           \
-                }                                                                                                                         \
-                hipLaunchKernelGGL((prior_bwd1_px_kernel<10, LWV, VARV>), grid, dim3(256), shm_px, s, k, tpb);                              \
-            } while (0)
-            if (d->w == 128) { if (d->variant == 0) UPS_PRIOR_B1(7, 0); else UPS_PRIOR_B1(7, 1); }
-            else { if (d->variant == 0) UPS_PRIOR_B1(8, 0); else UPS_PRIOR_B1(8, 1); }
-#undef UPS_PRIOR_B1
-            UPS_LAUNCH_CHECK();
-            return UPS_OK;
-        }
-        if (px_on && d->view == 0 && d->P == 10 && (d->w == 128 || d->w == 256) && hw % 256 == 0 && aligned && d->l && d->l_mean &&
-            d->hard && ((((uintptr_t)d->l) | ((uintptr_t)d->l_mean) | ((uintptr_t)d->hard)) & 15) == 0) {
-            const int tiles_img = (int)(hw / 256);
-            int bpi = 1;          // one block per CU
-            const int cap = px_bpi_cap();
-            while (2 * bpi <= cap && bpi < tiles_img && (long long)d->n * bpi < 256 && tiles_img % (2 * bpi) == 0) bpi *= 2;
-            constexpr size_t shm_px = (4 * 2 + 2 * 3) * (size_t)(256 * 10 * 4);
-            const dim3 grid(d->n * bpi);
-            const int tpb = tiles_img / bpi;
-#define UPS_PRIOR_B0(LWV, VARV)                                                                                                          \
-            do {                                                                                                                          \
-                static UpsPerDevice at_;                                                                                                  \
-                if (!at_) {                                                                                                               \
-                    if (hipFuncSetAttribute((const void*)prior_bwd0_px_kernel<10, LWV, VARV>, hipFuncAttributeMaxDynamicSharedMemorySize,   \
-                                            (int)shm_px) != hipSuccess) return UPS_E_LAUNCH;                                               \
-                    at_ = true;                                                                                                           \
-                }                                                                                                                         \
-                hipLaunchKernelGGL((prior_bwd0_px_kernel<10, LWV, VARV>), grid, dim3(256), shm_px, s, k, tpb);                              \
-            } while (0)
-            if (d->w == 128) { if (d->variant == 0) UPS_PRIOR_B0(7, 0); else UPS_PRIOR_B0(7, 1); }
-            else { if (d->variant == 0) UPS_PRIOR_B0(8, 0); else UPS_PRIOR_B0(8, 1); }
-#undef UPS_PRIOR_B0
-            UPS_LAUNCH_CHECK();
-            return UPS_OK;
-        }
+    // (the tiled forms: both result maps asked for; view 0 reads the logits and the hard mask too)
+    const long long hw = (long long)d->h * d->w;
+    const int tiles_img = (int)(hw / 256);
+    if (px_eligible(d, 1, {d->m, d->g_hard, d->dl, d->dl_rec})) {   // pixel-per-lane form of the view-1 backward
+        int bpi = 1;          // ~two blocks per CU
+        const int cap = px_bpi_cap();
+        while (2 * bpi <= cap && bpi < tiles_img && (long long)d->n * bpi < 512 && tiles_img % (2 * bpi) == 0) bpi *= 2;
+        constexpr size_t shm_px = 3 * 2 * (size_t)(256 * 10 * 4) + 10 * 8 * sizeof(float);
+        const dim3 grid(d->n * bpi);
+        const int tpb = tiles_img / bpi;
+        const int rc = prior_dispatch<10>(d, [&](auto PC, auto LW, auto VAR) {
+            return ups_launch_lds<prior_bwd1_px_kernel<PC(), LW(), VAR()>>("prior_bwd1_px_kernel", shm_px, grid, dim3(256), shm_px, s, k, tpb);
+        });
+        if (rc != UPS_OK) return rc;
+        UPS_LAUNCH_CHECK();
+        return UPS_OK;
     }
-    {   // direct-from-global form (round 6): view 0, the part counts the rings cannot hold, both result maps asked for
-        static int dr_on = -1;
-        if (dr_on < 0) { const char* e = getenv("UPS_PRIOR_DIRECT"); dr_on = (e && e[0] == '0') ? 0 : 1; }
-        const long long hw = (long long)d->h * d->w;
-        const uintptr_t all = ((uintptr_t)d->m) | ((uintptr_t)d->l_mean) | ((uintptr_t)d->l) | ((uintptr_t)d->hard) | ((uintptr_t)d->g_hard) |
-                              ((uintptr_t)d->dl) | ((uintptr_t)d->dl_rec);
-        if (dr_on && d->view == 1 && (d->P == 16 || d->P == 20 || d->P == 25) && (d->w == 128 || d->w == 256) && hw % 256 == 0 &&
-            d->g_hard && d->dl_rec && (((uintptr_t)d->m | (uintptr_t)d->g_hard | (uintptr_t)d->dl | (uintptr_t)d->dl_rec) & 15) == 0 &&
-            d->n * (hw / 256) < (1ll << 31)) {
-            const int bpi_c = (int)ups_cdiv(hw, d->P == 16 ? Cpl<16>::PXB : Cpl<20>::PXB);
-            const dim3 grid((unsigned)(d->n * (long long)bpi_c));
-#define UPS_PRIOR_D1(PV, LWV, VARV) hipLaunchKernelGGL((prior_bwd1_cpl_kernel<PV, LWV, VARV>), grid, dim3(256), 0, s, k, bpi_c)
-#define UPS_PRIOR_D1P(PV)                                                                                  \
-            do {                                                                                          \
-                if (d->w == 128) { if (d->variant == 0) UPS_PRIOR_D1(PV, 7, 0); else UPS_PRIOR_D1(PV, 7, 1); } \
-                else { if (d->variant == 0) UPS_PRIOR_D1(PV, 8, 0); else UPS_PRIOR_D1(PV, 8, 1); }         \
-            } while (0)
-            if (d->P == 16) UPS_PRIOR_D1P(16); else if (d->P == 20) UPS_PRIOR_D1P(20); else UPS_PRIOR_D1P(25);
-#undef UPS_PRIOR_D1P
-#undef UPS_PRIOR_D1
-            UPS_LAUNCH_CHECK();
+    if (px_eligible(d, 0, {d->m, d->g_hard, d->dl, d->dl_rec, d->l, d->l_mean, d->hard})) {
+        int bpi = 1;          // one block per CU
+        const int cap = px_bpi_cap();
+        while (2 * bpi <= cap && bpi < tiles_img && (long long)d->n * bpi < 256 && tiles_img % (2 * bpi) == 0) bpi *= 2;
+        constexpr size_t shm_px = (4 * 2 + 2 * 3) * (size_t)(256 * 10 * 4);
+        const dim3 grid(d->n * bpi);
+        const int tpb = tiles_img / bpi;
+        const int rc = prior_dispatch<10>(d, [&](auto PC, auto LW, auto VAR) {
+            return ups_launch_lds<prior_bwd0_px_kernel<PC(), LW(), VAR()>>("prior_bwd0_px_kernel", shm_px, grid, dim3(256), shm_px, s, k, tpb);
+        });
+        if (rc != UPS_OK) return rc;
+        UPS_LAUNCH_CHECK();
+        return UPS_OK;
+    }
+    // direct-from-global forms: a grid of chunks of PXB pixels that fits 32 bits
+    if (cpl_eligible(d, 1, {d->m, d->g_hard, d->dl, d->dl_rec}) && d->n * (hw / 256) < (1ll << 31)) {
+        const int bpi_c = (int)ups_cdiv(hw, d->P == 16 ? Cpl<16>::PXB : Cpl<20>::PXB);
+        const dim3 grid((unsigned)(d->n * (long long)bpi_c));
+        const int rc = prior_dispatch<16, 20, 25>(d, [&](auto PC, auto LW, auto VAR) {
+            hipLaunchKernelGGL((prior_bwd1_cpl_kernel<PC(), LW(), VAR()>), grid, dim3(256), 0, s, k, bpi_c);
             return UPS_OK;
-        }
-        if (dr_on && d->view == 0 && (d->P == 16 || d->P == 20 || d->P == 25) && (d->w == 128 || d->w == 256) && hw % 256 == 0 &&
-            d->g_hard && d->dl_rec && d->l && d->l_mean && d->hard && (all & 15) == 0 && d->n * (hw / 256) < (1ll << 31)) {
-            const int pxb = d->P == 16 ? Cpl<16>::PXB : Cpl<20>::PXB;
-            const int bpi_c = (int)ups_cdiv(hw, pxb);
-            const dim3 grid((unsigned)(d->n * (long long)bpi_c));
-#define UPS_PRIOR_D0(PV, LWV, VARV) hipLaunchKernelGGL((prior_bwd0_cpl_kernel<PV, LWV, VARV>), grid, dim3(256), 0, s, k, bpi_c)
-#define UPS_PRIOR_D0P(PV)                                                                                  \
-            do {                                                                                          \
-                if (d->w == 128) { if (d->variant == 0) UPS_PRIOR_D0(PV, 7, 0); else UPS_PRIOR_D0(PV, 7, 1); } \
-                else { if (d->variant == 0) UPS_PRIOR_D0(PV, 8, 0); else UPS_PRIOR_D0(PV, 8, 1); }         \
-            } while (0)
-            if (d->P == 16) UPS_PRIOR_D0P(16); else if (d->P == 20) UPS_PRIOR_D0P(20); else UPS_PRIOR_D0P(25);
-#undef UPS_PRIOR_D0P
-#undef UPS_PRIOR_D0
-            UPS_LAUNCH_CHECK();
+        });
+        if (rc != UPS_OK) return rc;
+        UPS_LAUNCH_CHECK();
+        return UPS_OK;
+    }
+    if (cpl_eligible(d, 0, {d->m, d->l_mean, d->l, d->hard, d->g_hard, d->dl, d->dl_rec}) && d->n * (hw / 256) < (1ll << 31)) {
+        const int bpi_c = (int)ups_cdiv(hw, d->P == 16 ? Cpl<16>::PXB : Cpl<20>::PXB);
+        const dim3 grid((unsigned)(d->n * (long long)bpi_c));
+        const int rc = prior_dispatch<16, 20, 25>(d, [&](auto PC, auto LW, auto VAR) {
+            hipLaunchKernelGGL((prior_bwd0_cpl_kernel<PC(), LW(), VAR()>), grid, dim3(256), 0, s, k, bpi_c);
             return UPS_OK;
-        }
+        });
+        if (rc != UPS_OK) return rc;
+        UPS_LAUNCH_CHECK();
+        return UPS_OK;
     }
     const int PP = d->P | 1;
     auto lds_fl = [&](int t) { return ((d->view == 0 ? (size_t)(5 * t + 4 * d->w) : (size_t)(4 * t)) * PP + (size_t)d->P * 8 + (size_t)t * 4); };
@@ -1687,7 +1627,10 @@ extern "C" int ups_prior_bwd(const ups_prior_desc* d, void* stream) {
     const size_t shm = lds_fl(tpx) * sizeof(float);
     UPS_CHECK_ARG(shm <= 160 * 1024);
     const dim3 grid(ups_cdiv((long long)d->h * d->w, tpx) * d->n);
-    UPS_PRIOR_DISPATCH(prior_bwd_kernel, grid, shm, k, tpx);
+    const int rc = prior_dispatch_staged(d, [&](auto PC, auto LW) {
+        return ups_launch_lds<prior_bwd_kernel<PC(), LW()>>("prior_bwd_kernel", PRIOR_LDS, grid, dim3(256), shm, s, k, tpx);
+    });
+    if (rc != UPS_OK) return rc;
     UPS_LAUNCH_CHECK();
     return UPS_OK;
 }

@@ -3,10 +3,11 @@ behaviour is a function of an undocumented environment").
 
 * The Python package reads its switches through `flag()` / `value()` below, once, at import; `report()` lists the ones that differ
   from their defaults and the Trainer logs that line at start-up.
-* The library's switches are `getenv` calls inside csrc/*.hip (most are read once per process, the test hooks at every call); they
-  are listed here with the same fields so that the one table is complete.  `tests/test_host.py::test_every_switch_is_documented` greps
-  both trees for `UPS_[A-Z0-9_]+` environment reads and fails when a switch is not in this table (or the table names one that no
-  longer exists).
+* The library's switches are read through the helpers of csrc/env.h and nowhere else: `UPS_ENV_*_CACHED("UPS_...")` once per process,
+  `ups_env_*_now("UPS_...")` at every call (the hooks that tests toggle inside one process) -- the call site says which, and that is
+  part of a switch's contract.  They are listed here with the same fields so that the one table is complete.
+  `tests/test_host.py::test_every_switch_is_documented` greps both trees for `UPS_[A-Z0-9_]+` environment reads and fails when a switch
+  is not in this table (or the table names one that no longer exists), and when csrc/ calls `getenv` outside env.h.
 * kinds: `product` = a supported way to run (also reachable as a config key where one is named), `ab` = kept for A/B measurements of a
   decision that is documented in docs/design/, `test` = a hook the test-suite uses to reach a code path at small sizes, `debug`.
 * Compile-time forms (`-DUPS_ROWS_FWD_SIGN`, `-DUPS_ROWS_NO_FENCE`, `-DUPS_VMAX_BUILTIN`: the wrong-result investigation of
@@ -43,7 +44,7 @@ SWITCHES = OrderedDict([
     ("UPS_DP_STANDIN", ("0", "debug", "dist.py", "1: every bucket all-reduce replaced by a device copy on its own stream (one-GPU stream-budget probe)")),
     ("UPS_FORCE_COLLECTIVES", ("0", "test", "dist.py", "1: issue the collectives at world size 1 (the RCCL call pattern test)")),
     ("UPS_JOIN_TIMING", ("0", "debug", "model.py", "1: HIP events around the end-of-backward joins (tools/probes/join_wait.py)")),
-    # ---- libupsparts_hip.so (getenv in csrc/)
+    # ---- libupsparts_hip.so (the csrc/env.h helpers)
     ("UPS_ROWS_KERNEL", ("1", "test", "conv3x3_rows.hip", "0: row-stream layers through the patch / generic kernels; force: also at small batches (parity tests)")),
     ("UPS_S2_KERNEL", ("1", "ab", "conv3x3_s2.hip", "0: the other stride-2 forwards through the generic kernel")),
     ("UPS_THIN_SW", ("32", "ab", "conv3x3_rows.hip", "16: 16-column strips in the logit convolution (measured equal)")),
