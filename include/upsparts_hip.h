@@ -28,8 +28,9 @@ extern "C" {
 /* 2: ups_conv_desc grew by out_act / res_act, ups_wgrad_desc by in_f16, UPS_F16 was added (round 3) -- a stale library
  * built against the older structs ignores those fields silently, so the loader also compares ups_struct_sizes().
  * 3: ups_wgrad_desc grew by dout_f8 / dout_f8_scale / in_f8_scale / in_f8_amax (the fp8 weight gradient, round 5).
- * 5: ups_gather_views was added (device-resident training data): a binding that expects it refuses an older library by number. */
-#define UPS_ABI_VERSION 5
+ * 5: ups_gather_views was added (device-resident training data): a binding that expects it refuses an older library by number.
+ * 6: ups_part_confusion was added (part-IoU evaluation on the device). */
+#define UPS_ABI_VERSION 6
 
 /* UPS_F16 (IEEE half): element type of FORWARD tensors of precision-critical scopes (the mask decoder): ups_conv_igemm,
  * ups_weight_prep(_batch), ups_bilinear2x_fwd, ups_convert / ups_pad_convert accept it; gradients are never fp16 (range): the
@@ -466,6 +467,23 @@ int ups_canvas_first_item(const float* m, const float* hard, const uint32_t* bit
  * shape or alignment one pixel per lane.  No scratch, no atomics: the same plan gives the same bits. */
 int ups_gather_views(const uint8_t* images, int64_t n_images, const int32_t* plan, int32_t B, int32_t S, float* view0, float* view1,
                      float* target, void* stream);
+
+/* ---------------------------------------------------------------- part-IoU evaluation (csrc/evalparts.hip)
+ * The per-image joint histogram of inferred part and ground-truth label: the sufficient statistic of the protocol of
+ * eval_01.py:229-383 (evalutil.evaluate_from_counts).
+ * counts[i][p][g] += #{pixels k of image i : pred[i][k] == p and lut[gt[i][k]] == g}      (lut == NULL: identity)
+ * pred   [N, HW] int64   arg-max map of ups_part_softmax_fwd (8-byte aligned; 16-byte loads where the address allows)
+ * gt     [N, HW] uint8   ground-truth labels as stored (any alignment)
+ * lut    [256]   uint8   DEVICE, raw label -> evaluated label (the reference's dp_remap_dict), or NULL
+ * counts [N, P, G] int32, caller-zeroed or holding earlier launches' counts: the kernel only adds
+ * invalid [1] int32: += number of pixels with pred outside [0,P) or mapped label >= G; such pixels touch no count
+ * 1 <= P <= 32, 1 <= G <= 32, else UPS_E_UNSUPPORTED.  UPS_E_ARG: a NULL required pointer, N <= 0, HW <= 0, HW > 2^31 - 1.
+ * Integer atomics only: the result does not depend on launch geometry or on the order in which blocks finish.
+ * The kernel takes the arg-max map and never recomputes it from logits: out_parts_hard is the first maximal index of the fp32
+ * soft-max, where two different logits can round to a tie that they would not have as logits -- a fused arg-max + confusion form
+ * would not be bit-equal to the host evaluation, so there is none. */
+int ups_part_confusion(const int64_t* pred, const uint8_t* gt, const uint8_t* lut, int32_t N, int64_t HW, int32_t P, int32_t G,
+                       int32_t* counts, int32_t* invalid, void* stream);
 
 /* ---------------------------------------------------------------- mask priors (M:652-797), fused
  * One pass over l/m per view producing the partial sums, one fused backward producing dl.

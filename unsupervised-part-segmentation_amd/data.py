@@ -351,3 +351,47 @@ def _device_batches(L, dataset, images, batch_size, device, shuffle, seed, epoch
                        L.ptr(out.get("view0_target")), L.stream())
             yield out
         ep += 1
+
+
+# ------------------------------------------------------------------ validation set of `val_freq` (Trainer.validate)
+class ValidationSet(object):
+    """``val_csv`` decoded ONCE: uint8 views [n,S,S,3] and uint8 label maps [n,S,S] (pinned when a device is there), the first
+    ``val_max_images`` rows (default 512) in csv order, no flips, no partners.  Every other key -- data_root, the csv columns,
+    spatial_size, ``data_gt_segmentation_column`` (required) -- is the training dataset's."""
+
+    def __init__(self, config, workers=8):
+        from .evalutil import labels_u8
+        col = config.get("data_gt_segmentation_column")
+        if not config.get("val_csv") or not col:
+            raise ValueError("val_freq needs `val_csv` and `data_gt_segmentation_column` (the csv column with the label images)")
+        ds = StochasticPairs(dict(config, data_csv=config["val_csv"]))
+        if col not in ds.labels:
+            raise ValueError("val_csv {} has no column {}".format(config["val_csv"], col))
+        n = min(len(ds), int(config.get("val_max_images", 512)))
+        if n < 1:
+            raise ValueError("val_csv {} lists no image".format(config["val_csv"]))
+        S = int(ds.size)
+        views, labels = np.empty((n, S, S, 3), dtype=np.uint8), np.empty((n, S, S), dtype=np.uint8)
+        with cf.ThreadPoolExecutor(max_workers=max(1, min(int(workers), MAX_STORE_WORKERS))) as pool:
+            for i, img in enumerate(pool.map(ds.preprocess_u8, ds.labels["file_path_"][:n])):
+                views[i] = img
+            for i, lab in enumerate(pool.map(ds.preprocess_labels, [os.path.join(ds.root, q) for q in ds.labels[col][:n]])):
+                labels[i] = labels_u8(lab)
+        self.views, self.labels = torch.from_numpy(views), torch.from_numpy(labels)
+        if torch.cuda.is_available():
+            self.views, self.labels = self.views.pin_memory(), self.labels.pin_memory()
+
+    def __len__(self):
+        return self.views.shape[0]
+
+    def float_views(self, c0, c1, device):
+        """Views [c0, c1) as float32 [k,S,S,3] on `device`, current stream: the bytes are copied (non-blocking) and ``ups_gather_views``
+        applies the host path's `u / 127.5 - 1` bit for bit (plan: image b -> view b, no flip)."""
+        from . import lib as L
+        u8 = self.views[c0:c1].to(device, non_blocking=True)
+        k, S = u8.shape[0], u8.shape[1]
+        plan = torch.arange(k, dtype=torch.int32, device=device)[:, None].repeat(1, 3)
+        plan[:, 2] = 0
+        out = torch.empty((2, k, S, S, 3), dtype=torch.float32, device=device)
+        L.call("ups_gather_views", L.ptr(u8), k, L.ptr(plan), k, S, L.ptr(out[0]), L.ptr(out[1]), None, L.stream())
+        return out[0]

@@ -3,7 +3,9 @@
 The reference takes these from the un-vendored ``denseposelib`` (``compute_best_iou_remapping``, ``remap_parts``,
 ``compute_iou``); semantics re-derived from their call sites: every inferred part id is mapped to the ground-truth label it
 overlaps best (IoU over the whole evaluation set), the remapped prediction is scored per label, and the reported "overall"
-number averages the labels except ``background`` (cub_semantic_ours.ipynb:615).  NumPy only -- outside the hot path.
+number averages the labels except ``background`` (cub_semantic_ours.ipynb:615).  ``evaluate_parts`` is NumPy on the pixel maps;
+``evaluate_from_counts`` computes the same dict from the per-image part x label histogram (``confusion_counts`` on the host,
+ups_part_confusion on the device through ``PartEvaluator``), which is all the protocol needs.
 """
 import logging
 import os
@@ -73,6 +75,193 @@ def evaluate_parts(out_parts_hard, gt_segmentation, background_label=0):
     return {"mapping": mapping, "iou": per_label, "per_image": rows,
             "overall": float(np.mean(fg)) if fg else float("nan"),
             "pooled": dict(zip(pl.tolist(), pooled.tolist()))}
+
+
+def lut_array(lut):
+    """The raw label -> evaluated label table as uint8 [256]: None, a {raw: new} dict (the reference's dp_remap_dict; raw labels it
+    does not list keep their value) or 256 values.  ValueError on an entry outside 0..255."""
+    if lut is None:
+        return None
+    if isinstance(lut, dict):
+        t = np.arange(256, dtype=np.int64)
+        for k, v in lut.items():
+            if not 0 <= int(k) <= 255:
+                raise ValueError("label lut: raw label {} is outside 0..255".format(k))
+            t[int(k)] = int(v)
+    else:
+        t = np.asarray(lut).astype(np.int64).reshape(-1)
+    if t.size != 256 or t.min() < 0 or t.max() > 255:
+        raise ValueError("label lut: 256 entries in 0..255 expected (got {} in [{}, {}])".format(t.size, t.min(), t.max()))
+    return t.astype(np.uint8)
+
+
+def labels_u8(gt):
+    """Ground-truth label maps as uint8; a label outside 0..255 is a ValueError (the device stores labels as bytes)."""
+    gt = np.asarray(gt)
+    if gt.dtype == np.uint8:
+        return gt
+    if gt.size and (gt.min() < 0 or gt.max() > 255 or np.any(gt != np.floor(gt))):
+        raise ValueError("ground-truth labels must be integers in 0..255 (got values in [{}, {}])".format(gt.min(), gt.max()))
+    return gt.astype(np.uint8)
+
+
+def confusion_counts(pred, gt, P, G, lut=None, return_invalid=False):
+    """counts [N,P,G] int32 with counts[i,p,g] = #{pixels of image i with pred == p and lut[gt] == g} (lut None: identity): the joint
+    histogram ups_part_confusion (csrc/evalparts.hip) computes, in NumPy -- its test reference and the host fallback for P or G
+    above 32.  pred, gt: integer maps [N,..] of one shape; lut: see ``lut_array``.  A pixel with pred outside [0,P) or a mapped
+    label >= G is counted nowhere; return_invalid=True returns (counts, number of such pixels)."""
+    pred = np.asarray(pred)
+    N = pred.shape[0]
+    pred = pred.reshape(N, -1).astype(np.int64)
+    lab = np.asarray(gt).reshape(N, -1).astype(np.int64)
+    if pred.shape != lab.shape:
+        raise ValueError("confusion_counts: pred and gt differ in shape")
+    t = lut_array(lut)
+    if t is not None:
+        if lab.size and (lab.min() < 0 or lab.max() > 255):
+            raise ValueError("confusion_counts: a lut needs labels in 0..255")
+        lab = t.astype(np.int64)[lab]
+    ok = (pred >= 0) & (pred < P) & (lab >= 0) & (lab < G)
+    counts = np.zeros((N, P, G), dtype=np.int32)
+    for i in range(N):
+        key = pred[i][ok[i]] * G + lab[i][ok[i]]
+        counts[i] = np.bincount(key, minlength=P * G).reshape(P, G)
+    return (counts, int(ok.size - ok.sum())) if return_invalid else counts
+
+
+def _quot(inter, union):
+    # the division evaluate_parts performs: np.int64 / np.int64 -> float64 (0.0 on an empty union)
+    return np.int64(inter) / np.int64(union) if union else 0.0
+
+
+def _iou_rows(R, labels):
+    """compute_iou on remapped counts R [L,G] (R[a,b] = pixels predicted as labels[a] with ground truth labels[b]) -> (ious, present)."""
+    pred_n, gt_n = R.sum(axis=1), R.sum(axis=0)
+    present = [b for b in range(len(labels)) if gt_n[b] > 0]
+    ious = [_quot(R[b, b], pred_n[b] + gt_n[b] - R[b, b]) for b in present]
+    return np.asarray(ious, dtype=np.float64), [labels[b] for b in present]
+
+
+def evaluate_from_counts(counts, part_ids=None, labels=None, background_label=0):
+    """``evaluate_parts`` from the joint histogram counts [N,P,G] (``confusion_counts`` / ups_part_confusion): the same dict --
+    mapping, iou, per_image, pooled, overall -- with the same integers divided, hence the same float64 values and the same ties.
+    part_ids [P] / labels [G]: the part id of row p and the (ascending) label of column g; default 0..P-1 / 0..G-1.
+    "Present" = a non-zero row / column sum: over the set for `mapping` and `iou`, per image for `per_image`.  Tie rules as
+    ``compute_best_iou_remapping``: labels are tried in ascending order and only a strictly larger IoU replaces the best; a part that
+    occurs nowhere has no mapping entry; a label absent from an image's ground truth is absent from that image's row."""
+    C = np.asarray(counts).astype(np.int64)
+    N, P, G = C.shape
+    part_ids = list(range(P)) if part_ids is None else [int(p) for p in part_ids]
+    labels = list(range(G)) if labels is None else [int(g) for g in labels]
+    if len(part_ids) != P or len(labels) != G or sorted(labels) != labels or sorted(part_ids) != part_ids:
+        raise ValueError("evaluate_from_counts: {} ascending part ids and {} ascending labels expected".format(P, G))
+    T = C.sum(axis=0)
+    part_n, label_n = T.sum(axis=1), T.sum(axis=0)
+    gl = [g for g in range(G) if label_n[g] > 0]
+    mapping, col = {}, {}
+    for p in range(P):
+        if part_n[p] == 0:
+            continue
+        best, best_iou = gl[0], -1.0
+        for g in gl:
+            iou = _quot(T[p, g], part_n[p] + label_n[g] - T[p, g])
+            if iou > best_iou:
+                best, best_iou = g, float(iou)
+        mapping[part_ids[p]], col[p] = labels[best], best
+    # remap_parts: the rows of the parts mapped to one label are added up (every present part has a mapping)
+    R = np.zeros((N, G, G), dtype=np.int64)
+    for p, g in col.items():
+        R[:, g, :] += C[:, p, :]
+    rows = []
+    for i in range(N):
+        ious, present = _iou_rows(R[i], labels)
+        rows.append(dict(zip(present, ious.tolist())))
+    per_label = {labels[g]: float(np.mean([r[labels[g]] for r in rows if labels[g] in r])) for g in gl}
+    fg = [v for g, v in per_label.items() if g != background_label]
+    pooled, pl = _iou_rows(R.sum(axis=0), labels)
+    return {"mapping": mapping, "iou": per_label, "per_image": rows,
+            "overall": float(np.mean(fg)) if fg else float("nan"),
+            "pooled": dict(zip(pl, pooled.tolist()))}
+
+
+class PartEvaluator(object):
+    """The part-IoU protocol with the pixels left on the device: ``update`` runs ``model.segment`` (pose path only) and
+    ups_part_confusion into a device buffer of counts that grows by one [P,G] row per image, without synchronising with the host;
+    ``result`` copies the counts once and returns ``evaluate_from_counts``.
+    n_labels = G: evaluated labels are 0..G-1 (columns no pixel hits are "absent", so a G larger than needed changes nothing).
+    lut: raw label -> evaluated label (``lut_array``).  P or G above 32 (the kernel's table) falls back to ``confusion_counts`` on
+    the host, with one logged line."""
+
+    def __init__(self, model, n_labels, lut=None, background_label=0):
+        import torch
+        self.model, self.P, self.G, self.background_label = model, int(model.n_parts), int(n_labels), background_label
+        self.lut = lut_array(lut)
+        self.on_device = self.P <= 32 and self.G <= 32
+        if self.P < 1 or self.G < 1:
+            raise ValueError("PartEvaluator: n_parts and n_labels must be positive (got {}, {})".format(self.P, self.G))
+        if not self.on_device:
+            LOG.info("PartEvaluator: P = %d, G = %d exceed the device table (32 x 32): counting on the host", self.P, self.G)
+        self._lut_dev = None if self.lut is None or not self.on_device else torch.from_numpy(self.lut).to(model.device)
+        self.reset()
+
+    def reset(self):
+        import torch
+        self.n, self._host, self._host_invalid = 0, [], 0
+        self._counts = self._invalid = None
+        if self.on_device:
+            self._counts = torch.zeros((64, self.P, self.G), dtype=torch.int32, device=self.model.device)
+            self._invalid = torch.zeros(1, dtype=torch.int32, device=self.model.device)
+
+    def _labels(self, gt):
+        import torch
+        if torch.is_tensor(gt) and gt.dtype == torch.uint8:
+            return gt
+        return torch.from_numpy(np.ascontiguousarray(labels_u8(gt.cpu().numpy() if torch.is_tensor(gt) else gt)))
+
+    def update(self, views, gt, valid=None):
+        """views [n,S,S,3] in [-1,1], gt [n,S,S] integer labels (cast to uint8 on the host: a label outside 0..255 raises ValueError
+        before anything is launched); valid: only the first `valid` images count (a padded last batch)."""
+        import torch
+        from . import ops
+        gt = self._labels(gt)
+        n = len(gt) if valid is None else int(valid)
+        if n == 0:
+            return
+        views, gt = views[:n], gt[:n]
+        pred = self.model.segment(torch.as_tensor(views))
+        if tuple(pred.shape) != tuple(gt.shape):
+            raise ValueError("PartEvaluator.update: label maps {} do not match the part maps {}".format(tuple(gt.shape), tuple(pred.shape)))
+        if not self.on_device:
+            c, bad = confusion_counts(pred.cpu().numpy(), gt.cpu().numpy(), self.P, self.G, self.lut, return_invalid=True)
+            self._host.append(c)
+            self._host_invalid += bad
+            self.n += n
+            return
+        if self.n + n > self._counts.shape[0]:        # grow on the device (stream-ordered): the evaluated rows are kept
+            grown = torch.zeros((max(2 * self._counts.shape[0], self.n + n), self.P, self.G), dtype=torch.int32, device=self._counts.device)
+            grown[:self.n] = self._counts[:self.n]
+            self._counts = grown
+        ops.part_confusion(pred, gt.to(pred.device, non_blocking=True), self.P, self.G, lut=self._lut_dev,
+                           counts=self._counts[self.n:self.n + n], invalid=self._invalid)
+        self.n += n
+
+    def counts(self):
+        """(counts [n,P,G] int32 NumPy, invalid): the one copy to the host."""
+        import torch
+        if not self.on_device:
+            return (np.concatenate(self._host) if self._host else np.zeros((0, self.P, self.G), np.int32)), self._host_invalid
+        both = torch.cat([self._counts[:self.n].reshape(-1), self._invalid]).cpu().numpy()
+        return both[:-1].reshape(self.n, self.P, self.G), int(both[-1])
+
+    def result(self):
+        from .lib import UpsError
+        counts, invalid = self.counts()
+        if invalid != 0:
+            raise UpsError("PartEvaluator: {} pixel(s) with a part id outside [0, {}) or a label outside [0, {}) were not counted "
+                           "(n_labels too small, or a label lut is missing)".format(invalid, self.P, self.G))
+        if self.n == 0:
+            raise ValueError("PartEvaluator.result: no image was evaluated")
+        return evaluate_from_counts(counts, background_label=self.background_label)
 
 
 def write_eval_tables(res, root, global_step, part_names=None, background_label=0):

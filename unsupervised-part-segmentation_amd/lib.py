@@ -14,7 +14,7 @@ from . import switches as SW
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = SW.value("UPS_LIB") or os.path.join(_HERE, "csrc", "libupsparts_hip.so")   # UPS_LIB: A/B builds
 
-ABI_VERSION = 5               # include/upsparts_hip.h UPS_ABI_VERSION
+ABI_VERSION = 6               # include/upsparts_hip.h UPS_ABI_VERSION
 F32, BF16, F16 = 0, 1, 2      # F16: forward tensors of precision-critical scopes (held in torch.bfloat16 containers, see ops.py)
 ACT_NONE, ACT_LRELU, ACT_RELU, ACT_ELU = 0, 1, 2, 3
 ACT = {None: ACT_NONE, "leaky_relu": ACT_LRELU, "relu": ACT_RELU, "elu": ACT_ELU}
@@ -151,6 +151,7 @@ _SIGS = {
     "ups_canvas_assigned_parts": ([_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P], C.c_int),
     "ups_canvas_first_item": ([_P, _P, _P, _I, _I, _I, C.POINTER(_F), _I, C.POINTER(_F), _I, _P, _P, _P, _P, _P, _P], C.c_int),
     "ups_gather_views": ([_P, _L, _P, _I, _I, _P, _P, _P, _P], C.c_int),
+    "ups_part_confusion": ([_P, _P, _P, _I, _L, _I, _I, _P, _P, _P], C.c_int),
     "ups_prior_sums_floats": ([_I, _I], _Z),
     "ups_prior_fwd": ([C.POINTER(PriorDesc), _P], C.c_int),
     "ups_prior_bwd": ([C.POINTER(PriorDesc), _P], C.c_int),

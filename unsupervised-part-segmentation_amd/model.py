@@ -161,10 +161,11 @@ class TrainModel(object):
     # training graph's _cross_generated, SB_model48i/model.py:488-500).  Only unpool_features and the hourglass decoder depend on
     # the (pose, appearance) pair: n poses and m appearances are encoded once each, K = n * m combinations are decoded.  Test-mode
     # semantics as forward(batch, noise=None): latent means, no sampling noise, this model's Fp8State active.
-    def _encode(self, *groups):
+    def _encode(self, *groups, masks=True):
         """groups: (views [n_g,S,S,3], want_feat) -> one dict per group.  The pose path (e_pi, dv, soft-max) runs ONCE over all groups
         concatenated, as ``forward`` runs it over view0 and view1 together: the convolutions' split-K factors depend on the batch, so
-        only the same batch composition gives ``forward``'s bits.  e_alpha runs per group that wants features (forward: view1)."""
+        only the same batch composition gives ``forward``'s bits.  e_alpha runs per group that wants features (forward: view1).
+        masks=False (``segment``): only "out_parts_hard" per group -- no hard masks, no bit sets, nothing for e_alpha to read."""
         cfg = self.config
         ops.Fp8.activate(self.fp8)
         vs = [g[0].to(self.device, torch.float32).contiguous() for g in groups]
@@ -174,12 +175,16 @@ class TrainModel(object):
         img = self.to_act(v)
         pe = self.nets.e_pi(Act(img, n, S, S, 3)).t.view(n, -1)
         lm = self.nets.dv(self.latent_act(pe[:, :Z].contiguous())).t
-        _, m, hard, _, bits = ops.part_softmax(lm, None, want_bits=P <= 32)
+        if masks:
+            _, m, hard, _, bits = ops.part_softmax(lm, None, want_bits=P <= 32)
         _, soft, _, amax = ops.part_softmax(lm.contiguous(), None, want_hard=False, want_argmax=True)
         outs, o = [], 0
         for vg, (_, want_feat) in zip(vs, groups):
             sl = slice(o, o + vg.shape[0])
             o += vg.shape[0]
+            if not masks:
+                outs.append({"out_parts_hard": amax[sl]})
+                continue
             out = {"hard": hard[sl].contiguous(), "out_parts_hard": amax[sl], "out_parts_soft": soft[sl], "m0_sample": m[sl]}
             if want_feat:
                 yp = self.nets.e_alpha(self.part_images(img[sl], vg, out["hard"], None if bits is None else bits[sl].contiguous())).t
@@ -194,6 +199,31 @@ class TrainModel(object):
         convolutions plan by the batch (``_encode``), so the views stand in for the view1 half as well: the pose path is paid twice
         here (transfer_matrix, which encodes rows and columns together, pays it once)."""
         return self._encode((views, False), (views, False))[0]
+
+    @torch.no_grad()
+    def segment(self, views):
+        """views [n,S,S,3] -> ``out_parts_hard`` int64 [n,S,S] on the device, from the pose path alone: e_pi -> dv -> soft-max
+        arg-max.  No e_alpha, no unpool, no dd -- most of a ``forward``'s FLOPs -- and no soft or hard map is kept.
+        The views run in passes of at most 2 * batch_size images, each pass ONE ``_encode`` of two groups of batch_size: the batch
+        ``forward`` gives the pose path.  As ``_encode`` says, the convolutions' split-K factors depend on the batch, so only the same
+        batch composition gives ``forward``'s bits: for n = 2 * batch_size the first batch_size maps are the bits of
+        ``forward({"view0": views[:B], "view1": views[B:]})["out_parts_hard"]``.  A shorter last pass is padded to 2 * batch_size with
+        copies of its first image and the padding is dropped, so every pass plans alike.  Test-mode semantics (latent means, no
+        noise).  Under precision: fp8 a pass records activation maxima like any forward."""
+        B = int(self.config["batch_size"])
+        views = torch.as_tensor(views)
+        n, S = views.shape[0], views.shape[1]
+        out = torch.empty((n, S, S), dtype=torch.int64, device=self.device)
+        for c0 in range(0, n, 2 * B):
+            v = views[c0:c0 + 2 * B].to(self.device, torch.float32)
+            k = v.shape[0]
+            if k < 2 * B:
+                v = torch.cat([v, v[:1].expand(2 * B - k, S, S, v.shape[3])], 0)
+            a, b = self._encode((v[:B], False), (v[B:], False), masks=False)
+            out[c0:c0 + min(k, B)] = a["out_parts_hard"][:k]
+            if k > B:
+                out[c0 + B:c0 + k] = b["out_parts_hard"][:k - B]
+        return out
 
     @torch.no_grad()
     def encode_appearance(self, views):
@@ -338,12 +368,27 @@ def gram_weight_of(config, logger=None):
     return v if v > 0 else 0.0
 
 
+def check_validation_config(config):
+    """The refusals of `val_freq` (ValueError with the reason), decided from the config alone, before anything touches the device."""
+    if not int(config.get("val_freq", 0) or 0):
+        return
+    if str(config.get("precision", "bf16")).lower() in ("fp8", "f8", "e4m3"):
+        raise ValueError("val_freq cannot be combined with precision: fp8: the model's forward records activation maxima into "
+                         "its delayed-scaling slots, so a validation pass would move the next training step's scales")
+    if bool(config.get("hip_graph", SW.flag("UPS_GRAPH"))):
+        raise ValueError("val_freq cannot be combined with hip_graph: True: eager launches between replays of the captured "
+                         "step have not been shown safe")
+    if not config.get("val_csv") or not config.get("data_gt_segmentation_column"):
+        raise ValueError("val_freq needs `val_csv` and `data_gt_segmentation_column` (the csv column with the label images)")
+
+
 class Trainer(object):
     """Mirror of model.py:570-1068 plus the pieces edflow's TFBaseTrainer supplied (session loop,
     one Adam per loss key over the variables whose name contains the key, logging cadence)."""
 
     def __init__(self, config, root=None, model=None, **kwargs):
         self.config, self.root, self.model = config, root, model
+        check_validation_config(config)
         self.device = model.device
         self.logger = kwargs.get("logger")
         self.global_step = 0
@@ -427,6 +472,11 @@ class Trainer(object):
         # `log_images` (default off): the reference's img_ops (model.py:968-1053) as uint8 canvases on the steps that log scalars
         self.log_images = bool(config.get("log_images", False))
         self._want_images = False       # set for the duration of a train_step(..., images=True)
+        # `val_freq: K` with `val_csv`: the part IoU of a validation csv after every K-th step (``validate``)
+        self.val_freq = int(config.get("val_freq", 0) or 0)
+        self._val, self._val_logs = None, OrderedDict()
+        if self.val_freq > 0:
+            self._init_validation()
         self._img = None                # side stream, colour tables, writer: created by the first image step
         self._img_hold = None           # (sources, event) of canvases still being rendered: released when the next step begins
 
@@ -1717,7 +1767,43 @@ class Trainer(object):
         out = OrderedDict()
         for k, v in self.log_ops.items():
             out[k] = float(v) if torch.is_tensor(v) else float(v)
+        out.update(getattr(self, "_val_logs", {}))      # val/overall, val/iou_<label> of the most recent validation (`val_freq`)
         return out
+
+    # ------------------------------------------------------------------ periodic validation (`val_freq`, `val_csv`)
+    def _init_validation(self):
+        """On rank 0, the validation set: decoded once, kept as pinned uint8 (the refusals were checked when __init__ began)."""
+        cfg = self.config
+        check_validation_config(cfg)
+        if self.rank != 0:              # rank 0 validates; the others meet it at the next step's first collective
+            return
+        from . import data as _data
+        from . import evalutil
+        vs = _data.ValidationSet(cfg)
+        ev = evalutil.PartEvaluator(self.model, int(cfg.get("eval_n_labels", 32)), lut=cfg.get("eval_label_lut"))
+        self._val = {"set": vs, "evaluator": ev}
+
+    @torch.no_grad()
+    def validate(self):
+        """Part IoU (evalutil.PartEvaluator: ``model.segment`` + ups_part_confusion) of the validation set under the CURRENT
+        weights -> {"val/overall", "val/iou_<label>", "val/steps_done"}, also kept for ``fetch_logs``.  Runs on the main stream
+        between two steps, draws nothing from the trainer's generators and touches neither optimizer nor Lagrangian / EMA state: the training
+        trajectory is the same with and without it.  One host synchronisation (the copy of the counts)."""
+        if self._val is None:
+            return OrderedDict()
+        vs, ev = self._val["set"], self._val["evaluator"]
+        ev.reset()
+        chunk = 2 * int(self.config["batch_size"])
+        for c0 in range(0, len(vs), chunk):
+            c1 = min(len(vs), c0 + chunk)
+            ev.update(vs.float_views(c0, c1, self.device), vs.labels[c0:c1])
+        res = ev.result()
+        logs = OrderedDict([("val/overall", res["overall"])])
+        for g in sorted(res["iou"]):
+            logs["val/iou_{}".format(g)] = res["iou"][g]
+        logs["val/steps_done"] = self.global_step       # which weights the numbers belong to: they stay in fetch_logs until the next report
+        self._val_logs = logs
+        return logs
 
     def iterate(self, batch_iterator, num_steps=None, log_fn=print):
         """edflow's session loop with its hooks.  LoggingHook cadence as cub/train/log.txt:221-860 shows it (an IntervalHook whose
@@ -1739,6 +1825,15 @@ class Trainer(object):
                 self._write_images(s)
             else:
                 self.train_step(batch)
+            # `val_freq`: after the K-th, 2K-th, ... step (global_step counts the steps done); on a step that logs, its lines carry the
+            # fresh numbers, on any other step the val/ keys get lines of their own
+            val_freq = getattr(self, "val_freq", 0)
+            val_now = val_freq > 0 and self.global_step % val_freq == 0 and self._val is not None
+            if val_now:
+                val = self.validate()
+                if not log_now:
+                    for k in sorted(val):
+                        log_fn("[INFO] [LoggingHook]: {}: {}".format(k, val[k]))
             if log_now:
                 interval = min(2 * interval, max(1, log_freq))
                 logs = self.fetch_logs()

@@ -1781,6 +1781,32 @@ def unpool_mix(hard, feat, pose_idx, app_idx, act_dtype):
     return out
 
 
+# --------------------------------------------------------------------------- part-IoU evaluation (csrc/evalparts.hip)
+def part_confusion(pred, gt_u8, P, G, lut=None, counts=None, invalid=None):
+    """counts[i,p,g] += #{pixels of image i with pred == p and lut[gt] == g} (ups_part_confusion; the statistic
+    evalutil.evaluate_from_counts takes).  pred [N,..] int64 (the arg-max map of part_softmax), gt_u8 [N,..] uint8 of the same shape,
+    lut [256] uint8 on the device or None (identity), 1 <= P, G <= 32.  counts [N,P,G] int32 (default: new zeros; given: added to --
+    a row-offset view of a larger buffer is fine), invalid [1] int32 (default: new zero): += the pixels with pred outside [0,P) or
+    a mapped label >= G, which are counted nowhere else.  Asynchronous on the current stream.  Returns counts."""
+    N = pred.shape[0]
+    if (pred.dtype != torch.int64 or gt_u8.dtype != torch.uint8 or pred.shape != gt_u8.shape or N == 0
+            or (lut is not None and (lut.dtype != torch.uint8 or lut.numel() != 256))):
+        raise L.UpsError("part_confusion: pred int64 and gt uint8 of one shape [N >= 1, ..], lut [256] uint8 (got {} {}, {} {}, lut {})"
+                         .format(tuple(pred.shape), pred.dtype, tuple(gt_u8.shape), gt_u8.dtype,
+                                 None if lut is None else (tuple(lut.shape), lut.dtype)))
+    if counts is None:
+        counts = torch.zeros((N, P, G), dtype=torch.int32, device=pred.device)
+    if invalid is None:
+        invalid = torch.zeros(1, dtype=torch.int32, device=pred.device)
+    if counts.dtype != torch.int32 or tuple(counts.shape) != (N, P, G) or invalid.dtype != torch.int32 or invalid.numel() != 1:
+        raise L.UpsError("part_confusion: counts [{},{},{}] int32 and invalid [1] int32 expected (got {} {}, {} {})".format(
+            N, P, G, tuple(counts.shape), counts.dtype, tuple(invalid.shape), invalid.dtype))
+    pred, gt_u8 = pred.contiguous(), gt_u8.contiguous()
+    L.call("ups_part_confusion", L.ptr(pred), L.ptr(gt_u8), L.ptr(lut), N, pred.numel() // N, P, G, L.ptr(counts), L.ptr(invalid),
+           L.stream())
+    return counts
+
+
 # --------------------------------------------------------------------------- training image logs (csrc/canvas.hip): uint8 canvases
 def canvas_grid(n, cols=None):
     """(rows, cols) of tf_batch_to_canvas for n tiles (re-derived, UNVERIFIED): cols=None -> the square grid of side ceil(sqrt(n)),

@@ -186,6 +186,13 @@ def evaluate(args):
     model = Model(cfg)
     it = Iterator(cfg, root, model)
     it.initialize(args.checkpoint)
+    if cfg.get("eval_on_device", False):
+        res = evaluate_on_device(model, batches_it, cfg, args.eval_batches)
+        odir = os.path.join(root, "eval", str(it.global_step))
+        os.makedirs(odir, exist_ok=True)
+        write_iou_files(res, odir, cfg, it.global_step)
+        print("[INFO] evaluation tables written to", odir)
+        return res
     keys = cfg.get("fetch_output_keys", ["out_parts_hard", "out_parts_soft", "generated", "m0_sample"])
     outs, ins, gts = {k: [] for k in keys}, {"view0": [], "view1": []}, []
     for bi, batch in enumerate(batches_it):
@@ -205,16 +212,55 @@ def evaluate(args):
     with open(os.path.join(odir, "model_outputs.p"), "wb") as f:
         pickle.dump(data, f)
     if gts:
-        res = evalutil.evaluate_parts(data["outputs"]["out_parts_hard"], np.concatenate(gts))
-        with open(os.path.join(odir, "iou.yml"), "w") as f:
-            yaml.safe_dump({"iou": {int(k): float(v) for k, v in res["iou"].items()}, "overall": res["overall"],
-                            "pooled_iou": {int(k): float(v) for k, v in res["pooled"].items()},
-                            "best_remapping": {int(k): int(v) for k, v in res["mapping"].items()}}, f)
-        # part_ious.csv / mean_part_ios.csv / best_remapping.yml as eval_01.py:355-383 writes them
-        names = cfg.get("part_names")
-        evalutil.write_eval_tables(res, odir, it.global_step, {int(k): str(v) for k, v in names.items()} if names else None)
+        gt = np.concatenate(gts)
+        if cfg.get("eval_label_lut"):       # (the same table the device route hands to the kernel)
+            gt = evalutil.lut_array(cfg["eval_label_lut"])[evalutil.labels_u8(gt)]
+        write_iou_files(evalutil.evaluate_parts(data["outputs"]["out_parts_hard"], gt), odir, cfg, it.global_step)
     print("[INFO] evaluation outputs written to", odir)
     return data
+
+
+def write_iou_files(res, odir, cfg, global_step):
+    """iou.yml, and part_ious.csv / mean_part_ios.csv / best_remapping.yml as eval_01.py:355-383 writes them, from the result dict of
+    ``evalutil.evaluate_parts`` or ``evalutil.evaluate_from_counts``."""
+    from . import evalutil
+    with open(os.path.join(odir, "iou.yml"), "w") as f:
+        yaml.safe_dump({"iou": {int(k): float(v) for k, v in res["iou"].items()}, "overall": res["overall"],
+                        "pooled_iou": {int(k): float(v) for k, v in res["pooled"].items()},
+                        "best_remapping": {int(k): int(v) for k, v in res["mapping"].items()}}, f)
+    names = cfg.get("part_names")
+    evalutil.write_eval_tables(res, odir, global_step, {int(k): str(v) for k, v in names.items()} if names else None)
+
+
+def evaluate_on_device(model, batches_it, cfg, eval_batches=None):
+    """``eval_on_device: True``: the part-IoU protocol without the generator and without the outputs on the host.  ``view0`` of every
+    batch goes through ``model.segment`` (pose path only) and ups_part_confusion (``evalutil.PartEvaluator``); one copy of the
+    counts at the end.  ``eval_n_labels`` (default 32, the kernel's table; more counts on the host) and ``eval_label_lut``
+    {raw: new} describe the labels.  Batches without ``gt_segmentation`` are a ValueError: this route computes nothing else."""
+    import numpy as np
+    from . import evalutil
+    ev = evalutil.PartEvaluator(model, int(cfg.get("eval_n_labels", 32)), lut=cfg.get("eval_label_lut"))
+    views, gts, held = [], [], 0
+
+    def flush():
+        ev.update(torch.cat(views, 0), np.concatenate(gts))
+        del views[:], gts[:]
+    for bi, batch in enumerate(batches_it):
+        if eval_batches is not None and bi >= eval_batches:
+            break
+        if "gt_segmentation" not in batch:
+            raise ValueError("eval_on_device: the batches carry no `gt_segmentation` (set data_gt_segmentation_column; without "
+                             "ground truth there is nothing this route computes -- run -e without eval_on_device)")
+        valid = batch.get("valid")
+        views.append(torch.as_tensor(batch["view0"])[:valid])
+        gts.append(evalutil.labels_u8(np.asarray(batch["gt_segmentation"]))[:valid])
+        held += len(gts[-1])
+        if held >= 2 * int(cfg["batch_size"]):       # a whole pass of segment: two batches' view0, nothing padded
+            flush()
+            held = 0
+    if views:
+        flush()
+    return ev.result()
 
 
 class SyntheticTransfer(object):
