@@ -468,6 +468,31 @@ int ups_canvas_first_item(const float* m, const float* hard, const uint32_t* bit
 int ups_gather_views(const uint8_t* images, int64_t n_images, const int32_t* plan, int32_t B, int32_t S, float* view0, float* view1,
                      float* target, void* stream);
 
+/* ---------------------------------------------------------------- device-side augmentation of the training data (csrc/augment.hip)
+ * AugmentedPair2's appearance and shape pipelines (cub/code/data/data.py:57-154, restated in augment.py) executed on the uint8 store of
+ * ups_gather_views from realisations the HOST has drawn (augment.draw_appearance / draw_shape): one record of
+ * ups_augment_record_words() int32 words per output image (layout: the R_* constants of csrc/augment.hip = data.REC_*).  Added without
+ * a new UPS_ABI_VERSION: no struct changed, and a binding that expects these symbols fails to load an older library by name.
+ *   images  [n_images, S, S, 3] uint8;   records [n, words] int32, DEVICE, n = 3 B (target given) or 2 B: image r * B + b is role r
+ *   (0 view0, 1 view1, 2 target) of item b;   luts [2, 256] uint8, DEVICE: T_in, T_mid (the host's truncating uint8 round trips);
+ *   field [n_fields, 2, S, S] fp32 from ups_augment_field (dx, dy), may be NULL when n_fields == 0;
+ *   scratch_a, scratch_b [n, S, S, 3] uint8 (caller-owned, overwritten);   view0, view1, target [B, S, S, 3] fp32, target may be NULL.
+ * value chain: store byte (plan flips) -> T_in -> filter, three colour ops, gray, perm -> T_mid (records with the `mid` flag) ->
+ * hflip, affine warp -> grid or elastic warp -> v * 2 / 255 - 1.  Every warp: fp32 source coordinates, clamped to [0, S-1], floored,
+ * a + (b - a) * f along x then y, rintf and clip to uint8.  Bit-equal to tests/devaug_ref.py's float32 NumPy restatement.
+ * passes: bit 0 pass 1 (-> scratch_a), bit 1 pass 2 (scratch_a -> scratch_b), bit 2 pass 3 (scratch_b -> views); 7 runs all (the
+ * single passes exist for timing).  UPS_E_ARG, nothing launched: B <= 0, S <= 0, n_images <= 0, n_fields < 0, a NULL required pointer,
+ * passes outside 1..7, 3 B > 65535.  A record with a source image, field index or op code out of range reads nothing and gives a NaN image. */
+int32_t ups_augment_record_words(void);
+int ups_augment_views(const uint8_t* images, int64_t n_images, const int32_t* records, const uint8_t* luts, const float* field,
+                      int32_t n_fields, int32_t B, int32_t S, uint8_t* scratch_a, uint8_t* scratch_b, float* view0, float* view1,
+                      float* target, int32_t passes, void* stream);
+/* The elastic displacement fields: noise [n_fields, 2, S, S] fp32 -> field, through tmp of the same size.  Separable Gaussian of 401
+ * taps (weights: DEVICE, fp32, sigma 50 / radius 200, normalised in float64 on the host), scipy `reflect` border repeated as often as the
+ * radius needs, axis 0 first, the accumulator starting at 0 and adding taps 0 .. 400 in order, contraction off.
+ * UPS_E_ARG: n_fields <= 0, S <= 0, a NULL pointer, 2 n_fields > 65535. */
+int ups_augment_field(const float* noise, const float* weights, int32_t n_fields, int32_t S, float* tmp, float* field, void* stream);
+
 /* ---------------------------------------------------------------- part-IoU evaluation (csrc/evalparts.hip)
  * The per-image joint histogram of inferred part and ground-truth label: the sufficient statistic of the protocol of
  * eval_01.py:229-383 (evalutil.evaluate_from_counts).

@@ -16,6 +16,19 @@ device-fed figures do not.
 Prints one JSON line per row.
 
     python tools/bench_data.py [--images 512] [--repeats 3] [--skip-model] > profiles/bench_data.jsonl
+
+`--augment` measures the device-side augmentation instead (yaml `data_augment_on_device`; csrc/augment.hip), with the same PNGs and
+rules, and its rows are APPENDED to the file:
+(d) aug_kernel    event time per launch of each of the three passes of ups_augment_views and of ups_augment_field at (B, S) = (64, 128)
+                  and (16, 256): records drawn by data.fill_aug_plan with both switches on (the mix of ops a training batch has),
+                  rotating record / output sets;
+(e) aug_plan      host time of data.fill_aug_plan per batch (it runs in the iterator's thread);
+(f) aug_batches   batches per second of data.batches (8 workers) with both switches on -- the only route without the switch --
+                  against data.device_batches' augmented route;
+(g) aug_training  Trainer.iterate img/s at batch 64, bf16, alternated readings, fed by the host iterator with augmentation, the device
+                  iterator with augmentation and the device iterator without.
+
+    python tools/bench_data.py --augment [--images 512] [--repeats 3] [--skip-model] >> profiles/bench_data.jsonl
 """
 import argparse
 import itertools
@@ -176,6 +189,139 @@ def training_rows(dcfg, repeats, steps_host, steps_dev):
     emit(row)
 
 
+AUG = {"data_augment_appearance": True, "data_augment_shape": True, "data_on_device": True, "data_augment_on_device": True}
+
+
+def _event_us(launch, n, repeats):
+    ts = []
+    for _ in range(repeats):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for k in range(n):
+            launch(k)
+        e1.record()
+        torch.cuda.synchronize()
+        ts.append(e0.elapsed_time(e1) * 1e3 / n)
+    return ts
+
+
+def aug_kernel_rows(dcfg, iters, repeats, sets_mib):
+    from upsparts_amd import data, lib as L
+    dev = torch.device("cuda:0")
+    for B, S in ((64, 128), (16, 256)):
+        ds = data.AugmentedPair2(dict(dcfg, spatial_size=S, batch_size=B, **AUG))
+        N = len(ds)
+        store = torch.from_numpy(data.build_u8_store(ds)).to(dev)
+        luts, weights = torch.from_numpy(data.aug_luts()).to(dev), torch.from_numpy(data.gauss_weights()).to(dev)
+        out_bytes = 3 * B * S * S * 3 * 4
+        nsets = max(3, -(-sets_mib * (1 << 20) // out_bytes))
+        rng = np.random.RandomState(S)
+        sets, plan_s, n_els = [], [], []
+        for k in range(nsets):
+            recs, noise = np.zeros((3, B, data.REC_WORDS), dtype=np.int32), np.zeros((2 * B, 2, S, S), dtype=np.float32)
+            t0 = time.perf_counter()
+            n_el = data.fill_aug_plan(ds, rng.permutation(N)[:B], recs, noise)
+            plan_s.append(time.perf_counter() - t0)
+            n_els.append(n_el)
+            fld = torch.from_numpy(noise[:max(n_el, 1)]).to(dev)
+            sets.append((torch.from_numpy(recs).to(dev), n_el, fld, torch.empty_like(fld), torch.empty_like(fld),
+                         torch.empty((2, 3 * B, S, S, 3), dtype=torch.uint8, device=dev),
+                         [torch.empty((B, S, S, 3), dtype=torch.float32, device=dev) for _ in range(3)]))
+
+        def views(k, passes):
+            recs, n_el, _, _, fld, scr, (v0, v1, vt) = sets[k % nsets]
+            L.call("ups_augment_views", L.ptr(store), N, L.ptr(recs), L.ptr(luts), L.ptr(fld), n_el, B, S, L.ptr(scr[0]), L.ptr(scr[1]),
+                   L.ptr(v0), L.ptr(v1), L.ptr(vt), passes, L.stream())
+
+        def field(k):
+            _, n_el, noise, tmp, fld, _, _ = sets[k % nsets]
+            if n_el:
+                L.call("ups_augment_field", L.ptr(noise), L.ptr(weights), n_el, S, L.ptr(tmp), L.ptr(fld), L.stream())
+        for k in range(nsets):
+            field(k)
+            views(k, 7)
+        torch.cuda.synchronize()
+        n = max(iters, 2 * nsets)
+        common = {"B": B, "S": S, "store_images": N, "record_sets": nsets, "launches_per_reading": n,
+                  "elastic_fields_per_batch_mean": round(float(np.mean(n_els)), 2), "note": NOTE}
+        for name, fn in (("pass 1: gather + T_in + filter + colour chain", lambda k: views(k, 1)),
+                         ("pass 2: T_mid + hflip + affine", lambda k: views(k, 2)),
+                         ("pass 3: grid / elastic warp + normalise", lambda k: views(k, 4)),
+                         ("ups_augment_views, all three passes", lambda k: views(k, 7)),
+                         ("ups_augment_field (both axes; sets without an elastic record launch nothing)", field)):
+            ts = _event_us(fn, n, repeats)
+            emit(dict(common, row="aug_kernel", launch=name, us=round(min(ts), 2), us_all=[round(t, 2) for t in ts]))
+        emit(dict(common, row="aug_plan", what="host time of data.fill_aug_plan per batch, both switches on",
+                  ms=round(1e3 * min(plan_s), 3), ms_mean=round(1e3 * float(np.mean(plan_s)), 3), ms_max=round(1e3 * max(plan_s), 3)))
+        del sets, store
+        torch.cuda.empty_cache()
+
+
+def aug_batch_rows(dcfg, repeats, n_host, n_dev):
+    from upsparts_amd import data
+    dev = torch.device("cuda:0")
+    cfg = dict(dcfg, spatial_size=128, batch_size=64, **AUG)
+    host, devr = [], []
+    for _ in range(repeats):
+        it = data.batches(data.AugmentedPair2(cfg), 64)
+        next(it)
+        t0 = time.perf_counter()
+        for _ in range(n_host):
+            next(it)
+        host.append(n_host / (time.perf_counter() - t0))
+        del it
+    it = data.device_batches(data.AugmentedPair2(cfg), 64, dev)
+    for _ in range(8):
+        next(it)
+    for _ in range(repeats):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(n_dev):
+            next(it)
+        torch.cuda.synchronize()
+        devr.append(n_dev / (time.perf_counter() - t0))
+    emit({"row": "aug_batches", "B": 64, "S": 128, "augment": "appearance + shape", "host_batches_per_s": round(max(host), 2),
+          "host_all": [round(v, 2) for v in host], "host_workers": 8, "host_batches_per_reading": n_host,
+          "device_batches_per_s": round(max(devr), 1), "device_all": [round(v, 1) for v in devr], "device_batches_per_reading": n_dev,
+          "device_ms_per_batch": round(1e3 / max(devr), 3), "note": NOTE})
+
+
+def aug_training_rows(dcfg, repeats, steps_host, steps_dev):
+    from upsparts_amd import configs, data
+    from upsparts_amd.model import TrainModel, Trainer
+    dev = torch.device("cuda:0")
+    B, S = 64, 128
+    cfg = configs.BENCH_CONFIGS["cub128p10"][0](B)
+    cfg["precision"] = "bf16"
+    cfg.update(dcfg)
+    model = TrainModel(cfg, device=dev, seed=0)
+    tr = Trainer(cfg, None, model)
+    g = torch.Generator().manual_seed(1234)
+    fixed = {k: (torch.rand(B, S, S, 3, generator=g) * 2 - 1).to(dev) for k in ("view0", "view1", "view0_target")}
+    aug = dict(cfg, **AUG)
+    feeds = {"host_augmented": (data.batches(data.AugmentedPair2(aug), B), steps_host),
+             "device_augmented": (data.device_batches(data.AugmentedPair2(aug), B, dev), steps_dev),
+             "device_plain": (data.device_batches(data.AugmentedPair2(cfg), B, dev), steps_dev)}
+    quiet = lambda line: None
+    tr.iterate(itertools.islice(itertools.repeat(fixed), 8), num_steps=tr.global_step + 8, log_fn=quiet)          # warm-up
+    rates = {k: [] for k in feeds}
+    for _ in range(repeats):
+        for name, (it, n) in feeds.items():                  # alternated
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            tr.iterate(itertools.islice(it, n), num_steps=tr.global_step + n, log_fn=quiet)
+            torch.cuda.synchronize()
+            rates[name].append(n * B / (time.perf_counter() - t0))
+    row = {"row": "aug_training", "config": "cub128p10", "B": B, "S": S, "precision": "bf16",
+           "steps_per_reading": {k: n for k, (_, n) in feeds.items()}}
+    for k, v in rates.items():
+        row[k + "_img_per_s"] = round(sum(v) / len(v), 1)
+        row[k + "_all"] = [round(x, 1) for x in v]
+        row[k + "_spread"] = round(max(v) - min(v), 1)
+    row["note"] = NOTE
+    emit(row)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--images", type=int, default=512)
@@ -188,9 +334,19 @@ def main():
     ap.add_argument("--steps-host", type=int, default=12)
     ap.add_argument("--steps", type=int, default=48)
     ap.add_argument("--skip-model", action="store_true")
+    ap.add_argument("--augment", action="store_true", help="the rows of the device-side augmentation (appended to the file) instead")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "bench_data.py times the GPU: no device"
     import upsparts_amd  # noqa: F401
+    if args.augment:
+        emit({"row": "about", "rows": "augment", "device": torch.cuda.get_device_name(0), "images": args.images, "note": NOTE})
+        with tempfile.TemporaryDirectory() as tmp:
+            dcfg = write_pngs(tmp, args.images)
+            aug_kernel_rows(dcfg, args.iters, max(args.repeats, 5), args.sets_mib)
+            aug_batch_rows(dcfg, args.repeats, args.host_batches, args.device_batches)
+            if not args.skip_model:
+                aug_training_rows(dcfg, args.repeats, args.steps_host, args.steps)
+        return
     emit({"row": "about", "device": torch.cuda.get_device_name(0), "images": args.images, "note": NOTE})
     kernel_rows(args.iters, max(args.repeats, 5), args.sets_mib, args.store_mib)
     with tempfile.TemporaryDirectory() as tmp:

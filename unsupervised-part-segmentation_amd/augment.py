@@ -30,10 +30,13 @@ def _median3(img):
     return ndimage.median_filter(img, size=(3, 3, 1), mode="nearest")
 
 
+def _bc_table(alpha, beta):
+    """RandomBrightnessContrast, brightness_by_max=True: x * alpha + beta * 255 as a 256-entry uint8 table."""
+    return np.clip(np.arange(256, dtype=np.float32) * alpha + beta * 255.0, 0, 255).astype(np.uint8)
+
+
 def _brightness_contrast(img, alpha, beta):
-    """RandomBrightnessContrast, brightness_by_max=True: x * alpha + beta * 255 through a 256-entry table."""
-    lut = np.clip(np.arange(256, dtype=np.float32) * alpha + beta * 255.0, 0, 255).astype(np.uint8)
-    return lut[img]
+    return _bc_table(alpha, beta)[img]
 
 
 def _rgb_shift(img, shifts):
@@ -80,35 +83,75 @@ def _to_gray(img):
     return np.repeat(np.clip(g, 0, 255).astype(np.uint8)[..., None], 3, -1)
 
 
+# A realisation is DRAWN first and BUILT second: ``draw_*`` consume the generator and return plain records (a tuple whose first entry
+# names the op), ``build_*`` turn records into uint8 -> uint8 image functions.  The device path (data.fill_aug_plan, csrc/augment.hip)
+# executes the same records, so both paths see the same draws.
+#   ("median",) ("box",) ("gray",) ("hflip",)      no parameters
+#   ("bc", table)                                   the uint8 [256] table of _bc_table
+#   ("rgb", [s0, s1, s2])   ("hsv", dh, ds, dv)   ("perm", [i0, i1, i2])
+#   ("affine", inv)                                 the inverse 2x3 float32 matrix of _shift_scale_rotate
+#   ("grid", jy, jx)                                float32 [4,4] each
+#   ("elastic", inv, ndx, ndy)                      inverse 2x3 float32 matrix, the two noise fields float32 [h,w] in [-1, 1)
 def _draw_color_op(rng):
     """One of RandomBrightnessContrast / RGBShift / HueSaturationValue (equal weights), with its parameters."""
     k = rng.randint(3)
     if k == 0:
         a, b = 1.0 + rng.uniform(-0.2, 0.2), rng.uniform(-0.2, 0.2)
-        return lambda im: _brightness_contrast(im, a, b)
+        return ("bc", _bc_table(a, b))
     if k == 1:
-        sh = [int(round(rng.uniform(-20, 20))) for _ in range(3)]
-        return lambda im: _rgb_shift(im, sh)
+        return ("rgb", [int(round(rng.uniform(-20, 20))) for _ in range(3)])
     dh, ds, dv = int(round(rng.uniform(-20, 20))), int(round(rng.uniform(-30, 30))), int(round(rng.uniform(-20, 20)))
-    return lambda im: _hue_sat_val(im, dh, ds, dv)
+    return ("hsv", dh, ds, dv)
+
+
+def draw_appearance(rng, p=0.9):
+    """Draw one realisation of the appearance pipeline: a list of records."""
+    recs = []
+    if rng.rand() >= p:
+        return recs
+    if rng.rand() < 0.5:
+        recs.append(("median",) if rng.randint(2) == 0 else ("box",))
+    for _ in range(3):
+        if rng.rand() < 0.8:
+            recs.append(_draw_color_op(rng))
+    if rng.rand() < 0.1:
+        recs.append(("gray",))
+    if rng.rand() < 0.3:
+        recs.append(("perm", rng.permutation(3)))
+    return recs
+
+
+def _build_appearance_op(rec):
+    kind = rec[0]
+    if kind == "median":
+        return _median3
+    if kind == "box":
+        return _box3
+    if kind == "bc":
+        lut = rec[1]
+        return lambda im: lut[im]
+    if kind == "rgb":
+        sh = rec[1]
+        return lambda im: _rgb_shift(im, sh)
+    if kind == "hsv":
+        dh, ds, dv = rec[1:]
+        return lambda im: _hue_sat_val(im, dh, ds, dv)
+    if kind == "gray":
+        return _to_gray
+    if kind == "perm":
+        perm = rec[1]
+        return lambda im: np.ascontiguousarray(im[..., perm])
+    raise ValueError("unknown appearance record {!r}".format(kind))
+
+
+def build_appearance(recs):
+    """Records of ``draw_appearance`` -> a list of uint8 -> uint8 image functions."""
+    return [_build_appearance_op(r) for r in recs]
 
 
 def appearance_ops(rng, p=0.9):
     """Draw one realisation of the appearance pipeline: a list of uint8 -> uint8 image functions."""
-    ops = []
-    if rng.rand() >= p:
-        return ops
-    if rng.rand() < 0.5:
-        ops.append(_median3 if rng.randint(2) == 0 else _box3)
-    for _ in range(3):
-        if rng.rand() < 0.8:
-            ops.append(_draw_color_op(rng))
-    if rng.rand() < 0.1:
-        ops.append(_to_gray)
-    if rng.rand() < 0.3:
-        perm = rng.permutation(3)
-        ops.append(lambda im: np.ascontiguousarray(im[..., perm]))
-    return ops
+    return build_appearance(draw_appearance(rng, p))
 
 
 # -------------------------------------------------------------------------------------------------------------- geometric
@@ -126,24 +169,32 @@ def _affine_grid(h, w, mat):
     return mat[1, 0] * xx + mat[1, 1] * yy + mat[1, 2], mat[0, 0] * xx + mat[0, 1] * yy + mat[0, 2]
 
 
-def _shift_scale_rotate(rng, h, w):
+def _draw_shift_scale_rotate(rng, h, w):
     angle = np.deg2rad(rng.uniform(-25, 25))
     scale = 1.0 + rng.uniform(-0.25, 0.25)
     dx, dy = rng.uniform(-0.0625, 0.0625) * w, rng.uniform(-0.0625, 0.0625) * h
     cx, cy = w / 2.0, h / 2.0
     c, s = np.cos(angle) * scale, np.sin(angle) * scale
     fwd = np.array([[c, s, (1 - c) * cx - s * cy + dx], [-s, c, s * cx + (1 - c) * cy + dy], [0, 0, 1]], np.float64)
-    inv = np.linalg.inv(fwd)[:2].astype(np.float32)       # cv2.warpAffine inverts the forward matrix the same way
+    return ("affine", np.linalg.inv(fwd)[:2].astype(np.float32))       # cv2.warpAffine inverts the forward matrix the same way
+
+
+def _affine_op(inv, h, w):
     ys, xs = _affine_grid(h, w, inv)
     return lambda im: _warp(im, ys, xs)
 
 
-def _piecewise_affine(rng, h, w, rows=4, cols=4):
-    """imgaug PiecewiseAffine: a rows x cols control grid whose points move by N(0, scale * size), scale ~ U(.03, .05).
-    The displacement between control points is interpolated bilinearly here (imgaug triangulates the grid)."""
+def _draw_piecewise_affine(rng, h, w, rows=4, cols=4):
     scale = rng.uniform(0.03, 0.05)
     jy = rng.normal(0, scale, (rows, cols)).astype(np.float32) * h
     jx = rng.normal(0, scale, (rows, cols)).astype(np.float32) * w
+    return ("grid", jy, jx)
+
+
+def _grid_op(jy, jx, h, w):
+    """imgaug PiecewiseAffine: a rows x cols control grid whose points move by N(0, scale * size), scale ~ U(.03, .05).
+    The displacement between control points is interpolated bilinearly here (imgaug triangulates the grid)."""
+    rows, cols = jy.shape
     gy, gx = np.mgrid[0:h, 0:w].astype(np.float32)
     cy, cx = gy * (rows - 1) / max(h - 1, 1), gx * (cols - 1) / max(w - 1, 1)
     dy = ndimage.map_coordinates(jy, [cy, cx], order=1, mode="nearest")
@@ -152,9 +203,7 @@ def _piecewise_affine(rng, h, w, rows=4, cols=4):
     return lambda im: _warp(im, ys, xs)
 
 
-def _elastic(rng, h, w, alpha=1.0, sigma=50.0, alpha_affine=50.0):
-    """albumentations ElasticTransform: a random affine from three jittered anchor points, then a Gaussian-smoothed random
-    displacement field of amplitude alpha."""
+def _draw_elastic(rng, h, w, alpha_affine=50.0):
     c = np.float32([w, h]) / 2.0
     sq = min(h, w) // 3
     p1 = np.float32([c + sq, [c[0] + sq, c[1] - sq], c - sq])
@@ -162,24 +211,67 @@ def _elastic(rng, h, w, alpha=1.0, sigma=50.0, alpha_affine=50.0):
     a = np.concatenate([p1, np.ones((3, 1), np.float32)], 1)
     fwd = np.linalg.solve(a.astype(np.float64), p2.astype(np.float64)).T          # 2x3: p2 = fwd @ (p1, 1)
     inv = np.linalg.inv(np.vstack([fwd, [0, 0, 1]]))[:2].astype(np.float32)
+    ndx = rng.rand(h, w).astype(np.float32) * 2 - 1
+    ndy = rng.rand(h, w).astype(np.float32) * 2 - 1
+    return ("elastic", inv, ndx, ndy)
+
+
+def _elastic_op(inv, ndx, ndy, h, w, alpha=1.0, sigma=50.0):
+    """albumentations ElasticTransform: a random affine from three jittered anchor points, then a Gaussian-smoothed random
+    displacement field of amplitude alpha."""
     ys, xs = _affine_grid(h, w, inv)
-    dx = ndimage.gaussian_filter(rng.rand(h, w).astype(np.float32) * 2 - 1, sigma) * alpha
-    dy = ndimage.gaussian_filter(rng.rand(h, w).astype(np.float32) * 2 - 1, sigma) * alpha
+    dx = ndimage.gaussian_filter(ndx, sigma) * alpha
+    dy = ndimage.gaussian_filter(ndy, sigma) * alpha
     ys, xs = ys + dy, xs + dx
     return lambda im: _warp(im, ys, xs)
 
 
-def shape_ops(rng, h, w, p=0.9):
-    ops = []
+def draw_shape(rng, h, w, p=0.9):
+    """Draw one realisation of the shape pipeline for h x w images: a list of records."""
+    recs = []
     if rng.rand() >= p:
-        return ops
+        return recs
     if rng.rand() < 0.3:
-        ops.append(lambda im: np.ascontiguousarray(im[:, ::-1]))
+        recs.append(("hflip",))
     if rng.rand() < 0.3:
-        ops.append(_shift_scale_rotate(rng, h, w))
+        recs.append(_draw_shift_scale_rotate(rng, h, w))
     if rng.rand() < 0.3:
-        ops.append(_piecewise_affine(rng, h, w) if rng.randint(2) == 0 else _elastic(rng, h, w))
-    return ops
+        recs.append(_draw_piecewise_affine(rng, h, w) if rng.randint(2) == 0 else _draw_elastic(rng, h, w))
+    return recs
+
+
+def _build_shape_op(rec, h, w):
+    kind = rec[0]
+    if kind == "hflip":
+        return lambda im: np.ascontiguousarray(im[:, ::-1])
+    if kind == "affine":
+        return _affine_op(rec[1], h, w)
+    if kind == "grid":
+        return _grid_op(rec[1], rec[2], h, w)
+    if kind == "elastic":
+        return _elastic_op(rec[1], rec[2], rec[3], h, w)
+    raise ValueError("unknown shape record {!r}".format(kind))
+
+
+def _shift_scale_rotate(rng, h, w):
+    return _build_shape_op(_draw_shift_scale_rotate(rng, h, w), h, w)
+
+
+def _piecewise_affine(rng, h, w):
+    return _build_shape_op(_draw_piecewise_affine(rng, h, w), h, w)
+
+
+def _elastic(rng, h, w):
+    return _build_shape_op(_draw_elastic(rng, h, w), h, w)
+
+
+def build_shape(recs, h, w):
+    """Records of ``draw_shape`` -> a list of uint8 -> uint8 image functions."""
+    return [_build_shape_op(r, h, w) for r in recs]
+
+
+def shape_ops(rng, h, w, p=0.9):
+    return build_shape(draw_shape(rng, h, w, p), h, w)
 
 
 # ------------------------------------------------------------------------------------------------------------ entry points

@@ -12,6 +12,11 @@ import copy
 #   data_cache             path of an on-disk copy of that store (<path>.npy + <path>.json), rebuilt whenever the csv or the size changes
 #   data_on_device_max_gb  refuse (ValueError) a store of more than this many GB (10^9 bytes)
 DATA_ON_DEVICE = {"data_on_device": False, "data_cache": None, "data_on_device_max_gb": 16}
+# ... and the switch that lets that path run AugmentedPair2's `data_augment_appearance` / `data_augment_shape` on the device
+# (data.device_batches' augmented route, csrc/augment.hip): the host iterator's draws, pixels within two uint8 levels of its pixels
+# (docs/design/surroundings.md 8c) -- a different promise from the plain path's "same bits", hence a key of its own, in a table of its
+# own beside the three above.
+DATA_AUGMENT_ON_DEVICE = {"data_augment_on_device": False}
 
 
 def _stair(start, start_value, step_size, stair_factor, cmin, cmax):

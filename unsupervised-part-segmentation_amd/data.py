@@ -22,7 +22,10 @@ step.  ``preprocess_image`` is ``uint8 -> / 127.5 - 1``, so nothing is lost by d
 ``[N,S,S,3]`` (``build_u8_store``, optionally cached on disk under ``data_cache``) and keeping it in device memory.
 ``device_batches`` then draws the SAME pairs, flips and order as ``batches`` -- ``StochasticPairs.plan_example`` is the decision half
 of ``get_example`` -- sends B x 3 int32 per step and lets ``ups_gather_views`` (csrc/dataset.hip) write the float32 views: the same
-bits as the host path.  The albumentations-style augmentations and the label maps stay host-only.
+bits as the host path.  The label maps stay host-only; so do the albumentations-style augmentations unless
+``data_augment_on_device: True``: then ``fill_aug_plan`` draws the host iterator's realisations (``augment.draw_appearance`` /
+``draw_shape``) into one fixed-size record per output image and ``ups_augment_views`` (csrc/augment.hip) executes them -- the same
+draws, pixels within two uint8 levels of the host path's (two of the host's transforms run in double precision inside scipy).
 """
 import concurrent.futures as cf
 import hashlib
@@ -32,7 +35,7 @@ import os
 import numpy as np
 import torch
 
-from .configs import DATA_ON_DEVICE
+from .configs import DATA_AUGMENT_ON_DEVICE, DATA_ON_DEVICE
 
 
 def add_choices(character_ids):
@@ -237,11 +240,30 @@ def _cache_paths(cache):
     return npy, npy[:-len(".npy")] + ".json"
 
 
+AUG_KEYS = ("data_augment_appearance", "data_augment_shape")
+
+
+def augment_on_device(cfg):
+    return bool(cfg.get("data_augment_on_device", DATA_AUGMENT_ON_DEVICE["data_augment_on_device"]))
+
+
+def check_augment_on_device(cfg):
+    """``data_augment_on_device`` without ``data_on_device`` is a ValueError naming both keys (``runner.make_dataset`` asks before it
+    chooses the iterator; on the device path ``check_on_device`` refuses a dataset that is not an ``AugmentedPair2``)."""
+    if augment_on_device(cfg) and not cfg.get("data_on_device", DATA_ON_DEVICE["data_on_device"]):
+        raise ValueError("data_augment_on_device needs data_on_device: True (it is a route of the device-resident data path)")
+
+
 def check_on_device(dataset):
     """The refusals of ``data_on_device`` (ValueError, before a file or the device is touched): host-only transforms, and a store
-    that would not fit ``data_on_device_max_gb``.  There is no silent fall-back to the host path."""
+    that would not fit ``data_on_device_max_gb``.  There is no silent fall-back to the host path.  ``data_augment_on_device: True``
+    lifts the refusal of the two augmentation switches on an ``AugmentedPair2`` (the label maps stay refused)."""
     cfg = dataset.config
-    host_only = [k for k in ("data_augment_appearance", "data_augment_shape") if cfg.get(k, False)]
+    on_device = augment_on_device(cfg)
+    if on_device and not isinstance(dataset, AugmentedPair2):
+        raise ValueError("data_augment_on_device with data_on_device: {} is not an AugmentedPair2, the only dataset with "
+                         "data_augment_appearance / data_augment_shape".format(type(dataset).__name__))
+    host_only = [] if on_device else [k for k in AUG_KEYS if cfg.get(k, False)]
     if dataset.gt_column:
         host_only.append("data_gt_segmentation_column")
     if host_only:
@@ -307,6 +329,109 @@ def fill_plan(dataset, idx, plan):
 
 PLAN_RING = 4                   # pinned plan buffers in flight (a copy is waited for only when its buffer comes round again)
 
+# ---- the record of one output image of the augmented route: int32 words, floats by bit pattern (csrc/augment.hip R_*)
+REC_WORDS = 272
+REC_SRC, REC_FLIP, REC_MID, REC_FILTER, REC_COLOR, REC_CPAR, REC_GRAY, REC_PERM, REC_PIDX = 0, 1, 2, 3, 4, 7, 16, 17, 18
+REC_HFLIP, REC_AFFINE, REC_WARP, REC_FIELD, REC_AMAT, REC_EMAT, REC_JY, REC_JX, REC_BC = 21, 22, 23, 24, 32, 38, 44, 60, 76
+FILTER_CODE = {"median": 1, "box": 2}
+COLOR_CODE = {"bc": 1, "rgb": 2, "hsv": 3}
+GAUSS_SIGMA, GAUSS_RADIUS = 50.0, 200          # ElasticTransform's field: scipy's truncate = 4 sigma
+
+
+def aug_luts():
+    """uint8 [2,256]: T_in[u] = _to_u8(float32(u) / 127.5 - 1), what ``preprocess_image`` followed by a pipeline's first cast gives, and
+    T_mid[v] = _to_u8(_from_u8(v)), the round trip between the two pipelines -- augment.py's own expressions."""
+    from . import augment
+    u = np.arange(256, dtype=np.uint8)
+    return np.stack([augment._to_u8(u.astype(np.float32) / 127.5 - 1.0), augment._to_u8(augment._from_u8(u))])
+
+
+def gauss_weights(sigma=GAUSS_SIGMA, radius=GAUSS_RADIUS):
+    """The 2 * radius + 1 weights of scipy's gaussian_filter1d: float64, normalised, rounded to float32."""
+    x = np.arange(-radius, radius + 1, dtype=np.float64)
+    w = np.exp(-0.5 / (sigma * sigma) * x ** 2)
+    return (w / w.sum()).astype(np.float32)
+
+
+def write_appearance(rec, recs):
+    """The records of ``augment.draw_appearance`` into one image's int32 record (a NumPy view of REC_WORDS words)."""
+    slot = 0
+    for r in recs:
+        kind = r[0]
+        if kind in FILTER_CODE:
+            rec[REC_FILTER] = FILTER_CODE[kind]
+        elif kind in COLOR_CODE:
+            rec[REC_COLOR + slot] = COLOR_CODE[kind]
+            if kind == "bc":
+                rec[REC_BC + 64 * slot:REC_BC + 64 * (slot + 1)] = np.asarray(r[1], dtype=np.uint8).view(np.int32)
+            else:
+                rec[REC_CPAR + 3 * slot:REC_CPAR + 3 * slot + 3] = r[1] if kind == "rgb" else r[1:]
+            slot += 1
+        elif kind == "gray":
+            rec[REC_GRAY] = 1
+        elif kind == "perm":
+            rec[REC_PERM] = 1
+            rec[REC_PIDX:REC_PIDX + 3] = r[1]
+        else:
+            raise ValueError("unknown appearance record {!r}".format(kind))
+
+
+def write_shape(rec, recs, field):
+    """The records of ``augment.draw_shape`` into one image's record; `field` is the index of the realisation's elastic noise."""
+    f32 = rec.view(np.float32)
+    for r in recs:
+        kind = r[0]
+        if kind == "hflip":
+            rec[REC_HFLIP] = 1
+        elif kind == "affine":
+            rec[REC_AFFINE] = 1
+            f32[REC_AMAT:REC_AMAT + 6] = r[1].reshape(6)
+        elif kind == "grid":
+            rec[REC_WARP] = 1
+            f32[REC_JY:REC_JY + 16], f32[REC_JX:REC_JX + 16] = r[1].reshape(16), r[2].reshape(16)
+        elif kind == "elastic":
+            rec[REC_WARP], rec[REC_FIELD] = 2, field
+            f32[REC_EMAT:REC_EMAT + 6] = r[1].reshape(6)
+        else:
+            raise ValueError("unknown shape record {!r}".format(kind))
+
+
+def fill_aug_plan(dataset, idx, recs, noise):
+    """recs [3,B,REC_WORDS] int32 and noise [>= 2 B,2,S,S] float32 (NumPy views of pinned buffers) <- the examples `idx` of an
+    ``AugmentedPair2``: ``plan_example`` as in ``fill_plan``, then the generator of ``get_example`` --
+    RandomState([seed, i, draws[i], 7]), draws[i] read AFTER plan_example incremented it -- drawn in the host's order: A1 appearance of
+    view0, A2 appearance shared by view1 and the target, S3 shape shared by view0 and the target, S4 shape of view1, each kind only when
+    its switch is on.  Role r of item b is recs[r, b] (0 view0, 1 view1, 2 target).  Returns the number of elastic noise pairs written
+    (noise[e] = (dx, dy) of one elastic realisation, S3's shared by its two images).  Nothing per pixel happens here but those draws."""
+    from . import augment
+    n, S = len(dataset), int(dataset.size)
+    app, shp = bool(dataset.use_appearance_augmentation), bool(dataset.use_shape_augmentation)
+    recs[...] = 0
+    n_el = 0
+    for b, i in enumerate(idx):
+        i, j, fh, fv = dataset.plan_example(i)
+        if not (0 <= i < n and 0 <= j < n):
+            raise ValueError("data_on_device: example ({}, {}) is outside the store of {} images".format(i, j, n))
+        recs[:, b, REC_SRC] = (i, j, i)
+        recs[:, b, REC_FLIP] = int(fh) | (int(fv) << 1)
+        recs[:, b, REC_MID] = int(app and shp)
+        rng = np.random.RandomState([dataset.seed & 0x7fffffff, int(i), dataset.draws[int(i)], 7])
+        if app:
+            write_appearance(recs[0, b], augment.draw_appearance(rng))
+            a2 = augment.draw_appearance(rng)
+            write_appearance(recs[1, b], a2)
+            write_appearance(recs[2, b], a2)
+        if shp:
+            for roles in ((0, 2), (1,)):
+                drawn = augment.draw_shape(rng, S, S)
+                for r in drawn:
+                    if r[0] == "elastic":
+                        noise[n_el, 0], noise[n_el, 1] = r[2], r[3]
+                for role in roles:
+                    write_shape(recs[role, b], drawn, n_el)
+                n_el += any(r[0] == "elastic" for r in drawn)
+    return n_el
+
 
 def device_batches(dataset, batch_size, device, shuffle=True, seed=0, epochs=None):
     """``batches`` fed from device memory: the same ``RandomState(seed).permutation`` per epoch, the ragged last batch dropped, the
@@ -314,7 +439,10 @@ def device_batches(dataset, batch_size, device, shuffle=True, seed=0, epochs=Non
     batch.  Per step the host draws the plan (``fill_plan``), copies its B x 3 int32 from a pinned buffer (non-blocking) and launches
     ``ups_gather_views`` on the current stream of `device`; nothing is decoded and the host never waits for the device.
     The store is built (or loaded from ``data_cache``) and uploaded HERE, not at the first ``next()``: the refusals of
-    ``check_on_device`` and a missing image tree raise at construction."""
+    ``check_on_device`` and a missing image tree raise at construction.
+    With ``data_augment_on_device`` and one of ``data_augment_appearance`` / ``data_augment_shape`` the batches take the augmented
+    route (``fill_aug_plan`` + ``ups_augment_views``): the same order, partners, flips and draw counters, the host iterator's
+    realisations, pixels within two uint8 levels of the host iterator's."""
     from . import lib as L
     check_on_device(dataset)
     if batch_size < 1 or len(dataset) < batch_size:
@@ -323,6 +451,8 @@ def device_batches(dataset, batch_size, device, shuffle=True, seed=0, epochs=Non
     store = build_u8_store(dataset, cache=dataset.config.get("data_cache", DATA_ON_DEVICE["data_cache"]))
     images = torch.from_numpy(store).to(device)
     with_target = dataset.n_images == 3          # AugmentedPair2: view0_target = a copy of view0 (cub/code/data/data.py:164)
+    if augment_on_device(dataset.config) and (dataset.use_appearance_augmentation or dataset.use_shape_augmentation):
+        return _device_aug_batches(L, dataset, images, batch_size, device, shuffle, seed, epochs)
     return _device_batches(L, dataset, images, batch_size, device, shuffle, seed, epochs, with_target)
 
 
@@ -349,6 +479,50 @@ def _device_batches(L, dataset, images, batch_size, device, shuffle, seed, epoch
                        for key in (("view0", "view1", "view0_target") if with_target else ("view0", "view1"))}
                 L.call("ups_gather_views", L.ptr(images), N, L.ptr(plan), batch_size, S, L.ptr(out["view0"]), L.ptr(out["view1"]),
                        L.ptr(out.get("view0_target")), L.stream())
+            yield out
+        ep += 1
+
+
+def _device_aug_batches(L, dataset, images, batch_size, device, shuffle, seed, epochs):
+    """The augmented route of ``device_batches``.  Pinned ring buffers hold the records [3,B,REC_WORDS] and the elastic noise
+    [2 B,2,S,S] (at most two elastic realisations per example); both are copied non-blocking and the host never waits for the device.
+    The uint8 scratch of the three passes, the device copy of the noise and the field buffers are allocated once and reused on the
+    iterator's stream; records and views are fresh per batch."""
+    N, S, B = images.shape[0], images.shape[1], batch_size
+    if L.load().ups_augment_record_words() != REC_WORDS:
+        raise L.UpsError("ups_augment_record_words() = {} but data.REC_WORDS = {}: rebuild the library".format(
+            L.load().ups_augment_record_words(), REC_WORDS))
+    rng = np.random.RandomState(seed)
+    shape = bool(dataset.use_shape_augmentation)
+    ring = [torch.zeros((3, B, REC_WORDS), dtype=torch.int32).pin_memory() for _ in range(PLAN_RING)]
+    nring = [torch.zeros((2 * B if shape else 1, 2, S, S), dtype=torch.float32).pin_memory() for _ in range(PLAN_RING)]
+    copied = [None] * PLAN_RING
+    with torch.cuda.device(device):
+        luts = torch.from_numpy(aug_luts()).to(device)
+        weights = torch.from_numpy(gauss_weights()).to(device)
+        scratch = torch.empty((2, 3 * B, S, S, 3), dtype=torch.uint8, device=device)
+        fields = torch.empty((3, 2 * B if shape else 1, 2, S, S), dtype=torch.float32, device=device)     # noise, tmp, field
+    k, ep = 0, 0
+    while epochs is None or ep < epochs:
+        order = rng.permutation(N) if shuffle else np.arange(N)
+        for b in range(len(order) // B):
+            slot = k % PLAN_RING
+            k += 1
+            if copied[slot] is not None:
+                copied[slot].synchronize()       # (four batches old: long done)
+            n_el = fill_aug_plan(dataset, order[b * B:(b + 1) * B], ring[slot].numpy(), nring[slot].numpy())
+            with torch.cuda.device(device):
+                recs = torch.empty((3, B, REC_WORDS), dtype=torch.int32, device=device)
+                recs.copy_(ring[slot], non_blocking=True)
+                if n_el:
+                    fields[0, :n_el].copy_(nring[slot][:n_el], non_blocking=True)
+                copied[slot] = torch.cuda.Event()
+                copied[slot].record()
+                if n_el:
+                    L.call("ups_augment_field", L.ptr(fields[0]), L.ptr(weights), n_el, S, L.ptr(fields[1]), L.ptr(fields[2]), L.stream())
+                out = {key: torch.empty((B, S, S, 3), dtype=torch.float32, device=device) for key in ("view0", "view1", "view0_target")}
+                L.call("ups_augment_views", L.ptr(images), N, L.ptr(recs), L.ptr(luts), L.ptr(fields[2]), n_el, B, S, L.ptr(scratch[0]),
+                       L.ptr(scratch[1]), L.ptr(out["view0"]), L.ptr(out["view1"]), L.ptr(out["view0_target"]), 7, L.stream())
             yield out
         ep += 1
 

@@ -151,6 +151,9 @@ _SIGS = {
     "ups_canvas_assigned_parts": ([_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P], C.c_int),
     "ups_canvas_first_item": ([_P, _P, _P, _I, _I, _I, C.POINTER(_F), _I, C.POINTER(_F), _I, _P, _P, _P, _P, _P, _P], C.c_int),
     "ups_gather_views": ([_P, _L, _P, _I, _I, _P, _P, _P, _P], C.c_int),
+    "ups_augment_record_words": ([], _I),
+    "ups_augment_views": ([_P, _L, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P, _I, _P], C.c_int),
+    "ups_augment_field": ([_P, _P, _I, _I, _P, _P, _P], C.c_int),
     "ups_part_confusion": ([_P, _P, _P, _I, _L, _I, _I, _P, _P, _P], C.c_int),
     "ups_prior_sums_floats": ([_I, _I], _Z),
     "ups_prior_fwd": ([C.POINTER(PriorDesc), _P], C.c_int),
@@ -185,7 +188,10 @@ def load():
                        "(there is no CPU fallback for the product path)".format(LIB_PATH))
     lib = C.CDLL(LIB_PATH)
     for name, (args, res) in _SIGS.items():
-        fn = getattr(lib, name)
+        try:
+            fn = getattr(lib, name)
+        except AttributeError:      # (an entry point added without a new ABI number, as the ups_augment_* ones: refused by name)
+            raise UpsError("{} lacks {} (a stale library): rebuild with __graft_entry__.build()".format(LIB_PATH, name))
         fn.argtypes = args
         fn.restype = res
     lib.ups_last_error.argtypes = []

@@ -75,10 +75,12 @@ def make_dataset(cfg, rank=0, strict=False, device=None):
     is logged at WARNING level here and again with every logged step (main).  Any other exception is a bug and propagates: a run with
     a wrong key must not quietly train on noise (round-5 verdict).
     `data_on_device: True`: the csv pair datasets are fed by `data.device_batches` from a uint8 store on `device` (default: the
-    current HIP device) -- same seeds, same batches; every rank holds its own copy of the store."""
+    current HIP device) -- same seeds, same batches; every rank holds its own copy of the store.  With `data_augment_on_device: True`
+    that path also runs AugmentedPair2's `data_augment_appearance` / `data_augment_shape` (the key alone is a ValueError)."""
     try:
         cls = DATA_ALIASES.get(cfg["dataset"]) or get_obj_from_str(cfg["dataset"])
         ds = cls(dict(cfg, data_seed=D.shard_seed(cfg.get("data_seed", 1), rank)))
+        _data.check_augment_on_device(cfg)
         if cfg.get("data_on_device", False):
             if not isinstance(ds, _data.StochasticPairs):
                 raise ValueError("data_on_device: {} is not one of the csv pair datasets of data.py".format(cfg["dataset"]))
