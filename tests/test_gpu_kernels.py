@@ -1,6 +1,7 @@
 """GPU parity tests: every HIP kernel family (through the C ABI) against the CPU oracle on identical
 seeded inputs.  fp32 mode must meet north_star's 1e-3 relative tolerance (the kernel-level bars below
 are tighter); bf16 mode is compared with the oracle evaluated on bf16-rounded inputs at 2e-2."""
+import copy
 import math
 
 import numpy as np
@@ -1381,7 +1382,7 @@ def test_conv_fp8_forward(case, dev):
             ref = _oracle_conv(R, x.double(), V.double(), b.double(), 1, coords, act, res_self, None)
             assert_close(y[..., :cout].float().cpu(), ref.float(), BF16_TOL, "bf16 path of an ineligible layer")
             return
-        f8 = lay._cache["f8"]
+        f8 = lay.copies["f8"].bufs
         s_a = float(ops.Fp8.scale[f8["slot"]].cpu())
         amax_seen = float(ops.Fp8.amax[f8["slot"]].max().cpu())
     finally:
@@ -1432,7 +1433,7 @@ def test_conv_fp8_input_gradient(case, dev):
         assert ops.Fp8.eligible_grad(lay, gy.to(dev), x.to(dev))
         gx = ops.conv_dgrad(gy.to(dev), x.to(dev), lay)
         torch.cuda.synchronize()
-        f8 = lay._cache["f8g"]
+        f8 = lay.copies["f8g"].bufs
         s_g = float(ops.Fp8.scale[f8["slot"]].cpu())
         amax_seen = float(ops.Fp8.amax[f8["slot"]].max().cpu())
     finally:
@@ -1506,7 +1507,7 @@ def test_conv_fp8_weight_gradient(case, dev):
         gV, gb = ops.conv_wgrad(gyd, x, lay, fmt=lib.F16 if f16in else None, f8_src=copy)
         torch.cuda.synchronize()
         assert F.stats["wgrad_f8"] == 1
-        ew = lay._cache["f8w"]
+        ew = lay.f8["f8w"]
         s_x = float(F.scale[ew["slot"]].cpu())
         amax_seen = float(F.amax[ew["slot"]].max().cpu())
     xa = xs if act is None else torch.where(xs > 0, xs, 0.2 * xs)
@@ -1581,7 +1582,7 @@ def test_conv_fp8_copy_handed_from_producer_to_consumer(case, dev):
         F.next_in = copy
         za = ops.conv_forward(y, l2)
         zb0 = ops.conv_forward(y, l2)                         # primes the layer's own slot from the tensor ...
-        F.scale[l2._cache["f8"]["slot"]] = F.scale[copy["slot"]]      # ... which is then set to the producer's scale
+        F.scale[l2.f8["f8"]["slot"]] = F.scale[copy["slot"]]      # ... which is then set to the producer's scale
         zb = ops.conv_forward(y, l2)
         torch.cuda.synchronize()
     finally:
@@ -1723,7 +1724,7 @@ def test_weight_copies_per_layer_and_batched_are_bit_identical(k, stride, ci, co
     reg = ops.PrepRegistry()
     lay.registry = reg
     ops.WeightVersion.value += 1
-    ent = lay.prepared(lib.BF16, hw, hw, True)              # per-layer launches (registers the entry)
+    ent = lay.prepared(lib.BF16, hw, hw)                    # per-layer launches (registers the entry)
     first = {n: ent[n].clone() for n in ("w_fwd", "w_dgrad", "ctab") if ent[n] is not None}
     assert "ctab" in first and float(first["ctab"].abs().max()) > 0
     for t in (ent["w_fwd"], ent["w_dgrad"], ent["ctab"]):
@@ -1734,6 +1735,168 @@ def test_weight_copies_per_layer_and_batched_are_bit_identical(k, stride, ci, co
     torch.cuda.synchronize()
     for n, t in first.items():
         assert torch.equal(t.view(torch.uint8), ent[n].view(torch.uint8)), n
+
+
+class _CopyCase(object):
+    """One layer kind of the converted-weight tests: its variables, ``layer()`` = a new layer object over them, ``run(lay)`` = the
+    operators that create every kind of copy the layer has, ``asks`` = the prepared* calls that do the same without a launch of the
+    operators, and the kinds of copy to expect (a copy's kind: its key, or the key's first element where that is a string)."""
+
+    def __init__(self, kind, ops, lib, dev):
+        g = torch.Generator().manual_seed(77)
+        self.ops, self.kind = ops, kind
+
+        def rnd(*shape, scale=1.0):
+            return (torch.randn(*shape, generator=g) * scale).to(dev)
+        if kind == "conv_f8":       # 3x3 / stride 1 / CoordConv, 64 -> 64 at 16 x 16: blocked-K + e4m3 forward + e4m3 input gradient
+            self.vars = [rnd(3, 3, 66, 64, scale=0.05), rnd(64, scale=0.1)]
+            x, gy = rnd(2, 16, 16, 64).bfloat16(), rnd(2, 16, 16, 64, scale=0.02).bfloat16()
+            self.layer = lambda: ops.ConvLayer("t/conv2d_0", self.vars[0], self.vars[1], 3, 1, True, "leaky_relu")
+            self.run = lambda lay: (ops.conv_forward(x, lay), ops.conv_dgrad(gy, x, lay))
+            self.asks = [lambda lay: lay.prepared(lib.BF16, 16, 16), lambda lay: lay.prepared_f8(None), lambda lay: lay.prepared_f8_grad(None)]
+            self.kinds = {lib.BF16, "f8", "f8g"}
+        elif kind == "d2s":         # 3x3 / stride 2, 8 -> 32 at 32 x 32: blocked-K + the depth-to-space input-gradient weights
+            self.vars = [rnd(3, 3, 10, 32, scale=0.1), rnd(32, scale=0.1)]
+            x, gy = rnd(2, 32, 32, 8).bfloat16(), rnd(2, 16, 16, 32, scale=0.02).bfloat16()
+            self.layer = lambda: ops.ConvLayer("t/conv2d_0", self.vars[0], self.vars[1], 3, 2, True, "leaky_relu")
+            assert self.layer().d2s_channels(x) == 8
+            self.run = lambda lay: (ops.conv_forward(x, lay), ops.conv_dgrad(gy, x, lay))
+            self.asks = [lambda lay: lay.prepared(lib.BF16, 32, 32), lambda lay: lay.prepared_d2s(32, 32)]
+            self.kinds = {lib.BF16, "d2s"}
+        else:                       # deconvolution 16 -> 32 at 8 x 8 with coordinates, forward in bf16 and in fp16
+            self.vars = [rnd(3, 3, 32, 18, scale=0.05), 1.0 + rnd(32, scale=0.1), rnd(32, scale=0.1)]
+            x = rnd(2, 8, 8, 16).bfloat16()
+            self.layer = lambda: ops.DeconvLayer("t/deconv2d_0", self.vars[0], self.vars[1], self.vars[2], True)
+            self.run = lambda lay: (ops.deconv_forward(x, lay), ops.deconv_forward(x, lay, fmt=lib.F16))
+            self.asks = [lambda lay: lay.prepared(lib.BF16, lib.BF16, 8, 8), lambda lay: lay.prepared(lib.F16, lib.BF16, 8, 8)]
+            self.kinds = {"deconv"}
+
+    def change_weights(self):
+        for i, v in enumerate(self.vars[:len(self.vars) - 1]):         # V (and g); the bias has no converted copy
+            v.mul_(1.0 + 0.25 * (i + 1)).add_(0.01)
+
+    def check_kinds(self, lay):
+        kinds = set(k if isinstance(k, str) else k[0] for k in lay.copies)
+        assert kinds == self.kinds and len(lay.copies) >= len(self.asks), (sorted(map(str, lay.copies)), self.kinds)
+
+    @staticmethod
+    def buffers(lay):
+        """(copy key, buffer name) -> tensor, for every device buffer of every converted copy of the layer."""
+        return {(k, n): t for k, c in lay.copies.items() for n, t in c.bufs.items() if torch.is_tensor(t)}
+
+    def poison(self, lay):
+        for t in self.buffers(lay).values():
+            t.view(torch.uint8).fill_(0x55)
+
+    def assert_equals_lazy_conversion(self, lay, make):
+        """Every buffer of `lay` is byte-equal to what a new registry-less layer over the same variables converts lazily (`make`)."""
+        fresh = self.layer()
+        make(fresh)
+        torch.cuda.synchronize()
+        got, want = self.buffers(lay), self.buffers(fresh)
+        assert set(got) == set(want) and all(c.version == self.ops.WeightVersion.value for c in fresh.copies.values())
+        for key, t in want.items():
+            assert not bool((t.view(torch.uint8) == 0x55).all()), key
+            assert torch.equal(t.view(torch.uint8), got[key].view(torch.uint8)), key
+
+
+_COPY_KINDS = ["conv_f8", "d2s", "deconv"]
+
+
+@pytest.mark.parametrize("kind", _COPY_KINDS)
+def test_refresh_equals_lazy_conversion_for_every_kind_of_copy(kind, dev):
+    """After an optimizer step the model's registry re-makes every converted copy of its trainable layers -- the blocked-K ones in the
+    batched launch, depth-to-space / e4m3 / deconvolution operands by their own conversion: each buffer must hold the very bytes a
+    layer without a registry converts lazily from the same master weights."""
+    lib, ops, R = _mods()
+    with ops.fp8_scope(enabled=True, copy_only=False):
+        case = _CopyCase(kind, ops, lib, dev)
+        lay, reg = case.layer(), ops.PrepRegistry()
+        lay.registry = reg
+        case.run(lay)
+        case.check_kinds(lay)
+        assert sorted(map(id, reg.copies)) == sorted(map(id, lay.copies.values()))
+        torch.cuda.synchronize()
+        case.poison(lay)
+        case.change_weights()
+        ops.weights_changed(reg)
+        torch.cuda.synchronize()
+        assert all(c.version == ops.WeightVersion.value and c.ready is None for c in lay.copies.values())
+        case.assert_equals_lazy_conversion(lay, case.run)
+
+
+@pytest.mark.parametrize("kind", _COPY_KINDS)
+def test_frozen_copies_convert_once_and_again_after_invalidate(kind, dev):
+    """A frozen layer (the perceptual trunk): version bumps and refreshes leave its converted copies alone; ``invalidate()`` (a load of
+    new weights) makes the next prepared* call convert again, and touches nothing but weight copies -- fp8 slots and sites stay."""
+    lib, ops, R = _mods()
+    with ops.fp8_scope(enabled=True, copy_only=False):
+        case = _CopyCase(kind, ops, lib, dev)
+        lay, reg = case.layer(), ops.PrepRegistry()
+        lay.frozen, lay.registry = True, reg
+        case.run(lay)
+        case.check_kinds(lay)
+        assert reg.copies == []
+        torch.cuda.synchronize()
+        case.poison(lay)
+        case.change_weights()
+        ops.weights_changed(reg)
+        for ask in case.asks:
+            ask(lay)
+        torch.cuda.synchronize()
+        for key, t in case.buffers(lay).items():
+            assert bool((t.view(torch.uint8) == 0x55).all()), key
+        f8 = getattr(lay, "f8", {})
+        before = copy.deepcopy(f8)
+        assert kind != "conv_f8" or {"f8", "f8g"} <= set(before)
+        lay.invalidate()
+        assert f8 == before and all(c.version == -1 for c in lay.copies.values())
+        for ask in case.asks:
+            ask(lay)
+        assert f8 == before
+        case.assert_equals_lazy_conversion(lay, lambda fresh: [ask(fresh) for ask in case.asks])
+
+
+@pytest.mark.parametrize("kind", _COPY_KINDS)
+def test_ready_marks_are_the_same_for_every_kind_of_copy(kind, dev, monkeypatch):
+    """A copy converted lazily on one stream carries a mark that makes every OTHER stream of the same step wait for that conversion,
+    once; the mark is dropped (without a wait) once ``Streams.epoch`` has moved, and none is set while a HIP graph is captured.
+    (The state the ordering rests on, for all kinds of copy alike -- not the race it prevents.)"""
+    lib, ops, R = _mods()
+    waits = []
+    wait_event = torch.cuda.Stream.wait_event
+    monkeypatch.setattr(torch.cuda.Stream, "wait_event", lambda self, ev: (waits.append((self.cuda_stream, ev)), wait_event(self, ev))[1])
+    sa, sb = torch.cuda.Stream(dev), torch.cuda.Stream(dev)
+    with ops.fp8_scope(enabled=True, copy_only=False):
+        case = _CopyCase(kind, ops, lib, dev)
+        torch.cuda.synchronize()
+        for ask in case.asks:
+            lay = case.layer()
+            with torch.cuda.stream(sa):
+                ask(lay)
+                (cp,) = lay.copies.values()
+                ev = cp.ready[1]
+                assert cp.ready[0] == sa.cuda_stream and cp.ready[2] == set() and cp.ready[3] == ops.Streams.epoch
+                ask(lay)                                    # the converting stream itself never waits
+                assert waits == [] and cp.ready[2] == set()
+            with torch.cuda.stream(sb):
+                ask(lay)
+                assert waits == [(sb.cuda_stream, ev)] and cp.ready[2] == {sb.cuda_stream}
+                ask(lay)                                    # ... and another stream waits once
+                assert waits == [(sb.cuda_stream, ev)] and cp.ready[2] == {sb.cuda_stream}
+            ask(lay)                                        # a third stream (the launching stream) of the same step
+            assert len(waits) == 2 and waits[1][1] is ev and len(cp.ready[2]) == 2
+            del waits[:]
+            ops.Streams.epoch += 1                          # end of the step: every stream joined
+            with torch.cuda.stream(sb):
+                ask(lay)
+            assert cp.ready is None and waits == []
+            ops.WeightVersion.value += 1
+            graph = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(graph):
+                ask(lay)
+            assert cp.version == ops.WeightVersion.value and cp.ready is None and waits == []
+        torch.cuda.synchronize()
 
 
 @pytest.mark.parametrize("B,S,P", [(3, 128, 10), (1, 32, 10), (2, 64, 10), (2, 64, 16), (1, 32, 16), (2, 64, 20), (3, 32, 20), (2, 64, 25),

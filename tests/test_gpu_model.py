@@ -168,7 +168,8 @@ def test_fp8_step_tracks_bf16(dev, mask_decoder):
                 assert F.stats["fwd_copy_in"] > 0, F.stats                                            # ... and forward copies
             scales = F.scale[:F.count].cpu()
             assert bool(torch.isfinite(scales).all()) and float(scales.min()) > 0
-            assert all(l._cache[k]["version"] == ops.WeightVersion.value for l in F.layers for k in ("f8", "f8g") if k in l._cache)
+            assert all(l.copies[k].version == ops.WeightVersion.value for l in model.nets.layers.values() if not l.frozen
+                       for k in ("f8", "f8g") if k in l.copies)
     for step in range(3):
         for k, vb in runs["bf16"][0][step].items():
             vf = runs["fp8"][0][step][k]

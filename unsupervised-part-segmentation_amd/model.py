@@ -752,10 +752,7 @@ class Trainer(object):
             return
         try:
             ops.Streams.join(self.device, names=("wgrad", "aux", "pre"))
-            ops.WeightVersion.value += 1
-            self.model.nets.prep.refresh()
-            if ops.Fp8.enabled:
-                ops.Fp8.after_step()
+            ops.weights_changed(self.model.nets.prep)
         except Exception:
             pass
         self._poisoned = ("a training step failed ({}: {}) after the optimizer keys {} had been updated while the others had not"
@@ -1529,7 +1526,7 @@ class Trainer(object):
                     self._adam(key_list, None)
                     ev = side.record_event()
                 # a converted-weight cache entry created later in this step (a new (dtype, size) instance, the depth-to-space or
-                # fp8 copies) reads the fp32 master: it must see the finished update, not race with it (ops.ConvLayer._wait_master)
+                # fp8 copies) reads the fp32 master: it must see the finished update, not race with it (ops.WeightCopy._wait_master)
                 for k in key_list:
                     ops.Streams.master_busy[k] = ev
                 self._adam_done.update(key_list)
@@ -1614,11 +1611,8 @@ class Trainer(object):
         self._adam_done, self._adam_stepped = set(), set()
         ops.Streams.master_busy.clear()         # (the join above ordered this stream behind every early Adam)
         ops.Streams.epoch += 1                  # lazy weight conversions of this step are ordered before everything that follows
-        if graph_lr is None:
-            ops.WeightVersion.value += 1
-        self.model.nets.prep.refresh()          # one launch: every layer's converted weights + CoordConv tables
-        if ops.Fp8.enabled:
-            ops.Fp8.after_step()
+        # one launch for every layer's blocked-K weights + CoordConv tables, one each for the other copies; then the fp8 scales
+        ops.weights_changed(self.model.nets.prep, bump=graph_lr is None)
 
     def dp_wait_ms(self):
         """Data parallel: mean time per step the launching stream waited at the end of the backward pass -- for the weight-gradient

@@ -91,7 +91,7 @@ class ParamBank(object):
     def initialize(self, seed):
         for n, spec in self.specs.items():
             self.params[n].copy_(init_variable(seed, n, *spec))
-        ops.WeightVersion.value += 1
+        ops.weights_changed()
 
     @torch.no_grad()
     def load(self, state):
@@ -99,7 +99,7 @@ class ParamBank(object):
         for n, t in state.items():
             if n in self.params:
                 self.params[n].copy_(t.to(torch.float32))
-        ops.WeightVersion.value += 1
+        ops.weights_changed()
 
     def state(self):
         return OrderedDict((n, p.detach().cpu().clone()) for n, p in self.params.items())
@@ -502,8 +502,7 @@ class VggTrunk(object):
                     raise ValueError("{}: kernel {} does not fit {} (HWIO expected)".format(
                         lay.name, tuple(state[lay.name + "/V"].shape), tuple(lay.V.shape)))
                 lay.V.copy_(state[lay.name + "/V"]); lay.b.copy_(state[lay.name + "/b"])
-                for ent in lay._cache.values():
-                    ent["version"] = -1
+                lay.invalidate()
 
     def features(self, x_img, act_dtype):
         """x_img [n,H,W,>=3] in [-1,1] -> list of (pre-activation feature, logical channels, act for L1)."""

@@ -58,7 +58,7 @@ class Streams(object):
     enabled = not SW.flag("UPS_NO_OVERLAP")
     _pool = {}
     _raw = {}       # (name, device index) -> raw hipStream_t
-    epoch = 0          # bumped by the trainer at the end of every step (all side streams joined): scopes ConvLayer._mark_ready
+    epoch = 0          # bumped by the trainer at the end of every step (all side streams joined): scopes WeightCopy.ready
     master_busy = {}   # optimizer key -> event on the "wgrad" stream behind that key's early Adam launch (model.Trainer._launch_reduce)
     _alive = {}     # device index -> tensors the "wgrad" stream still reads.  Holding references until the next join keeps
                     # their memory out of the allocator without record_stream (whose deferred frees made the caching
@@ -143,7 +143,7 @@ class KernelTimer(object):
 
 
 class WeightVersion(object):
-    """Bumped by the optimizer; ConvLayer caches of converted weights key on it."""
+    """Bumped whenever fp32 master weights change (weights_changed); every WeightCopy compares its own version with it."""
     value = 0
 
 
@@ -164,29 +164,91 @@ class SignBits(object):
         return b
 
 
+class WeightCopy(object):
+    """One converted copy of a layer's fp32 master weights (blocked-K 16-bit / fp32, depth-to-space, e4m3 forward / input-gradient,
+    deconvolution operands).  ``bufs``: name -> device buffer, allocated once (the pointers sit in the batched refresh's item tables
+    and in captured graphs) -- what the operators read.  ``convert()`` enqueues the launches that fill them on the current stream.
+    ``item`` = (dtype_code, hi, wi) where ups_weight_prep_batch can make the copy, else None.  A copy of a trainable layer that
+    has a registry is re-made by PrepRegistry.refresh after every optimizer step; all others convert in ``get()`` once
+    WeightVersion has moved -- a frozen layer's only the first time and after ``invalidate()``."""
+    __slots__ = ("layer", "bufs", "convert", "item", "version", "ready")
+
+    def __init__(self, layer, bufs, convert, item=None):
+        self.layer, self.bufs, self.convert, self.item = layer, bufs, convert, item
+        self.version = -1
+        self.ready = None       # (raw stream, event, streams that have waited for it, Streams.epoch) behind a lazy conversion
+        if layer.registry is not None and not layer.frozen:
+            layer.registry.register(self)
+
+    def invalidate(self):
+        self.version = -1
+
+    def get(self):
+        """``bufs``, holding the current weights as far as the current stream is concerned."""
+        if self.version != WeightVersion.value and not (self.version >= 0 and self.layer.frozen):
+            self._wait_master()
+            self.convert()
+            self.version = WeightVersion.value
+            # A lazy conversion was just enqueued on the current stream: remember where, so that a consumer on ANOTHER stream of the
+            # same step (the appearance encoder first runs on "aux", the frozen trunk on "pre", both again on the launching stream)
+            # waits for it instead of racing with it.  The refresh at the end of a step runs on the launching stream, from which
+            # every side stream forks afterwards: it clears the mark.
+            dev = self.layer.V.device
+            if torch.cuda.is_current_stream_capturing():       # (captures start after eager steps: nothing converts lazily in them)
+                self.ready = None
+            else:
+                self.ready = (L.raw_stream(dev), torch.cuda.current_stream(dev).record_event(), set(), Streams.epoch)
+        elif self.ready is not None:
+            self._wait_ready()
+        return self.bufs
+
+    def _wait_ready(self):
+        rd = self.ready
+        if rd[3] != Streams.epoch:          # an earlier step's conversion: every stream has been joined and re-forked since
+            self.ready = None
+            return
+        dev = self.layer.V.device
+        cur = L.raw_stream(dev)
+        if cur != rd[0] and cur not in rd[2] and not torch.cuda.is_current_stream_capturing():
+            torch.cuda.current_stream(dev).wait_event(rd[1])
+            rd[2].add(cur)
+
+    def _wait_master(self):
+        """Before reading the fp32 master weights on this stream: wait for an Adam launch of this layer's optimizer key that is
+        still in flight on the weight-gradient stream (the trainer's early per-key Adam; keys match by substring, as edflow's
+        variable lists do)."""
+        if Streams.master_busy:
+            cur = torch.cuda.current_stream(self.layer.V.device)
+            for key, ev in Streams.master_busy.items():
+                if key in self.layer.name:
+                    cur.wait_event(ev)
+
+
 class PrepRegistry(object):
-    """Converted-weight buffers of the layers of a model, refreshed by ONE launch after the optimizer step
-    (ups_weight_prep_batch) instead of two small launches per layer and step."""
+    """The WeightCopy objects of a model's trainable layers.  ``refresh`` re-makes all of them after the optimizer step: the
+    blocked-K copies (those with an ``item``) by ONE ups_weight_prep_batch launch per dtype instead of two small launches per layer
+    and step, the others (depth-to-space, e4m3, deconvolution operands) by their own ``convert()``.  The device-side item tables
+    are built at the first refresh after a registration."""
 
     def __init__(self):
-        self.entries = []          # (layer, ent, dtype_code, hi, wi)
+        self.copies = []
         self.tables = {}           # dtype_code -> (items_dev, prefix_dev, n, total_blocks)
-        self.extra = []            # per-layer conversions outside the batched launch (depth-to-space dgrad weights)
         self.dirty = True
 
-    def register(self, layer, ent, dtype_code, hi, wi):
-        self.entries.append((layer, ent, dtype_code, hi, wi))
-        self.dirty = True
+    def register(self, copy):
+        self.copies.append(copy)
+        self.dirty = self.dirty or copy.item is not None
 
     def _build(self):
         self.tables = {}
         lib = L.load()
-        for dcode in sorted(set(e[2] for e in self.entries)):
-            ents = [e for e in self.entries if e[2] == dcode]
+        batched = [c for c in self.copies if c.item is not None]
+        for dcode in sorted(set(c.item[0] for c in batched)):
+            ents = [c for c in batched if c.item[0] == dcode]
             arr = (L.PrepItem * len(ents))()
             prefix = [0]
-            for i, (lay, ent, _, hi, wi) in enumerate(ents):
-                it = arr[i]
+            for i, c in enumerate(ents):
+                lay, ent, (_, hi, wi), it = c.layer, c.bufs, c.item, arr[i]
                 it.src = lay.V.data_ptr()
                 it.w_fwd = ent["w_fwd"].data_ptr() if ent["w_fwd"] is not None else None
                 it.w_dgrad = ent["w_dgrad"].data_ptr() if ent["w_dgrad"] is not None else None
@@ -201,25 +263,36 @@ class PrepRegistry(object):
                     it.dx[r] = dx[r] if r < lay.k else 0
                 it.ax, it.ay = 2.0 / max(1, hi - 1), 2.0 / max(1, wi - 1)
                 prefix.append(prefix[-1] + lib.ups_prep_item_blocks(C.byref(it), dcode))
-            dev = ents[0][0].V.device
+            dev = ents[0].layer.V.device
             items_dev = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(dev)
             prefix_dev = torch.tensor(prefix, dtype=torch.int64, device=dev)
             self.tables[dcode] = (items_dev, prefix_dev, len(ents), prefix[-1])
         self.dirty = False
 
     def refresh(self):
-        """Re-convert every registered layer from the current fp32 master weights."""
-        if not self.entries:
-            return
+        """Re-convert every registered copy from the current fp32 master weights, on the current stream (the caller has ordered it
+        behind every optimizer launch and forks the side streams from it afterwards: no ready mark is needed)."""
         if self.dirty:
             self._build()
         for dcode, (items_dev, prefix_dev, n, total) in self.tables.items():
             L.call("ups_weight_prep_batch", L.ptr(items_dev), L.ptr(prefix_dev), n, total, dcode, L.stream())
-        for (_lay, ent, _d, _h, _w) in self.entries:
-            ent["version"] = WeightVersion.value
-            ent["ready"] = None
-        for fn in self.extra:
-            fn()
+        for c in self.copies:
+            if c.item is None:
+                c.convert()
+            c.version = WeightVersion.value
+            c.ready = None
+
+
+def weights_changed(registry=None, bump=True):
+    """The fp32 master weights have changed (optimizer step, initialisation, restore).  bump=False: a step inside a HIP graph -- the
+    graph's own launches re-make the copies at every replay, the host-side counter stays.  With the model's registry its copies are
+    re-made here and fp8 mode's delayed scales take their step; every other copy converts at its next use."""
+    if bump:
+        WeightVersion.value += 1
+    if registry is not None:
+        registry.refresh()
+        if Fp8.enabled:
+            Fp8.after_step()
 
 
 class Fp8State(object):
@@ -229,11 +302,12 @@ class Fp8State(object):
     ``update()`` -- once per step, three tiny launches for all layers -- turns it into the next step's scale
     448 * MARGIN / amax.  A layer's first launch scales from the tensor at hand.
 
-    One instance per model (``TrainModel.fp8``): scale slots, layer list, hand-off state, switches and counters.  The operators
+    One instance per model (``TrainModel.fp8``): scale slots, hand-off state, switches and counters.  The operators
     reach the state of the model that is running through the module-level ``Fp8`` proxy; ``TrainModel`` / ``Trainer`` activate
     their own instance before they touch a layer, so two models alive in one process (a trainer plus an evaluation model, a
-    test sweep) never share slots.  Layers cache slot numbers of THEIR model's state (``generation`` guards against a layer
-    being driven under a foreign state)."""
+    test sweep) never share slots.  Layers keep the slot numbers of THEIR model's state in ``layer.f8`` (scale slots, ``primed``
+    flags, producer sites; ``generation`` guards against a layer being driven under a foreign state).  The e4m3 weight copies are
+    WeightCopy objects like every other converted copy: the model's PrepRegistry re-makes them after the optimizer step."""
     MARGIN = 0.5            # headroom for the step-to-step growth of amax (e4m3 max normal = 448)
     MAX_LAYERS = 512
     E5M2_MAX = 57344.0
@@ -247,7 +321,6 @@ class Fp8State(object):
         self.scale = None           # [MAX_LAYERS] fp32
         self.fmax = None            # [MAX_LAYERS] fp32: largest normal of the slot's format
         self.count = 0
-        self.layers = []            # trainable layers with e4m3 weights (re-converted by after_step)
         self.GRAD = True            # input gradients of the fp8 layers on e5m2 operands (False: bf16 kernels)
         # weight gradients of the wide 3x3 layers on e4m3 x e5m2 operands (conv_wgrad3x3_f8.hip) wherever the gradient arrives with
         # its producer's e5m2 copy; UPS_F8_WGRAD=0: bf16 weight gradients (A/B runs)
@@ -277,7 +350,6 @@ class Fp8State(object):
             self.scale = torch.ones((self.MAX_LAYERS,), dtype=torch.float32, device=device)
             self.fmax = torch.full((self.MAX_LAYERS,), 448.0, dtype=torch.float32, device=device)   # e4m3; gradient slots: e5m2
             self.count = 0
-            self.layers = []
         i = self.count
         self.count += 1
         if i >= self.MAX_LAYERS:
@@ -295,16 +367,9 @@ class Fp8State(object):
         self.steps += 1
 
     def after_step(self):
-        """After the optimizer step: new activation scales, e4m3 copies of the updated weights (one launch per layer)."""
+        """After the optimizer step: new activation scales (the e4m3 weight copies are PrepRegistry.refresh's)."""
         self.update()
         self.grad_side.clear()          # copies nobody read this step are released (they pinned a gradient-sized tensor each)
-        for lay in self.layers:
-            for key, tr in (("f8", 0), ("f8g", 1)):
-                ent = lay._cache.get(key)
-                if ent is not None:
-                    L.call("ups_weight_prep_f8", L.ptr(lay.V), lay.k * lay.k, lay.cin_v, lay.ci_log, lay.co, tr,
-                           L.ptr(ent["w"]), L.ptr(ent["deq"]), L.stream())
-                    ent["version"] = WeightVersion.value
 
     @staticmethod
     def wanted(site):
@@ -314,7 +379,7 @@ class Fp8State(object):
     def site(self, holder, key, device, e5m2=False, layer=None):
         """The producer site stored at holder[key] (made on first use: its scale slot and the step it was born in), or None once
         the site has gone quiet (``wanted``).  e5m2: the copy is a gradient's, its slot takes that format's range.  layer: the
-        holder is that layer's cache -- the site then records this state's generation and is read back through ``layer_entry``.
+        holder is that layer's ``f8`` -- the site then records this state's generation and is read back through ``layer_entry``.
         Open: the point-wise sites (BilinearFn, MaxPoolFn: holder = a dict owned by the Scope) carry no generation guard."""
         so = holder.get(key) if layer is None else self.layer_entry(layer, key)
         if so is None:
@@ -374,8 +439,8 @@ class Fp8State(object):
         return ent[2]
 
     def layer_entry(self, layer, key):
-        """A layer's cached fp8 entry (slot numbers, converted weights) -- only if it was made under THIS state."""
-        ent = layer._cache.get(key)
+        """A layer's fp8 entry (``layer.f8``: scale slot, primed flag or producer site) -- only if it was made under THIS state."""
+        ent = layer.f8.get(key)
         if ent is not None and ent.get("gen") != self.generation:
             raise L.UpsError("{}: fp8 entry '{}' belongs to another model's Fp8State (generation {} != {}): a layer is being "
                              "driven while a different model's state is active".format(layer.name, key, ent.get("gen"), self.generation))
@@ -437,11 +502,29 @@ class fp8_scope(object):
         Fp8.activate(self.prev)
 
 
-class ConvLayer(object):
+class _Layer(object):
+    """What ConvLayer and DeconvLayer share: the master weights V and their converted copies (``copies``: key -> WeightCopy)."""
+
+    def __init__(self, name, V):
+        self.name, self.V = name, V
+        self.frozen = False         # frozen weights (perceptual trunk): converted copies survive optimizer steps
+        self.after_wgrad = None     # optional callback run right after this layer's weight gradient has been enqueued
+        self.registry = None        # PrepRegistry of the owning model (refresh after the optimizer) or None (lazy per-layer prep)
+        self.f16 = False            # forward tensors of this layer are fp16 (nets.Scope.fmt)
+        self.copies = {}
+
+    def invalidate(self):
+        """The master weights were overwritten behind WeightVersion's back (a frozen layer's, on load): convert again at next use."""
+        for c in self.copies.values():
+            c.invalidate()
+
+
+class ConvLayer(_Layer):
     """One conv2d variable pair (V [kh,kw,Cin(+2),Cout] HWIO fp32, b [Cout]) + its launch geometry."""
 
     def __init__(self, name, V, b, k, stride, coords, act_in, slope=0.2):
-        self.name, self.V, self.b = name, V, b
+        _Layer.__init__(self, name, V)
+        self.b = b
         self.k, self.stride, self.coords = k, stride, coords
         self.act_in = L.ACT[act_in] if not isinstance(act_in, int) else act_in
         self.slope = slope
@@ -450,84 +533,40 @@ class ConvLayer(object):
         self.co = V.shape[3]
         self.grad_V = None          # optional preallocated views into a flat gradient buffer
         self.grad_b = None
-        self.frozen = False         # frozen weights (perceptual trunk): converted copies survive optimizer steps
-        self.after_wgrad = None     # optional callback run right after this layer's weight gradient has been enqueued
-        self.registry = None        # PrepRegistry of the owning model (batched refresh) or None (lazy per-layer prep)
-        self.f16 = False            # forward tensors of this layer are fp16 (nets.Scope.fmt)
         # post-activation storage (ups_conv_desc.out_act / res_act): in_post = the input tensor already holds act_in(x) -- the
         # forward and the weight gradient stage it as it is (LDS-DMA patch), the input gradient still reads act' off its sign;
         # out_act = the output is stored as out_act(y) because its consumer would apply that activation on load
         self.in_post = False
         self.out_act = L.ACT_NONE
-        self._cache = {}
+        self.f8 = {}                # fp8 mode, per Fp8State.layer_entry: scale slots + primed flags ("f8", "f8g", "f8w"), producer sites
 
-    def _mark_ready(self, ent):
-        """A lazy conversion was just enqueued on the current stream: remember where, so that a consumer on ANOTHER stream of the same
-        step (the appearance encoder first runs on "aux", the frozen trunk on "pre", both again on the launching stream) waits for
-        it instead of racing with it.  The batched refresh at the end of a step runs on the launching stream, from which every
-        side stream forks afterwards: it clears the mark."""
-        dev = self.V.device
-        if torch.cuda.is_current_stream_capturing():       # (captures start after eager steps: nothing converts lazily in them)
-            ent["ready"] = None
-            return
-        ent["ready"] = (L.raw_stream(dev), torch.cuda.current_stream(dev).record_event(), set(), Streams.epoch)
-
-    def _wait_ready(self, ent):
-        rd = ent.get("ready")
-        if rd is not None:
-            if rd[3] != Streams.epoch:          # an earlier step's conversion: every stream has been joined and re-forked since
-                ent["ready"] = None
-                return
-            cur = L.raw_stream(self.V.device)
-            if cur != rd[0] and cur not in rd[2] and not torch.cuda.is_current_stream_capturing():
-                torch.cuda.current_stream(self.V.device).wait_event(rd[1])
-                rd[2].add(cur)
-
-    def _wait_master(self):
-        """Before reading the fp32 master weights on this stream: wait for an Adam launch of this layer's optimizer key that is
-        still in flight on the weight-gradient stream (the trainer's early per-key Adam; keys match by substring, as edflow's
-        variable lists do)."""
-        if Streams.master_busy:
-            cur = torch.cuda.current_stream(self.V.device)
-            for key, ev in Streams.master_busy.items():
-                if key in self.name:
-                    cur.wait_event(ev)
-
-    # ---- converted weights (refreshed when the optimizer has stepped)
-    def prepared(self, dtype_code, hi, wi, need_dgrad):
+    # ---- converted weights (WeightCopy: re-made when the optimizer has stepped)
+    def prepared(self, dtype_code, hi, wi):
+        """Blocked-K weights [tap][k-chunk][row][64 B] of the forward ("w_fwd") and the input gradient ("w_dgrad") + "ctab"."""
         key = (dtype_code, hi, wi)
-        ent = self._cache.get(key)
-        dev = self.V.device
-        td = L.torch_dtype(dtype_code)
-        ntaps = self.k * self.k
-        ci_pad = round8(self.ci_log)
-        bk = 16 if dtype_code == L.F32 else 32          # blocked-K layout [tap][k-chunk][row][64 B]
-        if ent is None:                                 # persistent buffers (pointers stay valid for the batched refresh)
+        copy = self.copies.get(key)
+        if copy is None:
+            dev, td = self.V.device, L.torch_dtype(dtype_code)
+            ntaps, ci_pad = self.k * self.k, round8(self.ci_log)
+            bk = 16 if dtype_code == L.F32 else 32
             # a layer with fp16 forward tensors: forward weights as fp16, input-gradient weights as bf16 (one copy each)
             want_f = not (self.f16 and dtype_code == L.BF16)
             want_d = dtype_code != L.F16
-            ent = {"version": -1,
-                   "w_fwd": torch.empty((ntaps, -(-ci_pad // bk), self.co, bk), dtype=td, device=dev) if want_f else None,
+            ent = {"w_fwd": torch.empty((ntaps, -(-ci_pad // bk), self.co, bk), dtype=td, device=dev) if want_f else None,
                    "w_dgrad": torch.empty((ntaps, -(-round8(self.co) // bk), self.ci_log, bk), dtype=td, device=dev) if want_d else None,
                    "ctab": torch.empty((64, 3, self.co), dtype=torch.float32, device=dev) if (self.coords and want_f) else None}
-            self._cache[key] = ent
-            if self.registry is not None and not self.frozen:
-                self.registry.register(self, ent, dtype_code, hi, wi)
-        if ent["version"] != WeightVersion.value and not (self.frozen and ent["version"] >= 0):
-            self._wait_master()
-            L.call("ups_weight_prep", L.ptr(self.V), ntaps, self.cin_v, self.ci_log, self.co, dtype_code,
-                   L.ptr(ent["w_fwd"]), ci_pad, L.ptr(ent["w_dgrad"]), self.ci_log, round8(self.co), L.stream())
-            if ent["ctab"] is not None:
-                dy, dx, _ = self.fwd_taps(hi, wi)
-                ax, ay = 2.0 / max(1, hi - 1), 2.0 / max(1, wi - 1)     # nn.py:2145-2148 (xx / (H-1), yy / (W-1))
-                L.call("ups_coord_table", L.ptr(self.V), self.k, self.k, self.ci_log, self.co,
-                       (C.c_int32 * 9)(*dy), (C.c_int32 * 9)(*dx), self.stride, self.stride, ax, ay,
-                       L.ptr(ent["ctab"]), L.stream())
-            ent["version"] = WeightVersion.value
-            self._mark_ready(ent)
-        else:
-            self._wait_ready(ent)
-        return ent
+
+            def convert():
+                L.call("ups_weight_prep", L.ptr(self.V), ntaps, self.cin_v, self.ci_log, self.co, dtype_code,
+                       L.ptr(ent["w_fwd"]), ci_pad, L.ptr(ent["w_dgrad"]), self.ci_log, round8(self.co), L.stream())
+                if ent["ctab"] is not None:
+                    dy, dx, _ = self.fwd_taps(hi, wi)
+                    ax, ay = 2.0 / max(1, hi - 1), 2.0 / max(1, wi - 1)     # nn.py:2145-2148 (xx / (H-1), yy / (W-1))
+                    L.call("ups_coord_table", L.ptr(self.V), self.k, self.k, self.ci_log, self.co,
+                           (C.c_int32 * 9)(*dy), (C.c_int32 * 9)(*dx), self.stride, self.stride, ax, ay,
+                           L.ptr(ent["ctab"]), L.stream())
+            copy = self.copies[key] = WeightCopy(self, ent, convert, item=key)
+        return copy.get()
 
     def d2s_channels(self, x):
         """C of the depth-to-space input gradient (ups_conv_desc.d2s) when this layer / tensor can take it, else 0."""
@@ -537,60 +576,51 @@ class ConvLayer(object):
         return c if ok else 0
 
     def prepared_d2s(self, hi, wi):
-        """Weights of the one-launch input gradient of a 3x3 / stride-2 layer (ups_weight_prep_d2s)."""
-        ent = self._cache.get("d2s")
-        if ent is None:
-            kc = -(-self.co // 32)
-            ent = {"version": -1, "w": torch.empty((9, kc, 4 * self.ci_log, 32), dtype=torch.bfloat16, device=self.V.device)}
-            _, pby = same_geometry(hi, 3, 2)
-            _, pbx = same_geometry(wi, 3, 2)
+        """Weights ("w") of the one-launch input gradient of a 3x3 / stride-2 layer (ups_weight_prep_d2s); they depend on the input
+        size through its 'SAME' pads alone."""
+        _, pby = same_geometry(hi, 3, 2)
+        _, pbx = same_geometry(wi, 3, 2)
+        key = ("d2s", pby, pbx)
+        copy = self.copies.get(key)
+        if copy is None:
+            w = torch.empty((9, -(-self.co // 32), 4 * self.ci_log, 32), dtype=torch.bfloat16, device=self.V.device)
+            copy = self.copies[key] = WeightCopy(self, {"w": w}, lambda: L.call(
+                "ups_weight_prep_d2s", L.ptr(self.V), self.cin_v, self.ci_log, self.co, pby, pbx, self.ci_log, L.ptr(w), L.stream()))
+        return copy.get()
 
-            def prep():
-                self._wait_master()
-                L.call("ups_weight_prep_d2s", L.ptr(self.V), self.cin_v, self.ci_log, self.co, pby, pbx, self.ci_log,
-                       L.ptr(ent["w"]), L.stream())
-                ent["version"] = WeightVersion.value
-            ent["prep"] = prep
-            self._cache["d2s"] = ent
-            if self.registry is not None and not self.frozen:
-                self.registry.extra.append(prep)
-        if ent["version"] != WeightVersion.value and not (self.frozen and ent["version"] >= 0):
-            ent["prep"]()
-            self._mark_ready(ent)
-        else:
-            self._wait_ready(ent)
+    def _prepared_e4m3(self, key, grad, rows, k, t):
+        """An e4m3 weight copy for a GEMM of `rows` output rows over K = `k` ("w", scaled per row; "deq": the rows' dequantisation
+        factors) + "slot": the delayed-scale slot of the tensor `t` it meets (grad: an e5m2 gradient, and the weights transposed),
+        primed from `t` at the first launch that brings one."""
+        st = Fp8.layer_entry(self, key)
+        fmax = Fp8.E5M2_MAX if grad else 448.0
+        if st is None:
+            dev = self.V.device
+            st = self.f8[key] = {"slot": Fp8.slot(dev), "primed": False, "gen": Fp8.generation}
+            if grad:
+                Fp8.fmax[st["slot"]] = fmax
+            w = torch.empty((self.k * self.k, -(-k // 64), rows, 64), dtype=torch.uint8, device=dev)
+            deq = torch.empty((rows,), dtype=torch.float32, device=dev)
+            self.copies[key] = WeightCopy(self, {"w": w, "deq": deq, "slot": st["slot"]}, lambda: L.call(
+                "ups_weight_prep_f8", L.ptr(self.V), self.k * self.k, self.cin_v, self.ci_log, self.co, int(grad),
+                L.ptr(w), L.ptr(deq), L.stream()))
+        ent = self.copies[key].get()
+        if not st["primed"] and t is not None:
+            m = t[..., :k].abs().amax().float()
+            Fp8.scale[st["slot"]] = torch.where(m > 0, (fmax * Fp8.MARGIN) / m.clamp_min(1e-30), torch.ones_like(m))
+            st["primed"] = True
         return ent
 
     def prepared_f8_grad(self, g):
         """e4m3 weights of the input-gradient GEMM (rows = input channels, scaled per row) + the gradient tensor's e5m2 scale slot."""
-        ent = Fp8.layer_entry(self, "f8g")
-        dev = self.V.device
-        if ent is None:
-            kc = -(-self.co // 64)
-            ent = {"version": -1, "slot": Fp8.slot(dev), "primed": False, "gen": Fp8.generation,
-                   "w": torch.empty((self.k * self.k, kc, self.ci_log, 64), dtype=torch.uint8, device=dev),
-                   "deq": torch.empty((self.ci_log,), dtype=torch.float32, device=dev)}
-            self._cache["f8g"] = ent
-            Fp8.fmax[ent["slot"]] = Fp8.E5M2_MAX
-            if not self.frozen and self not in Fp8.layers:
-                Fp8.layers.append(self)
-        if ent["version"] != WeightVersion.value and not (self.frozen and ent["version"] >= 0):
-            self._wait_master()
-            L.call("ups_weight_prep_f8", L.ptr(self.V), self.k * self.k, self.cin_v, self.ci_log, self.co, 1,
-                   L.ptr(ent["w"]), L.ptr(ent["deq"]), L.stream())
-            ent["version"] = WeightVersion.value
-        if not ent["primed"] and g is not None:
-            m = g[..., :self.co].abs().amax().float()
-            Fp8.scale[ent["slot"]] = torch.where(m > 0, (Fp8.E5M2_MAX * Fp8.MARGIN) / m.clamp_min(1e-30), torch.ones_like(m))
-            ent["primed"] = True
-        return ent
+        return self._prepared_e4m3("f8g", True, self.ci_log, self.co, g)
 
     def prepared_f8_wgrad(self, x, fmt):
         """Scale slot of the forward input as the fp8 weight gradient quantises it (delayed scaling: the kernel records
         max |act(x)|, ops.Fp8.update turns it into the next step's scale; the first launch scales from the tensor at hand)."""
         ent = Fp8.layer_entry(self, "f8w")
         if ent is None:
-            ent = self._cache["f8w"] = {"slot": Fp8.slot(self.V.device), "primed": False, "gen": Fp8.generation}
+            ent = self.f8["f8w"] = {"slot": Fp8.slot(self.V.device), "primed": False, "gen": Fp8.generation}
         if not ent["primed"]:
             xv = x.view(torch.float16) if fmt == L.F16 else x       # (fp16 forward tensors live in bf16 containers)
             m = xv[..., :round8(self.ci_log)].abs().amax().float()
@@ -599,27 +629,9 @@ class ConvLayer(object):
         return ent
 
     def prepared_f8(self, x):
-        """e4m3 weights + per-channel dequantisation factors + this layer's activation-scale slot."""
-        ent = Fp8.layer_entry(self, "f8")
-        dev = self.V.device
-        if ent is None:
-            kc = -(-self.ci_log // 64)
-            ent = {"version": -1, "slot": Fp8.slot(dev), "primed": False, "gen": Fp8.generation,
-                   "w": torch.empty((self.k * self.k, kc, self.co, 64), dtype=torch.uint8, device=dev),
-                   "deq": torch.empty((self.co,), dtype=torch.float32, device=dev)}
-            self._cache["f8"] = ent
-            if not self.frozen and self not in Fp8.layers:
-                Fp8.layers.append(self)
-        if ent["version"] != WeightVersion.value and not (self.frozen and ent["version"] >= 0):
-            self._wait_master()
-            L.call("ups_weight_prep_f8", L.ptr(self.V), self.k * self.k, self.cin_v, self.ci_log, self.co, 0,
-                   L.ptr(ent["w"]), L.ptr(ent["deq"]), L.stream())
-            ent["version"] = WeightVersion.value
-        if not ent["primed"] and x is not None:       # first launch of the layer: scale from the tensor at hand (|act(x)| <= |x|)
-            m = x[..., :self.ci_log].abs().amax().float()
-            Fp8.scale[ent["slot"]] = torch.where(m > 0, (448.0 * Fp8.MARGIN) / m.clamp_min(1e-30), torch.ones_like(m))
-            ent["primed"] = True
-        return ent
+        """e4m3 weights + per-channel dequantisation factors + this layer's activation-scale slot (the first launch of the layer
+        scales from the tensor at hand: |act(x)| <= |x|)."""
+        return self._prepared_e4m3("f8", False, self.co, self.ci_log, x)
 
     def out_hw(self, hi, wi):
         return same_geometry(hi, self.k, self.stride)[0], same_geometry(wi, self.k, self.stride)[0]
@@ -739,7 +751,7 @@ def conv_forward(x, layer, res=None, out_f32=False, ldo=None, co_fill=None, mask
     dcode = L.dt(x) if fmt is None else fmt
     assert dcode != L.F16 or (x.dtype == torch.bfloat16 and mask is None and layer.f16)
     ho, wo = layer.out_hw(hi, wi)
-    ent = layer.prepared(dcode, hi, wi, need_dgrad=False)
+    ent = layer.prepared(dcode, hi, wi)
     ldo = ldo if ldo is not None else (layer.co if out_f32 else round8(layer.co))
     co_fill = co_fill if co_fill is not None else ldo
     out = torch.empty((n, ho, wo, ldo), dtype=torch.float32 if out_f32 else x.dtype, device=x.device)
@@ -761,7 +773,7 @@ def conv_forward(x, layer, res=None, out_f32=False, ldo=None, co_fill=None, mask
         # (a usable copy: the producer quantised act(x) with its tensor's scale)
         _attach_f8_operand(d, layer.prepared_f8, x, src if Fp8.usable(src, layer, x, ldi) else None, "fwd")
         if Fp8.PRODUCER and want_act is not None and not out_f32 and ldo % 64 == 0 and co_fill == ldo:
-            eo = Fp8.site(layer._cache, "f8o", x.device, layer=layer)
+            eo = Fp8.site(layer.f8, "f8o", x.device, layer=layer)
             if eo is not None:
                 # a post-activation output already holds want_act(out): its copy is the quantisation of the stored value
                 assert not layer.out_act or layer.out_act == want_act
@@ -797,7 +809,7 @@ def conv_dgrad(g, x, layer, res=None, mask_view=None, n_parts=0, f8_src="pop", x
         SignBits.stats[key] = SignBits.stats.get(key, 0) + 1
     dcode = L.dt(x)
     ho, wo = layer.out_hw(hi, wi)
-    ent = layer.prepared(dcode, hi, wi, need_dgrad=True)
+    ent = layer.prepared(dcode, hi, wi)
     g_hard = None
     if mask_view is not None:
         assert layer.stride == 1 and layer.act_in == L.ACT_NONE and res is None
@@ -855,7 +867,7 @@ def conv_dgrad(g, x, layer, res=None, mask_view=None, n_parts=0, f8_src="pop", x
             elif layer.k == 3 and round8(layer.co) <= 32 and hi % 16 == 0 and wi % 16 == 0:
                 emit = True     # a bf16 launch off the 128-wide two-blocks-per-CU instance (the P-channel head): it can write the copy
             if emit and Fp8.PRODUCER and gx is not None and ldi % 64 == 0 and layer.ci_log == ldi:
-                eo = Fp8.site(layer._cache, "f8go", x.device, e5m2=True, layer=layer)
+                eo = Fp8.site(layer.f8, "f8go", x.device, e5m2=True, layer=layer)
                 if eo is not None:
                     d.out_f8_act, d.out_f8_e5m2 = L.ACT_NONE, 1
                     t8 = _attach_f8_copy(d, eo, gx.shape, x.device, "dgrad_copy_out")
@@ -1035,57 +1047,36 @@ DECONV_ONE_LAUNCH = True        # False: the forward as four per-class ups_conv_
 _DECONV_TAPS = {0: ((0, 0), (2, -1)), 1: ((1, 0),)}
 
 
-class DeconvLayer(object):
+class DeconvLayer(_Layer):
     """One deconv2d variable triple: V [3,3,nf,Cin(+2)] (TF transpose layout [kh, kw, out, in]), g [nf], b [nf].  The layer is
     the input gradient of a stride-2 3x3 convolution with forward weights W = g * l2_normalize(V): its forward is four parity
     classes of taps, dx a stride-2 forward convolution of dy with W, dW a stride-2 weight gradient with the two tensors' roles
-    swapped.  W's operands are made by ups_deconv_prep once per weight version (registered with the model's PrepRegistry like
-    ConvLayer.prepared_d2s, so that a captured step re-makes them behind Adam)."""
+    swapped.  W's operands are a WeightCopy made by ups_deconv_prep: like every copy of a trainable layer it is re-made by the
+    model's PrepRegistry behind Adam, in a captured step too."""
 
     def __init__(self, name, V, g, b, coords):
-        self.name, self.V, self.g, self.b, self.coords = name, V, g, b, coords
+        _Layer.__init__(self, name, V)
+        self.g, self.b, self.coords = g, b, coords
         self.co = V.shape[2]
         self.cin_v = V.shape[3]
         self.ci_log = self.cin_v - (2 if coords else 0)
         self.grad_V = self.grad_g = self.grad_b = None     # optional views into the flat gradient bucket
-        self.registry = None
-        self.frozen = False
-        self.f16 = False
-        self.after_wgrad = None
-        self._cache = {}
-
-    _mark_ready = ConvLayer._mark_ready
-    _wait_ready = ConvLayer._wait_ready
-    _wait_master = ConvLayer._wait_master
 
     def prepared(self, fwd_code, dx_code, hi, wi):
         """W's operands for an hi x wi input: forward (fwd_code), input gradient (dx_code), fp32 W, 1 / ||V_o||, CoordConv tables."""
         key = ("deconv", fwd_code, dx_code, hi, wi)
-        ent = self._cache.get(key)
-        dev = self.V.device
-        if ent is None:
+        copy = self.copies.get(key)
+        if copy is None:
+            dev = self.V.device
             bkf, bkd = (16 if fwd_code == L.F32 else 32), (16 if dx_code == L.F32 else 32)
-            ent = {"version": -1,
-                   "w_fwd": torch.empty((9, -(-round8(self.ci_log) // bkf), self.co, bkf), dtype=L.torch_dtype(fwd_code), device=dev),
+            ent = {"w_fwd": torch.empty((9, -(-round8(self.ci_log) // bkf), self.co, bkf), dtype=L.torch_dtype(fwd_code), device=dev),
                    "w_dx": torch.empty((9, -(-round8(self.co) // bkd), self.ci_log, bkd), dtype=L.torch_dtype(dx_code), device=dev),
                    "w32": torch.empty_like(self.V), "inv": torch.empty((self.co,), dtype=torch.float32, device=dev),
                    "ctab": torch.empty((4, 64, 3, self.co), dtype=torch.float32, device=dev) if self.coords else None}
-
-            def prep():
-                self._wait_master()
-                L.call("ups_deconv_prep", L.ptr(self.V), L.ptr(self.g), self.co, self.cin_v, self.ci_log, fwd_code, L.ptr(ent["w_fwd"]),
-                       dx_code, L.ptr(ent["w_dx"]), L.ptr(ent["w32"]), L.ptr(ent["inv"]), L.ptr(ent["ctab"]), hi, wi, L.stream())
-                ent["version"] = WeightVersion.value
-            ent["prep"] = prep
-            self._cache[key] = ent
-            if self.registry is not None and not self.frozen:
-                self.registry.extra.append(prep)
-        if ent["version"] != WeightVersion.value and not (self.frozen and ent["version"] >= 0):
-            ent["prep"]()
-            self._mark_ready(ent)
-        else:
-            self._wait_ready(ent)
-        return ent
+            copy = self.copies[key] = WeightCopy(self, ent, lambda: L.call(
+                "ups_deconv_prep", L.ptr(self.V), L.ptr(self.g), self.co, self.cin_v, self.ci_log, fwd_code, L.ptr(ent["w_fwd"]),
+                dx_code, L.ptr(ent["w_dx"]), L.ptr(ent["w32"]), L.ptr(ent["inv"]), L.ptr(ent["ctab"]), hi, wi, L.stream()))
+        return copy.get()
 
 
 def _dx_code(x):
@@ -1141,9 +1132,9 @@ def deconv_dgrad(g, x, layer, fmt=None):
 
 def _deconv_ent(layer, x, fmt):
     """The entry the forward of this input used."""
-    ent = layer._cache.get(("deconv", L.dt(x) if fmt is None else fmt, _dx_code(x)) + tuple(x.shape[1:3]))
-    if ent is not None:
-        return ent
+    copy = layer.copies.get(("deconv", L.dt(x) if fmt is None else fmt, _dx_code(x)) + tuple(x.shape[1:3]))
+    if copy is not None:
+        return copy.bufs
     raise L.UpsError("{}: no prepared deconvolution weights for input {}".format(layer.name, tuple(x.shape)))
 
 
@@ -1620,7 +1611,7 @@ class TowersFn(torch.autograd.Function):
         lay_arr = (L.TowerLayer * (T * Ln))()
         for t, tw in enumerate(towers):
             for l, lay in enumerate(tw):
-                ent = lay.prepared(L.BF16, 1, 1, need_dgrad=True)
+                ent = lay.prepared(L.BF16, 1, 1)
                 e = lay_arr[t * Ln + l]
                 e.w_fwd, e.w_dgrad, e.bias = ent["w_fwd"].data_ptr(), ent["w_dgrad"].data_ptr(), lay.b.data_ptr()
                 e.grad_w = lay.grad_V.data_ptr() if lay.grad_V is not None else None
