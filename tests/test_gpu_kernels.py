@@ -1561,13 +1561,13 @@ def test_conv_fp8_copy_handed_from_producer_to_consumer(case, dev):
     producer_was, copy_only_was = F.PRODUCER, F.COPY_ONLY
     F.PRODUCER, F.COPY_ONLY = True, False          # (the producing layer itself converts its bf16 input in the kernel here)
     try:
-        F.next_out_act = lib.ACT_LRELU
-        y0 = ops.conv_forward(x, l1, res=x)                   # first call: records max |act(y)| only
-        assert F.last_out is None
+        side = ops.Handoff(f8_out_act=lib.ACT_LRELU)
+        y0 = ops.conv_forward(x, l1, res=x, side=side)        # first call: records max |act(y)| only
+        assert side.f8_out is None
         F.update()
-        F.next_out_act = lib.ACT_LRELU
-        y = ops.conv_forward(x, l1, res=x)
-        copy = F.last_out
+        side = ops.Handoff(f8_out_act=lib.ACT_LRELU)
+        y = ops.conv_forward(x, l1, res=x, side=side)
+        copy = side.f8_out
         assert copy is not None and copy["act"] == lib.ACT_LRELU and copy["t"].shape == y.shape
         # (y differs from y0 in the last bits: the input's own scale moved from the primed to the recorded maximum)
         assert rel_err(y.float(), y0.float()) <= 5e-2, "second call"     # (two fp8 quantisations of the same tensor: a sanity bound)
@@ -1579,8 +1579,7 @@ def test_conv_fp8_copy_handed_from_producer_to_consumer(case, dev):
         want = (ya * scale).clamp(-448, 448).to(torch.float8_e4m3fn).view(torch.uint8)
         assert torch.equal(copy["t"], want), "fp8 copy differs from the quantised bf16 tensor in {} bytes".format(int((copy["t"] != want).sum()))
         # consumer: bytes as they are (two blocks per CU) vs its own conversion of the bf16 tensor with the same scale
-        F.next_in = copy
-        za = ops.conv_forward(y, l2)
+        za = ops.conv_forward(y, l2, side=ops.Handoff(f8_in=copy))
         zb0 = ops.conv_forward(y, l2)                         # primes the layer's own slot from the tensor ...
         F.scale[l2.f8["f8"]["slot"]] = F.scale[copy["slot"]]      # ... which is then set to the producer's scale
         zb = ops.conv_forward(y, l2)
@@ -1588,7 +1587,6 @@ def test_conv_fp8_copy_handed_from_producer_to_consumer(case, dev):
     finally:
         ops.Fp8.activate(ops.Fp8State(False))
         F.PRODUCER, F.COPY_ONLY = producer_was, copy_only_was
-        F.next_in = F.next_out_act = F.last_out = None
     assert_close(za[..., :cout].float(), zb[..., :cout].float(), 1e-6, "consumer of the fp8 copy vs in-kernel conversion")
     assert float((za[..., :cout].float() - zb0[..., :cout].float()).abs().max()) < 0.1 * float(zb0.float().abs().max())
 
@@ -1626,8 +1624,8 @@ def test_conv_fp8_block_scaled_mfma(case, dev):
         sl = F.slot(dev)
         F.scale[sl] = s_a
         xq8 = (xa * s_a).clamp(-448, 448).to(torch.float8_e4m3fn)
-        F.next_in = {"t": xq8.view(torch.uint8).to(dev), "slot": sl, "act": lib.ACT_LRELU, "site": None}
-        y = ops.conv_forward(xd, lay, res=xd if res_self else None)
+        side = ops.Handoff(f8_in={"t": xq8.view(torch.uint8).to(dev), "slot": sl, "act": lib.ACT_LRELU, "site": None})
+        y = ops.conv_forward(xd, lay, res=xd if res_self else None, side=side)
         assert F.stats["fwd_copy_in"] == 1
         # ---- input gradient: e5m2(gy * s_g) registered as the copy of exactly this gradient tensor
         s_g = 57344.0 * F.MARGIN / float(gy.float().abs().max())
@@ -1681,14 +1679,16 @@ def test_bilinear_fp8_copies(dev):
     try:
         site = {}
         xr = x.clone().requires_grad_(True)
-        y0 = ops.BilinearFn.apply(xr, site, lib.ACT_LRELU, 0.2)          # first step: maxima only
-        assert F.last_out is None and torch.equal(y0, y_ref)
+        side = ops.Handoff()
+        y0 = ops.BilinearFn.apply(xr, site, lib.ACT_LRELU, 0.2, None, 0, side)          # first step: maxima only
+        assert side.f8_out is None and torch.equal(y0, y_ref)
         y0.backward(gy)
         gx_ref = xr.grad.clone()
         F.update()
         xr.grad = None
-        y1 = ops.BilinearFn.apply(xr, site, lib.ACT_LRELU, 0.2)
-        copy = F.last_out
+        side = ops.Handoff()
+        y1 = ops.BilinearFn.apply(xr, site, lib.ACT_LRELU, 0.2, None, 0, side)
+        copy = side.f8_out
         assert copy is not None and torch.equal(y1, y_ref)
         yf = y_ref.float(); ya = torch.maximum(yf, 0.2 * yf)
         sc = float(F.scale[copy["slot"]].cpu())
@@ -1707,7 +1707,6 @@ def test_bilinear_fp8_copies(dev):
     finally:
         ops.Fp8.activate(ops.Fp8State(False))
         F.PRODUCER = producer_was
-        F.last_out = None
         F.grad_side.clear()
 
 
@@ -2050,9 +2049,9 @@ def test_sign_bits_written_by_the_producer_and_read_by_the_input_gradient(n, h, 
     x[0, 0, 0, :8] = 0.0                                    # zeros are not positive
     xs = x.to(torch.float16).view(torch.bfloat16) if f16 else x.to(torch.bfloat16)
     res = xs if (cin == cout and stride == 1 and k == 3) else None
-    ops.SignBits.want, ops.SignBits.last = True, None
-    y = ops.conv_forward(xs, lay, res=res, fmt=fmt, res_post=res is not None)
-    bits = ops.SignBits.take()
+    side = ops.Handoff(want_bits=True)
+    y = ops.conv_forward(xs, lay, res=res, fmt=fmt, res_post=res is not None, side=side)
+    bits = side.bits
     two_tile = rows and cin == 64 and h == 128    # (64 channels at 128 columns: conv3x3_rows2_kernel, no sign bytes)
     native = (k == 3 and stride == 1 and not rows) or (rows and stride == 2)     # best effort: patch epilogue, stride-2 row kernel
     assert (bits is not None) == native
@@ -2082,10 +2081,107 @@ def test_bilinear_sign_bits(dev):
         x = torch.randn(2, 16, 16, 64, generator=g).to(dev)
         xs = x.to(torch.float16).view(torch.bfloat16) if f16 else x.to(torch.bfloat16)
         fmt = lib.F16 if f16 else None
-        ops.SignBits.want, ops.SignBits.last = False, None
-        y0 = ops.BilinearFn.apply(xs, None, 0, 0.2, fmt, lib.ACT_LRELU)
-        assert ops.SignBits.take() is None
-        ops.SignBits.want = True
-        y1 = ops.BilinearFn.apply(xs, None, 0, 0.2, fmt, lib.ACT_LRELU)
-        bits = ops.SignBits.take()
+        side = ops.Handoff(want_bits=False)
+        y0 = ops.BilinearFn.apply(xs, None, 0, 0.2, fmt, lib.ACT_LRELU, side)
+        assert side.bits is None
+        side = ops.Handoff(want_bits=True)
+        y1 = ops.BilinearFn.apply(xs, None, 0, 0.2, fmt, lib.ACT_LRELU, side)
+        bits = side.bits
         assert torch.equal(y0, y1) and bits is not None and torch.equal(bits, _pack_signs(y1))
+
+
+def test_two_fp8_handoffs_alive_at_once(dev):
+    """ops.Handoff is per call: two producer calls keep their fp8 copies side by side, a convolution in between that is given no
+    Handoff neither consumes a request nor disturbs a result, and the first copy still feeds the consumer (the layers and the
+    expectation of test_conv_fp8_copy_handed_from_producer_to_consumer, its (8, 32, 64, 192, False) case)."""
+    lib, ops, R = _mods()
+    n, h, cin, cout = 8, 32, 64, 192
+    g = torch.Generator().manual_seed(21)
+    V1 = torch.randn(3, 3, cin, cin, generator=g) / math.sqrt(9 * cin)
+    V2 = torch.randn(3, 3, cin, cout, generator=g) / math.sqrt(9 * cin)
+    l1 = _layer(ops, lib, V1, torch.randn(cin, generator=g) * 0.1, 3, 1, False, "leaky_relu", dev)
+    l2 = _layer(ops, lib, V2, torch.randn(cout, generator=g) * 0.1, 3, 1, False, "leaky_relu", dev)
+    x = torch.randn(n, h, h, cin, generator=g).to(torch.bfloat16).to(dev)
+    l3 = _layer(ops, lib, torch.randn(3, 3, cin, cin, generator=g) / math.sqrt(9 * cin), torch.zeros(cin), 3, 1, False, "leaky_relu", dev)
+    with ops.fp8_scope(enabled=True, copy_only=False) as F:
+        F.PRODUCER = True
+        prime = ops.Handoff(f8_out_act=lib.ACT_LRELU)
+        ops.conv_forward(x, l1, res=x, side=prime)            # records max |act(y)| only
+        ops.conv_forward(x, l3)                               # (primes the unrelated layer's own input scale)
+        assert prime.f8_out is None
+        F.update()
+        u_alone = ops.conv_forward(x, l3)
+        a, b = ops.Handoff(f8_out_act=lib.ACT_LRELU), ops.Handoff(f8_out_act=lib.ACT_LRELU)
+        ya = ops.conv_forward(x, l1, res=x, side=a)
+        a_out = a.f8_out
+        assert a_out is not None and a_out["act"] == lib.ACT_LRELU and a.bits is None
+        a_bytes = a_out["t"].clone()
+        u = ops.conv_forward(x, l3)                           # no Handoff: nothing in, nothing wanted
+        yb = ops.conv_forward(x, l1, res=x, side=b)
+        assert b.f8_out is not None and b.f8_out is not a_out and b.f8_out["t"].data_ptr() != a_out["t"].data_ptr()
+        assert torch.equal(ya, yb) and torch.equal(a_out["t"], b.f8_out["t"])
+        assert a.f8_out is a_out and torch.equal(a_out["t"], a_bytes), "a later call touched an earlier call's hand-off"
+        assert torch.equal(u, u_alone)
+        assert F.stats["fwd_copy_out"] == 2 and F.stats["fwd_copy_in"] == 0
+        # the consumer: a's bytes as they are vs its own conversion of the bf16 tensor with the same scale
+        za = ops.conv_forward(ya, l2, side=ops.Handoff(f8_in=a_out))
+        assert F.stats["fwd_copy_in"] == 1 and a_out["site"]["used"] == 1
+        z_b = ops.conv_forward(ya, l2, side=ops.Handoff(f8_in=b.f8_out))
+        zb0 = ops.conv_forward(ya, l2)                        # primes the layer's own slot from the tensor ...
+        F.scale[l2.f8["f8"]["slot"]] = F.scale[a_out["slot"]]     # ... which is then set to the producer's scale
+        zb = ops.conv_forward(ya, l2)
+        torch.cuda.synchronize()
+    assert torch.equal(za, z_b)
+    assert_close(za[..., :cout].float(), zb[..., :cout].float(), 1e-6, "consumer of the fp8 copy vs in-kernel conversion")
+    assert float((za[..., :cout].float() - zb0[..., :cout].float()).abs().max()) < 0.1 * float(zb0.float().abs().max())
+
+
+def _post_conv_case(ops, lib, dev):
+    """The 3x3 / stride-1 residual layer in post-activation storage at (n=4, 32x32, 64 -> 64) and its input."""
+    g = torch.Generator().manual_seed(4 + 32 + 64 + 64)
+    V = (torch.randn(3, 3, 64, 64, generator=g) / math.sqrt(9 * 64)).to(dev)
+    lay = ops.ConvLayer("t/conv2d_0", V, torch.randn(64, generator=g).to(dev), 3, 1, False, "leaky_relu")
+    lay.in_post, lay.out_act = True, lib.ACT_LRELU
+    x = torch.randn(4, 32, 32, 64, generator=g).to(dev)
+    return lay, torch.where(x > 0, x, 0.2 * x).to(torch.bfloat16)
+
+
+def test_sign_bits_of_two_calls_alive_at_once(dev):
+    """Sign bytes travel in the call's own ops.Handoff: a call without one in between neither uses up a request nor touches the
+    bytes of the call before it (convolution epilogue and the x2 bilinear kernel)."""
+    lib, ops, R = _mods()
+    lay, xs = _post_conv_case(ops, lib, dev)
+    xu = torch.randn(2, 16, 16, 64, generator=torch.Generator().manual_seed(3)).to(torch.bfloat16).to(dev)
+    for call in (lambda side: ops.conv_forward(xs, lay, res=xs, res_post=True, side=side),
+                 lambda side: ops.BilinearFn.apply(xu, None, 0, 0.2, None, lib.ACT_LRELU, side)):
+        first, third = ops.Handoff(want_bits=True), ops.Handoff(want_bits=True)
+        y1 = call(first)
+        assert first.bits is not None and first.f8_out is None
+        kept, kept_bytes = first.bits, first.bits.clone()
+        y2 = call(None)
+        y3 = call(third)
+        assert torch.equal(y1, y2) and torch.equal(y1, y3)
+        assert first.bits is kept and torch.equal(kept, kept_bytes), "a later call touched an earlier call's sign bytes"
+        assert third.bits is not None and third.bits.data_ptr() != kept.data_ptr()
+        assert torch.equal(kept, third.bits) and torch.equal(kept, _pack_signs(y1))
+
+
+def test_autograd_tape_does_not_keep_the_handoff(dev):
+    """ConvFn hands `side` to conv_forward and forgets it: the output and its grad_fn pin neither the Handoff nor, through it, the
+    fp8 copy and the sign bytes (the nets.Act owns them)."""
+    import gc
+    import weakref
+    lib, ops, R = _mods()
+    lay, xs = _post_conv_case(ops, lib, dev)
+    xr = xs.clone().requires_grad_(True)
+    side = ops.Handoff(want_bits=True)
+    y = ops.conv(xr, lay, res_self=True, side=side)
+    ref = weakref.ref(side)
+    bits = side.bits
+    del side
+    gc.collect()
+    assert ref() is None, "something recorded in the forward still holds the Handoff"
+    assert y.grad_fn is not None and bits is not None and torch.equal(bits, _pack_signs(y))
+    gy = torch.randn(y.shape, device=dev).to(torch.bfloat16)
+    y.backward(gy)
+    assert torch.equal(xr.grad, ops.conv_dgrad(gy, xs, lay, res=gy))

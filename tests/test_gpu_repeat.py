@@ -108,13 +108,13 @@ def test_stride2_row_stream_launches_repeat_bit_identically(case, dev, monkeypat
     lay = ops.ConvLayer("t/conv2d_0", V, b, 3, 2, False, None)
     lay.out_act = lib.ACT_LRELU
     xs = torch.randn(n, h, h, cin, device=dev).to(torch.bfloat16)
-    ops.SignBits.want, ops.SignBits.last = True, None
-    y0 = ops.conv_forward(xs, lay)
-    bits0 = ops.SignBits.take()
+    side = ops.Handoff(want_bits=True)
+    y0 = ops.conv_forward(xs, lay, side=side)
+    bits0 = side.bits
     for rep in range(1, REPEATS):
-        ops.SignBits.want, ops.SignBits.last = True, None
-        y = ops.conv_forward(xs, lay)
-        bits = ops.SignBits.take()
+        side = ops.Handoff(want_bits=True)
+        y = ops.conv_forward(xs, lay, side=side)
+        bits = side.bits
         torch.cuda.synchronize()
         assert torch.equal(y.view(torch.int16), y0.view(torch.int16)), "{}: launch {} differs".format(name, rep)
         assert (bits is None) == (bits0 is None) and (bits is None or torch.equal(bits, bits0))

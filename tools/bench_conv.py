@@ -105,10 +105,7 @@ def main():
             ops.Fp8.scale[slot] = 224.0 / xa.abs().max()
             copy = {"t": (xa * ops.Fp8.scale[slot]).clamp(-448, 448).to(torch.float8_e4m3fn).view(torch.uint8), "act": lay.act_in, "slot": slot}
 
-            def fwd():
-                ops.Fp8.next_in = copy
-                return ops.conv_forward(x, lay)
-            tf = timeit(fwd, args.iters)
+            tf = timeit(lambda: ops.conv_forward(x, lay, side=ops.Handoff(f8_in=copy)), args.iters)
         else:
             tf = timeit(_fwd, args.iters)
         if fmt == lib.F16:

@@ -35,15 +35,15 @@ if fmt == lib.F16:
     x = x.to(torch.float16).view(torch.bfloat16)
 res = x if (cin == cout and stride == 1 and act is not None) else None
 F = ops.Fp8
+copy = None         # the producer's e4m3 copy of x, handed to the forward launch as Handoff.f8_in
 if f8:
     F = ops.Fp8.activate(ops.Fp8State(True))
     sx, sg = F.slot(dev), F.slot(dev)
     F.scale[sx] = 448.0 * F.MARGIN / float(x.float().abs().max()); F.scale[sg] = 57344.0 * F.MARGIN / 6.0
     xf = x.view(torch.float16).float() if fmt == lib.F16 else x.float()
     x8 = (xf * F.scale[sx]).clamp(-448, 448).to(torch.float8_e4m3fn).view(torch.uint8)
-    if fmt != lib.F16:
-        F.next_in = {"t": x8, "slot": sx, "act": lay.act_in, "site": None}
-y = ops.conv_forward(x, lay, res=res, fmt=fmt, res_post=lay.in_post)
+    copy = {"t": x8, "slot": sx, "act": lay.act_in, "site": None}
+y = ops.conv_forward(x, lay, res=res, fmt=fmt, res_post=lay.in_post, side=ops.Handoff(f8_in=copy if fmt != lib.F16 else None))
 gy = torch.randn(y.shape, device=dev).to(torch.bfloat16)
 if f8:
     g8 = (gy.float() * F.scale[sg]).clamp(-57344, 57344).to(torch.float8_e5m2).view(torch.uint8)
@@ -53,12 +53,10 @@ if bits:
     xbits = (pos * (2 ** torch.arange(8, device=dev, dtype=torch.uint8))).sum(-1).to(torch.uint8).contiguous()
 for _ in range(3):
     if mode == "fwd":
-        if f8:
-            F.next_in = {"t": x8, "slot": sx, "act": lay.act_in, "site": None}
-        ops.SignBits.want, ops.SignBits.last = bool(bits), None
-        ops.conv_forward(x, lay, res=res, fmt=fmt, res_post=lay.in_post)
+        side = ops.Handoff(f8_in=copy, want_bits=bits)
+        ops.conv_forward(x, lay, res=res, fmt=fmt, res_post=lay.in_post, side=side)
         if bits:
-            assert ops.SignBits.take() is not None, "the launch did not write the sign bytes"
+            assert side.bits is not None, "the launch did not write the sign bytes"
     elif mode == "dgrad":
         if f8:
             F.register_grad_copy(gy, {"t": g8, "slot": sg, "site": None})

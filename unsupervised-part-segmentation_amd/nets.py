@@ -175,17 +175,15 @@ class Scope(object):
         ho, wo = ops.same_geometry(x.h, k, stride)[0], ops.same_geometry(x.w, k, stride)[0]
         if lay is None:
             return Act(None, x.n, ho, wo, cout, fmt=None if out_f32 else self.fmt, post=post)
-        if ops.Fp8.enabled:     # hand the input's fp8 copy in, ask for one of the output (consumed with this scope's activation)
-            ops.Fp8.next_in, ops.Fp8.next_out_act, ops.Fp8.last_out = x.f8, (self.act if self.act != L.ACT_ELU else None), None
         assert x.fmt == self.fmt and (res is None or res.fmt == self.fmt), "tensor format does not match the scope's"
-        # a post-activation output feeds an activated convolution of this scope: its producer writes the sign bytes that
-        # convolution's input gradient needs (ops.SignBits), and this convolution hands its own input's on
-        ops.SignBits.want, ops.SignBits.last = bool(post), None
+        # fp8: hand the input's copy in, ask for one of the output (consumed with this scope's activation).  A post-activation
+        # output feeds an activated convolution of this scope: its producer writes the sign bytes that convolution's input
+        # gradient needs (ops.SignBits), and this convolution hands its own input's on
+        side = ops.Handoff(x.f8, self.act if self.act != L.ACT_ELU else None, post)
         t = ops.conv(x.t, lay, res=None if res is None else res.t, res_self=res_self, out_f32=out_f32, mask=x.mask, fmt=self.fmt,
-                     res_post=bool(res is not None and res.post), x_bits=x.bits if (act_in != L.ACT_NONE and x.mask is None) else None)
-        f8 = ops.Fp8.last_out if ops.Fp8.enabled else None
-        ops.Fp8.last_out = None
-        return Act(t, x.n, ho, wo, cout, f8=f8, fmt=None if out_f32 else self.fmt, post=post, bits=ops.SignBits.take())
+                     res_post=bool(res is not None and res.post), x_bits=x.bits if (act_in != L.ACT_NONE and x.mask is None) else None,
+                     side=side)
+        return Act(t, x.n, ho, wo, cout, f8=side.f8_out, fmt=None if out_f32 else self.fmt, post=post, bits=side.bits)
 
     def nin(self, x, cout, **kw):
         return self.conv2d(x, cout, k=1, **kw)
@@ -211,24 +209,19 @@ class Scope(object):
             raise L.UpsError("{}: bilinear up-sampling of a post-activation tensor".format(self.prefix))
         if x.t is None:
             return Act(None, x.n, 2 * x.h, 2 * x.w, x.c, fmt=self.fmt, post=post)
-        if not ops.Fp8.enabled or self.act == L.ACT_ELU:
-            ops.SignBits.want, ops.SignBits.last = bool(post), None
-            t = ops.BilinearFn.apply(x.t, None, 0, 0.2, self.fmt, self.act if post else 0)
-            return Act(t, x.n, 2 * x.h, 2 * x.w, x.c, fmt=self.fmt, post=post, bits=ops.SignBits.take())
-        # fp8: the up-sampled tensor feeds this scope's next convolution -- hand it an e4m3 copy of act(y) (and, backwards, the
-        # convolution below an e5m2 copy of the gradient); per-call-site scale slots live with the model.  A scope whose FORWARD
-        # stays fp16 (the mask decoder: its logits decide the masks, fp8 operands cost IoU) keeps the fp16 / post-activation
-        # forward of the bf16 mode and only hands the gradient copy on.
-        sites = self.owner.__dict__.setdefault("f8_sites", {})
-        site = sites.setdefault("{}/upsample@{}".format(self.prefix, self.counter), {})
-        if self.fmt == L.F16:
-            ops.SignBits.want, ops.SignBits.last = bool(post), None
-            t = ops.BilinearFn.apply(x.t, site, 0, 0.2, self.fmt, self.act if post else 0)
-            return Act(t, x.n, 2 * x.h, 2 * x.w, x.c, fmt=self.fmt, post=post, bits=ops.SignBits.take())
-        ops.Fp8.last_out = None
-        t = ops.BilinearFn.apply(x.t, site, self.act, 0.2)
-        f8, ops.Fp8.last_out = ops.Fp8.last_out, None
-        return Act(t, x.n, 2 * x.h, 2 * x.w, x.c, f8=f8)
+        # fp8: the up-sampled tensor feeds this scope's next convolution -- hand it an e4m3 copy of act(y), stored pre-activation
+        # (and, backwards, the convolution below an e5m2 copy of the gradient); per-call-site scale slots live with the model.
+        # A scope whose FORWARD stays fp16 (the mask decoder: its logits decide the masks, fp8 operands cost IoU) keeps the fp16 /
+        # post-activation forward of the bf16 mode and only hands the gradient copy on.
+        site, act = None, 0
+        if ops.Fp8.enabled and self.act != L.ACT_ELU:
+            sites = self.owner.__dict__.setdefault("f8_sites", {})
+            site = sites.setdefault("{}/upsample@{}".format(self.prefix, self.counter), {})
+            if self.fmt != L.F16:
+                act, post = self.act, False
+        side = ops.Handoff(want_bits=post)
+        t = ops.BilinearFn.apply(x.t, site, act, 0.2, self.fmt, self.act if post else 0, side)
+        return Act(t, x.n, 2 * x.h, 2 * x.w, x.c, f8=side.f8_out, fmt=self.fmt, post=post, bits=side.bits)
 
     def _deconv_layer(self, cin, nf):
         name = "{}/deconv2d_{}".format(self.prefix, self.dcounter)
@@ -517,24 +510,15 @@ class VggTrunk(object):
         hb = None       # sign bytes of h from the convolution that produced it (ops.SignBits): the next one's input gradient reads them
         for bi, blk in enumerate(self.layers):
             if bi > 0:
-                if f8:
-                    site = self.f8_sites.setdefault((bi, tuple(h.shape)), {})
-                    ops.Fp8.last_out = None
-                    h = ops.MaxPoolFn.apply(h, site, L.ACT_RELU)     # max-pool commutes with ReLU: pool the pre-activations
-                    h8, ops.Fp8.last_out = ops.Fp8.last_out, None
-                else:
-                    h = ops.MaxPoolFn.apply(h)     # max-pool commutes with ReLU: pool the pre-activations
-                hb = None
+                site = self.f8_sites.setdefault((bi, tuple(h.shape)), {}) if f8 else None
+                side = ops.Handoff()
+                h = ops.MaxPoolFn.apply(h, site, L.ACT_RELU, side)     # max-pool commutes with ReLU: pool the pre-activations
+                h8, hb = side.f8_out, None
             for ci, lay in enumerate(blk):
-                if f8:
-                    ops.Fp8.next_in, ops.Fp8.next_out_act, ops.Fp8.last_out = h8, (L.ACT_RELU if ci + 1 < len(blk) else None), None
-                ops.SignBits.want = bool(torch.is_grad_enabled() and lay.out_act and ci + 1 < len(blk))
-                ops.SignBits.last = None
-                h = ops.ConvFn.apply(h, lay.V, lay.b, None, lay, 0, False, None, None, None, None, None, False,
-                                     hb if lay.in_post else None)
-                hb = ops.SignBits.take()
-                if f8:
-                    h8, ops.Fp8.last_out = ops.Fp8.last_out, None
+                inner = ci + 1 < len(blk)       # feeds another convolution of the block: that one reads the copy and the sign bytes
+                side = ops.Handoff(h8, L.ACT_RELU if f8 and inner else None, bool(inner and lay.out_act and torch.is_grad_enabled()))
+                h = ops.conv(h, lay, x_bits=hb if lay.in_post else None, side=side)
+                h8, hb = side.f8_out, side.bits
                 if ci == 1:
                     feats.append((h, lay.co, L.ACT_RELU))
         return feats

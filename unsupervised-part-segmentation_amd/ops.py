@@ -152,16 +152,23 @@ class SignBits(object):
     bit of every element of the layer's forward input -- the sign, for act' -- and re-read the whole 16-bit tensor for it.  The
     PRODUCER of such a tensor (a convolution's epilogue, the x2 bilinear kernel) now also writes [n,h,w,c/8] sign bytes, the handle
     carries them (nets.Act.bits) and the consuming convolution's backward passes them to ups_conv_igemm next to `dact`.
-    Hand-off like Fp8.last_out: `want` is set by the caller that will keep the bits, `last` by the producer."""
+    The caller that will keep the bits asks for them with ``Handoff.want_bits`` and finds them in ``Handoff.bits`` after the call."""
     ENABLED = SW.flag("UPS_SIGN_BITS")
-    want = False
-    last = None
     stats = None        # a dict when a probe wants to know which input gradients ran without bits (tools/probes/sign_bits_coverage.py)
 
-    @classmethod
-    def take(cls):
-        b, cls.last, cls.want = cls.last, None, False
-        return b
+
+class Handoff(object):
+    """What ONE producer call (ops.conv, BilinearFn, MaxPoolFn: their last argument ``side``) is given and gives back beside its
+    tensor; made by the caller for that call, never kept by the operator or its autograd context (the nets.Act carries the results).
+    In: ``f8_in`` -- the fp8 copy of the input its producer wrote (Fp8.handle) or None; ``f8_out_act`` -- the activation-on-load of
+    the output's consumer, None: no fp8 copy of the output is wanted (ops.conv; the point-wise producers take it as `act` and
+    write whenever their site does); ``want_bits`` -- the output's sign bytes (SignBits) are wanted.
+    Out, None where the call wrote nothing: ``f8_out`` -- the output's fp8 copy (Fp8.handle); ``bits`` -- its sign bytes."""
+    __slots__ = ("f8_in", "f8_out_act", "want_bits", "f8_out", "bits", "__weakref__")
+
+    def __init__(self, f8_in=None, f8_out_act=None, want_bits=False):
+        self.f8_in, self.f8_out_act, self.want_bits = f8_in, f8_out_act, want_bits
+        self.f8_out = self.bits = None
 
 
 class WeightCopy(object):
@@ -332,13 +339,10 @@ class Fp8State(object):
         self.COPY_ONLY = copy_only
         # fp8 copies handed from layer to layer: the producing convolution's epilogue writes e4m3(act(out) * scale) next to its
         # bf16 output (scale = the delayed scale of that tensor), the consuming convolution stages those bytes without any
-        # conversion.  nets.Scope passes the handle along: next_in / next_out_act are set right before ops.conv, last_out is
-        # read right after.  UPS_F8_PRODUCER=0 switches the hand-off off (every eligible layer then converts its bf16 operand
-        # inside the kernel).
+        # conversion.  nets.Scope passes the handle ({"t": uint8 tensor, "act": UPS_ACT_*, "slot": scale slot, "site"}) along as
+        # arguments of the calls: Handoff.f8_in into ops.conv, Handoff.f8_out out of it; no state here outlives a call.
+        # UPS_F8_PRODUCER=0 switches the hand-off off (every eligible layer then converts its bf16 operand inside the kernel).
         self.PRODUCER = SW.flag("UPS_F8_PRODUCER")
-        self.next_in = None         # {"t": uint8 tensor, "act": UPS_ACT_*, "slot": scale slot} of the coming call's input
-        self.next_out_act = None    # activation-on-load of the consumer of the coming call's output (None: no copy wanted)
-        self.last_out = None        # the copy the last call wrote (same dict), or None
         self.steps = 0              # update() calls so far (a tensor's copy starts one step after its first maximum was recorded)
         self.stats = {"fwd_f8": 0, "fwd_copy_in": 0, "fwd_copy_out": 0, "dgrad_f8": 0, "dgrad_copy_in": 0, "dgrad_copy_out": 0,
                       "wgrad_f8": 0}
@@ -400,8 +404,8 @@ class Fp8State(object):
 
     @staticmethod
     def handle(site, t, act=None):
-        """What a producer hands on: ``next_in`` / ``last_out`` (act = the activation the copy was quantised behind) or, without
-        `act`, the argument of ``register_grad_copy``."""
+        """What a producer hands on: ``Handoff.f8_out``, the next call's ``Handoff.f8_in`` (act = the activation the copy was
+        quantised behind) or, without `act`, the argument of ``register_grad_copy``."""
         h = {"t": t, "slot": site["slot"], "site": site}
         if act is not None:
             h["act"] = act
@@ -740,8 +744,8 @@ def _launch_conv(d, layer, kind=None, flops=None):
         L.call("ups_conv_igemm", C.byref(d), L.stream())
 
 
-def conv_forward(x, layer, res=None, out_f32=False, ldo=None, co_fill=None, mask=None, fmt=None, res_post=False):
-    """out = conv(act(x) (+coords), V) + b (+ res);  x [n,hi,wi,ldi].
+def conv_forward(x, layer, res=None, out_f32=False, ldo=None, co_fill=None, mask=None, fmt=None, res_post=False, side=None):
+    """out = conv(act(x) (+coords), V) + b (+ res);  x [n,hi,wi,ldi].  side: this call's Handoff (None: nothing in, nothing wanted).
     fmt = L.F16: x, res and (unless out_f32) out hold fp16 in bf16 containers (module docstring).
     mask = (hard_bits [B,hi,wi] int32, P): x is the UNMASKED view [B,hi,wi,ldi] and the convolution runs on the P*B part images
     x[b] * hard[b,:,:,p] (part-major) without materialising them (model.py:176-187, nn.py:81-113)."""
@@ -765,11 +769,11 @@ def conv_forward(x, layer, res=None, out_f32=False, ldo=None, co_fill=None, mask
         d.res, d.ldr = res.data_ptr(), res.shape[-1]
         d.res_act = layer.act_in if res_post else L.ACT_NONE       # residual stored as act(x): inverted in the epilogue
         assert not (d.res_act and layer.act_in != L.ACT_LRELU), "only a leaky-ReLU residual can be stored post-activation"
-    f8_out = None
+    side = side if side is not None else Handoff()
+    src, want_act = side.f8_in, side.f8_out_act
     if mask is not None:
         d.mask_bits, d.mask_batch = mask[0].data_ptr(), x.shape[0]
-    elif dcode != L.F16 and Fp8.eligible(layer, x) and (not Fp8.copy_only() or Fp8.usable(Fp8.next_in, layer, x, ldi)):
-        src, want_act = Fp8.next_in, Fp8.next_out_act
+    elif dcode != L.F16 and Fp8.eligible(layer, x) and (not Fp8.copy_only() or Fp8.usable(src, layer, x, ldi)):
         # (a usable copy: the producer quantised act(x) with its tensor's scale)
         _attach_f8_operand(d, layer.prepared_f8, x, src if Fp8.usable(src, layer, x, ldi) else None, "fwd")
         if Fp8.PRODUCER and want_act is not None and not out_f32 and ldo % 64 == 0 and co_fill == ldo:
@@ -780,18 +784,15 @@ def conv_forward(x, layer, res=None, out_f32=False, ldo=None, co_fill=None, mask
                 d.out_f8_act = L.ACT_NONE if layer.out_act else want_act
                 t8 = _attach_f8_copy(d, eo, out.shape, x.device, "fwd_copy_out")
                 if t8 is not None:
-                    f8_out = Fp8.handle(eo, t8, want_act)
-    Fp8.next_in = Fp8.next_out_act = None
-    Fp8.last_out = f8_out
-    SignBits.last = None
-    if SignBits.want and SignBits.ENABLED and not out_f32 and out.dtype == torch.bfloat16 and ldo % 8 == 0:
-        SignBits.last = torch.empty((n, ho, wo, ldo // 8), dtype=torch.uint8, device=x.device)
-        d.sign_out = SignBits.last.data_ptr()
-    SignBits.want = False
+                    side.f8_out = Fp8.handle(eo, t8, want_act)
+    bits = None
+    if side.want_bits and SignBits.ENABLED and not out_f32 and out.dtype == torch.bfloat16 and ldo % 8 == 0:
+        bits = torch.empty((n, ho, wo, ldo // 8), dtype=torch.uint8, device=x.device)
+        d.sign_out = bits.data_ptr()
     assert round8(layer.ci_log) <= ldi, (layer.name, layer.ci_log, ldi)
     _launch_conv(d, layer, "fwd", 2.0 * n * ho * wo * layer.k * layer.k * layer.cin_v * layer.co)
-    if SignBits.last is not None and not L.load().ups_conv_sign_out_written():
-        SignBits.last = None            # the launch went to a kernel that does not write them (best effort: upsparts_hip.h)
+    if bits is not None and L.load().ups_conv_sign_out_written():
+        side.bits = bits                # (a launch that went to a kernel that does not write them hands none on: upsparts_hip.h)
     return out
 
 
@@ -976,15 +977,16 @@ class ConvFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, V, b, res, layer, res_mode, out_f32, ldo, hard=None, hard_bits=None, view_f32=None, fmt=None, res_post=False,
-                x_bits=None):
+                x_bits=None, side=None):
         """hard / hard_bits / view_f32 given: the part-masked convolution (x = the unmasked view in the activation dtype,
-        the P*B part images are formed in the kernel's load); the gradient w.r.t. `hard` comes out of the dgrad epilogue."""
+        the P*B part images are formed in the kernel's load); the gradient w.r.t. `hard` comes out of the dgrad epilogue.
+        side: the call's Handoff; it goes to conv_forward and is not kept on ctx (the tape pins neither fp8 copy nor sign bytes)."""
         x = x.contiguous()
         r = x if res_mode == 2 else (res.contiguous() if res_mode == 1 else None)
         ctx.mask = None if hard is None else (hard_bits, hard.shape[-1])
         # res_mode 2: the residual is the input itself -- stored post-activation exactly when the layer's input is
         out = conv_forward(x, layer, res=r, out_f32=out_f32, ldo=ldo, mask=ctx.mask, fmt=fmt,
-                           res_post=layer.in_post if res_mode == 2 else bool(res_post))
+                           res_post=layer.in_post if res_mode == 2 else bool(res_post), side=side)
         ctx.save_for_backward(x, view_f32)
         ctx.layer, ctx.res_mode, ctx.fmt = layer, res_mode, fmt
         ctx.x_bits = x_bits             # sign bytes of x from its producer (SignBits): the input gradient reads them instead of x
@@ -1027,17 +1029,19 @@ class ConvFn(torch.autograd.Function):
             # the autograd engine may accumulate other branches into the returned tensor IN PLACE; the side stream
             # is still reading g, so hand out a copy in that case
             gres = g.clone() if offloaded else g
-        return gx, gV, gb, gres, None, None, None, None, g_hard, None, None, None, None, None
+        return gx, gV, gb, gres, None, None, None, None, g_hard, None, None, None, None, None, None
 
 
-def conv(x, layer, res=None, res_self=False, out_f32=False, ldo=None, mask=None, fmt=None, res_post=False, x_bits=None):
+def conv(x, layer, res=None, res_self=False, out_f32=False, ldo=None, mask=None, fmt=None, res_post=False, x_bits=None, side=None):
     """mask = (hard [B,H,W,P] fp32 autograd leaf, hard_bits [B,H,W] int32, view_f32 [B,H,W,3]): part-masked convolution.
-    res_post: `res` is stored post-activation (ups_conv_desc.res_act).  x_bits: the sign bytes of x (SignBits)."""
+    res_post: `res` is stored post-activation (ups_conv_desc.res_act).  x_bits: the sign bytes of x (SignBits).
+    side: this call's Handoff -- the input's fp8 copy, what is wanted of the output, and what the call wrote."""
     mode = 2 if res_self else (1 if res is not None else 0)
     if mask is None:
-        return ConvFn.apply(x, layer.V, layer.b, res, layer, mode, out_f32, ldo, None, None, None, fmt, res_post, x_bits)
+        return ConvFn.apply(x, layer.V, layer.b, res, layer, mode, out_f32, ldo, None, None, None, fmt, res_post, x_bits, side)
     assert mode == 0
-    return ConvFn.apply(x, layer.V, layer.b, None, layer, 0, out_f32, ldo, mask[0], mask[1], mask[2].contiguous(), None, False)
+    return ConvFn.apply(x, layer.V, layer.b, None, layer, 0, out_f32, ldo, mask[0], mask[1], mask[2].contiguous(), None, False, None,
+                        side)
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------
@@ -1223,10 +1227,12 @@ def masked_conv_eligible(dtype, size, n_parts):
 
 class BilinearFn(torch.autograd.Function):
     """site: per-call-site state (a dict owned by the Scope) when the up-sampling feeds fp8 convolutions: its forward then also
-    writes the e4m3 copy of act(y), its backward the e5m2 copy of the gradient it returns (ops.Fp8 hand-off)."""
+    writes the e4m3 copy of act(y), its backward the e5m2 copy of the gradient it returns.  side: the call's Handoff (not kept on
+    ctx) -- the forward leaves that copy in ``side.f8_out`` and, asked by ``side.want_bits``, a post-activation result's sign bytes
+    in ``side.bits``."""
 
     @staticmethod
-    def forward(ctx, x, site=None, act=0, slope=0.2, fmt=None, out_act=0):
+    def forward(ctx, x, site=None, act=0, slope=0.2, fmt=None, out_act=0, side=None):
         """out_act: the result is stored as out_act(y) (post-activation storage for a consuming residual block; gradients stay
         with respect to y, so the backward is unchanged).  `site` with an fp16 / post-activation forward (the mask decoder in fp8
         mode: its forward stays fp16, round 4): only the BACKWARD hands an e5m2 copy of the gradient on."""
@@ -1236,21 +1242,20 @@ class BilinearFn(torch.autograd.Function):
         f8_site = site is not None and Fp8.enabled and Fp8.PRODUCER and x.dtype == torch.bfloat16 and c % 64 == 0 and (2 * h) % 16 == 0
         ctx.site, ctx.shape = (site if f8_site else None), (n, h, w, c)
         if out_act:
-            SignBits.last = None
-            if SignBits.want and SignBits.ENABLED and x.dtype == torch.bfloat16 and c % 8 == 0:
-                SignBits.last = torch.empty((n, 2 * h, 2 * w, c // 8), dtype=torch.uint8, device=x.device)
+            if side is not None and side.want_bits and SignBits.ENABLED and x.dtype == torch.bfloat16 and c % 8 == 0:
+                side.bits = torch.empty((n, 2 * h, 2 * w, c // 8), dtype=torch.uint8, device=x.device)
                 L.call("ups_bilinear2x_fwd_bits", L.ptr(x), L.ptr(y), L.dt(x) if fmt is None else fmt, n, h, w, c, out_act, slope,
-                       L.ptr(SignBits.last), L.stream())
+                       L.ptr(side.bits), L.stream())
             else:
                 L.call("ups_bilinear2x_fwd_act", L.ptr(x), L.ptr(y), L.dt(x) if fmt is None else fmt, n, h, w, c, out_act, slope, L.stream())
-            SignBits.want = False
             return y
         so = Fp8.site(site, "fwd", x.device) if (f8_site and fmt != L.F16) else None
         if so is not None:
             t8 = Fp8.emit(so, y.shape, x.device)
             L.call("ups_bilinear2x_fwd_f8", L.ptr(x), L.ptr(y), n, h, w, c, L.ptr(t8),
                    L.ptr(Fp8.scale[so["slot"]:]), L.ptr(Fp8.amax[so["slot"]]), act, slope, 0, L.stream())
-            Fp8.last_out = Fp8.handle(so, t8, act) if t8 is not None else None
+            if side is not None and t8 is not None:
+                side.f8_out = Fp8.handle(so, t8, act)
         else:
             L.call("ups_bilinear2x_fwd", L.ptr(x), L.ptr(y), L.dt(x) if fmt is None else fmt, n, h, w, c, L.stream())
         return y
@@ -1272,7 +1277,7 @@ class BilinearFn(torch.autograd.Function):
                 Fp8.register_grad_copy(gx, Fp8.handle(so, t8))
         else:
             L.call("ups_bilinear2x_bwd", L.ptr(g), L.ptr(gx), L.dt(g), n, h, w, c, L.stream())
-        return gx, None, None, None, None, None
+        return gx, None, None, None, None, None, None
 
 
 class DepthToSpaceFn(torch.autograd.Function):
@@ -1394,10 +1399,11 @@ class EluFn(torch.autograd.Function):
 
 class MaxPoolFn(torch.autograd.Function):
     """site (fp8 mode): per-call-site state when the pooled tensor feeds an fp8 convolution -- the forward then also writes the
-    e4m3 copy of act(y) (ops.Fp8 hand-off: Fp8State.site / emit); `act` = the activation-on-load of that consumer."""
+    e4m3 copy of act(y) (Fp8State.site / emit) and leaves it in ``side.f8_out`` (side: the call's Handoff, not kept on ctx);
+    `act` = the activation-on-load of that consumer."""
 
     @staticmethod
-    def forward(ctx, x, site=None, act=0):
+    def forward(ctx, x, site=None, act=0, side=None):
         x = x.contiguous()
         n, h, w, c = x.shape
         y = torch.empty((n, h // 2, w // 2, c), dtype=x.dtype, device=x.device)
@@ -1408,7 +1414,8 @@ class MaxPoolFn(torch.autograd.Function):
             t8 = Fp8.emit(so, y.shape, x.device)
             L.call("ups_maxpool2_fwd_f8", L.ptr(x), L.ptr(y), n, h, w, c, L.ptr(t8),
                    L.ptr(Fp8.scale[so["slot"]:]), L.ptr(Fp8.amax[so["slot"]]), act, 0.2, L.stream())
-            Fp8.last_out = Fp8.handle(so, t8, act) if t8 is not None else None
+            if side is not None and t8 is not None:
+                side.f8_out = Fp8.handle(so, t8, act)
         else:
             L.call("ups_maxpool2_fwd", L.ptr(x), L.ptr(y), L.dt(x), n, h, w, c, L.stream())
         ctx.save_for_backward(x)
@@ -1421,7 +1428,7 @@ class MaxPoolFn(torch.autograd.Function):
         g = g.contiguous()
         gx = torch.empty_like(x)
         L.call("ups_maxpool2_bwd", L.ptr(x), L.ptr(g), L.ptr(gx), L.dt(x), n, h, w, c, L.stream())
-        return gx, None, None
+        return gx, None, None, None
 
 
 class VggPreFn(torch.autograd.Function):
