@@ -324,7 +324,7 @@ def test_runner_trains_from_the_augmented_device_iterator(graph, dev, tmp_path):
     it = runner.main(["-t", str(ypath), "-p", str(root), "--strict-dataset"])
     assert it.global_step == steps
     if graph:
-        assert it._graph_enabled and it._g is not None and it._g["graph"] is not None, "no step was replayed"
+        assert it._graph_enabled and it.graph is not None and it.graph.graphs, "no step was replayed"
     log = (root / "train" / "log.txt").read_text()
     assert "SYNTHETIC" not in log
     losses = re.findall(r"\[LoggingHook\]: (loss_[a-z0-9_]+): (\S+)", log)

@@ -62,8 +62,8 @@ def _worker(rank, world, port, out):
         if step == 0:
             grads0 = {k: g["flat"]["g"].detach().cpu().clone() for k, g in model.bank.groups.items()}
     torch.cuda.synchronize()
-    # the encoder_0 head slice is all-reduced early (Trainer._hook_early_reduce): the hook must be installed and consumed
-    assert tr._early_hooked and not tr._early
+    # the encoder_0 head slice is all-reduced early (GradSync.hook_head): the hook must be installed and consumed
+    assert tr.sync.head_hooked and tr.sync.head_inflight is None
     assert any(lay.after_wgrad is not None for lay in model.nets.layers.values())
     out[rank] = {"params": {k: g["flat"]["p"].detach().cpu() for k, g in model.bank.groups.items()},
                  "grads0": grads0, "state": {k: float(v) for k, v in tr.state.items()}}
@@ -114,7 +114,7 @@ def _graph_worker(rank, world, port, out, use_graph, steps):
     for _ in range(steps):
         losses = tr.train_step(views, noise)
     torch.cuda.synchronize()
-    nseg = len(tr._g["graph"]["graphs"]) if use_graph and tr._g and tr._g["graph"] else 0
+    nseg = len(tr.graph.graphs) if use_graph and tr.graph else 0
     out[(use_graph, rank)] = {"params": {k: g["flat"]["p"].detach().cpu() for k, g in model.bank.groups.items()},
                               "state": {k: float(v) for k, v in tr.state.items()}, "segments": nseg,
                               "losses": {k: float(v) for k, v in losses.items()}, "step": tr.global_step}

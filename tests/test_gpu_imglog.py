@@ -312,7 +312,7 @@ def test_training_is_untouched_by_image_logs(hip_graph, dev):
     for k in off:
         assert torch.equal(off[k], on[k]), k
     if hip_graph:
-        assert tr._g is not None and tr._g["graph"] is not None, "the step was not captured"
+        assert tr.graph is not None and tr.graph.graphs, "the step was not captured"
     B = cfg["batch_size"]
     views = R.synthetic_views(cfg, seed=104)
     last, dbg = rendered[-1]

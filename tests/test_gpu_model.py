@@ -367,8 +367,8 @@ def test_hip_graph_replay_matches_eager(dev):
             losses = tr.train_step(views, noise)
             hist.append({k: float(v) for k, v in losses.items()})
         runs[mode] = (hist, {k: g["flat"]["p"].detach().cpu().clone() for k, g in model.bank.groups.items()},
-                      {k: float(v) for k, v in tr.state.items()}, tr.global_step, tr._g)
-    assert runs["graph"][4] is not None and runs["graph"][4]["graph"] is not None, "the graph was never captured"
+                      {k: float(v) for k, v in tr.state.items()}, tr.global_step, tr.graph)
+    assert runs["graph"][4] is not None and runs["graph"][4].graphs, "the graph was never captured"
     assert runs["eager"][3] == runs["graph"][3] == 7
     for a, b in zip(runs["eager"][0], runs["graph"][0]):
         assert a == b, (a, b)
@@ -659,10 +659,10 @@ def test_step_that_fails_after_an_early_adam_poisons_the_trainer(dev, tmp_path):
     the backward pass leaves encoder_1 / decoder_delta one optimizer step ahead of the other keys.  The trainer must not carry on
     as if nothing happened: it joins its streams, re-converts the weight copies and refuses further steps and checkpoints."""
     import upsparts_amd  # noqa: F401
-    from upsparts_amd import model as M
+    from upsparts_amd import stepsync as SS
     from upsparts_amd.model import TrainModel, Trainer
     from oracle import ref_model as R, configs
-    if not (M.EARLY_ADAM and M.LATE_JOIN):
+    if not (SS.EARLY_ADAM and SS.LATE_JOIN):
         pytest.skip("early per-key Adam is switched off in this environment")
     cfg = copy.deepcopy(configs.tiny_config())
     cfg.update(precision="bf16", vgg_widths=VGG_W)

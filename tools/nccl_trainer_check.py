@@ -2,7 +2,9 @@
 all-reduce (identity) exactly where the multi-GPU run issues it -- asynchronously, from inside the backward pass, beside the
 side streams, with the early encoder_0 head slice -- and the result must equal the run without collectives bit for bit.  A third
 run adds `hip_graph: True`: the step captured as a sequence of HIP graphs cut at the collectives, RCCL all-reduces issued eagerly
-between the replayed segments (model.Trainer._capture_step).
+between the replayed segments (stepsync.StepGraph).  The eager run with collectives also checks the reduce bookkeeping of
+stepsync.GradSync through Trainer.dp_wait_ms(): one entry per all-reduce in launch order, the encoder_0 head slice before the rest of
+its bucket, both together the whole bucket.
 Usage: UPS_FORCE_COLLECTIVES=1 python tools/nccl_trainer_check.py [towers]"""
 import copy, os, sys
 import torch
@@ -42,9 +44,19 @@ for use_nccl, use_graph in ((False, False), (True, False), (True, True)):
     torch.cuda.synchronize()
     res.append({k: grp["flat"]["p"].detach().cpu().clone() for k, grp in model.bank.groups.items()})
     if use_nccl:
-        assert tr._early_hooked
+        assert tr.sync.head_hooked
+    if use_nccl and not use_graph:
+        waits = list(tr.dp_wait_ms())
+        assert waits[0] == "side_streams", waits
+        names, sizes = [w.split(":")[0] for w in waits[1:]], [int(w.split(":")[1][:-1]) for w in waits[1:]]
+        order = ("encoder_1", "decoder_delta", "decoder_visualize", "mi0_discriminator", "mi1_discriminator", "mi_estimator")
+        # one entry per all-reduce, in the order the backward segments complete; the head slice of encoder_0 before the rest of its bucket
+        assert names == [k for k in order if k in tr.loss_keys()] + ["encoder_0[head]", "encoder_0"], waits
+        assert len(tr.sync.dp_wait_events[-1][1]) == len(names), "a step launched an all-reduce twice"     # (the mapping would merge them)
+        assert sum(sizes[-2:]) == 4 * model.bank.groups["encoder_0"]["flat"]["g"].numel(), waits
+        print("reduce bookkeeping:", waits)
     if use_graph:
-        nseg = len(tr._g["graph"]["graphs"])
+        nseg = len(tr.graph.graphs)
         assert nseg >= 5, nseg            # four bucket boundaries (world size 1 has no scalar boundary) -> five graphs
         print("graph mode: {} segments".format(nseg))
 dist.destroy_process_group()

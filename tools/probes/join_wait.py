@@ -21,15 +21,15 @@ batch = {k: (torch.rand(64, 128, 128, 3, generator=g) * 2 - 1).to(dev) for k in 
 for _ in range(8):
     tr.train_step(batch)
 torch.cuda.synchronize()
-tr._join_events = []
-tr._tail_events = []
+tr.sync.join_events.clear()
+tr.sync.tail_events.clear()
 t0 = time.perf_counter()
 for _ in range(20):
     tr.train_step(batch)
 torch.cuda.synchronize()
 dt = (time.perf_counter() - t0) / 20
-w = [a.elapsed_time(b) for a, b in tr._join_events]
-t = [a.elapsed_time(b) for a, b in tr._tail_events]
+w = [a.elapsed_time(b) for a, b in tr.sync.join_events]
+t = [a.elapsed_time(b) for a, b in tr.sync.tail_events]
 print("{} streams={} step {:.2f} ms; wait at the critics' join: mean {:.3f} ms, max {:.3f} ms; wait for the weight-gradient streams at the end of "
       "the backward pass: mean {:.3f} ms, max {:.3f} ms".format(cfg["precision"], os.environ.get("UPS_CRITIC_STREAMS", "1"), dt * 1e3, sum(w) / len(w), max(w),
                                                                 sum(t) / len(t), max(t)))

@@ -42,7 +42,7 @@ def child(steps):
     for _ in range(5):
         tr.train_step(batch)
     torch.cuda.synchronize()
-    tr._dp_wait_events = []
+    tr.sync.dp_wait_events.clear()
     t0 = time.perf_counter()
     for _ in range(steps):
         tr.train_step(batch)

@@ -15,7 +15,6 @@ The part path between B and C (soft-max, hard max, moments, rectangles, priors) 
 its forward and its fused backward are single HIP kernels.
 """
 import ctypes as C
-import contextlib
 import math
 import os
 import warnings
@@ -30,23 +29,18 @@ from . import nets as N
 from . import ops
 from . import dist as D
 from . import tps as TPS
+from . import stepsync as SS
 from . import imglog as IL
 from .nets import Act
 from .schedules import make_var, make_linear_var
 
 
 PERCEPTUAL_INPUTS = ("native", "resize256", "resize256_crop224")
-LATE_JOIN = SW.flag("UPS_LATE_JOIN")      # A/B switch: single rank joins the weight-gradient stream only before Adam
 # A/B switch (off: measured neutral, 2 032 / 2 034 against 2 017 / 2 057 img/s): enqueue the mask decoder's forward before the critics
 STATE_KERNEL = SW.flag("UPS_STATE_KERNEL")          # A/B switch: the state update as one launch (ups_state_update)
 STATE_KEYS = ("avg_acc0", "avg_acc1", "avg_acc_error", "avg_loss_dis0", "avg_loss_dis1", "avg_mim", "avg_independent_mim", "loa", "lor")
 CRITIC_STREAMS = SW.flag("UPS_CRITIC_STREAMS")      # A/B switch: the three critics on three side streams
 EARLY_ALPHA = SW.flag("UPS_EARLY_ALPHA")      # A/B switch: appearance code on "aux" beside the pose encoder
-JOIN_TIMING = SW.flag("UPS_JOIN_TIMING")
-# data parallel: bucket all-reduces are enqueued from the weight-gradient stream's position instead of after a join of the launching
-# stream with it (UPS_DP_SIDE_LAUNCH=0: the round-4 form, A/B runs)
-DP_SIDE_LAUNCH = SW.flag("UPS_DP_SIDE_LAUNCH")
-EARLY_ADAM = SW.flag("UPS_EARLY_ADAM")    # A/B switch: ... and queues each key's Adam behind its weight gradients
 
 
 def _scalar(v, device):
@@ -77,7 +71,7 @@ class TrainModel(object):
         self.df = N.is_48c(config)          # DeepFashion SB_model48c variant (two inputs, no rectangles, extra decoders)
         self.nets = N.Nets(config, self.device, seed if seed is not None else config.get("seed", 0))
         self.bank = self.nets.bank
-        self._last = {}
+        self._last, self._tps = {}, {}
 
     # model.py:260-263
     @property
@@ -95,7 +89,7 @@ class TrainModel(object):
     def outputs(self):
         out = dict(self._last)
         if self.use_tps:
-            out.update(getattr(self, "_tps", {}))        # model.py:272-279
+            out.update(self._tps)        # model.py:272-279
         return out
 
     def to_act(self, x_f32, fmt=None, out=None):
@@ -448,12 +442,12 @@ class Trainer(object):
         self._gen = torch.Generator(device=d)
         self._gen.manual_seed(D.shard_seed(config.get("noise_seed", 4321), kwargs.get("rank", 0)))      # TPS uniforms, crop window
         self._noise = ops.NoiseStream(D.shard_seed(config.get("noise_seed", 4321), kwargs.get("rank", 0)))  # the sampling noise
-        self._lazy_logs, self._done_thunk = None, None
+        self._lazy_logs, self._done_thunk, self._last_ckpt = None, None, None
         self.switches_report = SW.report()       # the environment switches that differ from their defaults (switches.py), logged once
         if self.logger:
             self.logger.info(self.switches_report)
-        self._adam_done, self._step_graph_lr = set(), None
-        self._adam_stepped = set()      # keys whose Adam step of the RUNNING training step has been enqueued (cleared when the step ends)
+        # the gradient hand-off of the running step (the keys that have stepped ...); a stepsync.StepGraph once graph mode is used
+        self.sync, self.graph = SS.GradSync(self), None
         # `stream_plan` (full | compact | auto): how the step's logical streams map onto HIP streams (ops.Streams.set_plan).  auto =
         # full on one rank, compact under data parallelism, where the collectives' stream needs a hardware queue of its own
         # (measured with a stand-in for the collectives on one GPU: tools/probes/stream_dp.py, profiles/round5_stream_dp.txt)
@@ -462,13 +456,9 @@ class Trainer(object):
             plan = "compact" if (self.world_size > 1 or D.FORCE_COLLECTIVES) else "full"
         self.stream_plan = plan
         ops.Streams.set_plan(plan)
-        self._reduce_marks = []         # (key, bytes) of the bucket all-reduces of the running step, in launch order
         self._poisoned = None           # set when a step failed half-way through its optimizer updates (_after_failed_step)
         self._losses = OrderedDict((k, None) for k in self.loss_keys())
-        self._early, self._early_hooked = {}, False
         self._graph_enabled = bool(config.get("hip_graph", SW.flag("UPS_GRAPH")))
-        self._g = None
-        self._cap = None                # set while the step is being captured into HIP graphs (_capture_step)
         # `log_images` (default off): the reference's img_ops (model.py:968-1053) as uint8 canvases on the steps that log scalars
         self.log_images = bool(config.get("log_images", False))
         self._want_images = False       # set for the duration of a train_step(..., images=True)
@@ -724,9 +714,10 @@ class Trainer(object):
     # ------------------------------------------------------------------ one session.run(train_op)
     def train_step(self, batch, noise=None, images=False):
         """One session.run(train_op).  images=True: the step's image logs are rendered into ``img_ops`` as well (``_render_images``;
-        ``iterate`` asks for them on the steps it logs scalars when the config sets ``log_images``).  With ``hip_graph: True`` the whole step -- ~1 000 kernel launches on three streams -- is
-        captured once into HIP graphs and replayed (one graph on a single GPU; under data parallelism a sequence of graphs cut
-        at the collectives); see ``_graph_step`` / ``_capture_step``."""
+        ``iterate`` asks for them on the steps it logs scalars when the config sets ``log_images``).  With ``hip_graph: True`` the whole
+        step -- ~1 000 kernel launches on three streams -- is captured once into HIP graphs and replayed (one graph on a single GPU;
+        under data parallelism a sequence of graphs cut at the collectives): ``_graph_step`` / ``stepsync.StepGraph``.  The optimizer
+        keys' hand-off is ``self.sync`` (``stepsync.GradSync``); a step that raises after some keys have stepped poisons the trainer."""
         ops.Fp8.activate(self.model.fp8)
         if self._poisoned:
             raise RuntimeError("this trainer's state is inconsistent: " + self._poisoned + " -- restore a checkpoint (Trainer.initialize)")
@@ -745,9 +736,7 @@ class Trainer(object):
         (EARLY_ADAM) leaves those keys at step t + 1 and the others at t, with the converted weight copies stale.  Make the
         device state coherent (side streams joined, copies re-converted from whatever the masters now hold) and refuse further
         steps / checkpoints: the run has to restart from its last checkpoint."""
-        done = sorted(self._adam_done | self._adam_stepped)     # early (side-stream) steps AND a partly run final Adam loop
-        self._adam_done, self._adam_stepped = set(), set()
-        ops.Streams.master_busy.clear()
+        done = self.sync.abort()
         if not done:
             return
         try:
@@ -780,118 +769,42 @@ class Trainer(object):
         """Static input / noise buffers + a device scalar for Adam's step size; the graph is (re)captured after two eager
         steps and whenever a schedule constant changes (staircases move every few thousand steps).  The small-batch
         configs of the reference (batch 8: ~2 400 launches for 24 ms of GPU work) are launch-bound without it."""
-        dev = self.device
         B, S = batch["view0"].shape[0], batch["view0"].shape[1]
-        if self._g is not None and tuple(next(iter(self._g["in"].values())).shape[:2]) != (B, S):
-            self._g = None                       # the capture bakes in shapes and workspace pointers: start over
-        if self._g is None:
-            self._g = {"in": {k: torch.empty((B, S, S, 3), dtype=torch.float32, device=dev) for k in self.model.inputs},
-                       "noise": {k: torch.empty_like(v) for k, v in self.draw_noise(B).items()},
-                       "lr": torch.zeros(1, dtype=torch.float32, device=dev), "graph": None, "sig": None, "eager": 0}
-        g = self._g
-        for k, buf in g["in"].items():
+        if self.graph is None or self.graph.shape != (B, S):     # the capture bakes in shapes and workspace pointers: start over
+            self.graph = None                    # (the old buffers go before the new ones are made)
+            self.graph = SS.StepGraph(self, B, S)
+        g = self.graph
+        for k, buf in g.inputs.items():
             buf.copy_(batch[k], non_blocking=True)
-        for k, buf in g["noise"].items():
-            if noise is None:
-                if k == "crop_yx":
-                    buf.random_(0, 33, generator=self._gen)
-                else:
-                    self._noise.fill(buf)
+        for k, buf in g.noise.items():
+            if k == "crop_yx" and (noise is None or "crop_yx" not in noise):     # (explicit noise without a window corner: drawn as usual)
+                buf.random_(0, 33, generator=self._gen)
+            elif noise is None:
+                self._noise.fill(buf)
             elif k == "eps_l" and "eps_l" not in noise:          # explicit noise in the fixtures' two-tensor form
                 buf[:B].copy_(noise["eps_l0"], non_blocking=True)
                 buf[B:].copy_(noise["eps_l1"], non_blocking=True)
-            elif k == "crop_yx" and "crop_yx" not in noise:      # explicit noise without a window corner: draw it as usual
-                buf.random_(0, 33, generator=self._gen)
             else:
                 buf.copy_(noise[k], non_blocking=True)
         t = self.model.bank.groups[self.loss_keys()[0]]["t"] + 1
         lr = self.learning_rate()
-        g["lr"].fill_(lr * math.sqrt(1.0 - self.beta2 ** t) / (1.0 - self.beta1 ** t))
+        g.lr.fill_(lr * math.sqrt(1.0 - self.beta2 ** t) / (1.0 - self.beta1 ** t))
         sig = self._schedule_signature() + (lr > 0,)
+        run_step = lambda: self._step_impl(g.inputs, g.noise, graph_lr=g.lr)
         # warm-up: kernel attributes, side streams, allocator pools; fp8: the copy hand-off settles over four steps (first maxima,
         # first copies, unread producers going quiet) and the captured graph freezes whatever it sees
-        if g["eager"] < (5 if ops.Fp8.enabled else 2):
-            g["eager"] += 1
-            out = self._step_impl(g["in"], g["noise"], graph_lr=g["lr"])
+        if g.eager < (5 if ops.Fp8.enabled else 2):
+            g.eager += 1
+            out = run_step()
             self._after_graph_step()
             return out
-        if g["graph"] is None or g["sig"] != sig:
-            g["graph"], g["sig"] = self._capture_step(g), sig   # (capturing does not execute: the replay below runs the step)
-        self._replay_step(g["graph"])
+        if not g.graphs or g.sig != sig:
+            g.capture(run_step, sig)    # (capturing does not execute: the replay below runs the step)
+        g.replay()
         self._after_graph_step()
         if self._want_images:           # outside the captured graphs, after the replay, from the buffers the capture owns
-            self._render_images(g["graph"]["img_src"], self.global_step - 1)
+            self._render_images(g.img_src, self.global_step - 1)
         return _LazyLosses(self)
-
-    # Data parallel: a collective cannot sit inside a captured region on every backend (gloo reduces on the host), and the
-    # buckets should start their all-reduce as early as in the eager step.  The step is therefore captured as a SEQUENCE of
-    # graphs, cut wherever the eager step talks to the other ranks: after the backward segment of each group of optimizer keys
-    # (bucket all-reduce, asynchronous, overlapping the next segments) and before the Lagrangian / EMA update (the averaged
-    # batch-mean scalars).  One python pass records all segments (the tape objects simply live on between them; the graphs
-    # share one memory pool and are always replayed in capture order); at replay the collectives run eagerly in between.
-    def _capture_step(self, g):
-        dev = self.device
-        torch.cuda.synchronize(dev)
-        cap = {"graphs": [], "bounds": [], "pool": torch.cuda.graph_pool_handle(), "stream": torch.cuda.Stream(dev), "cur": None}
-        cap["stream"].wait_stream(torch.cuda.current_stream(dev))
-        self._cap = cap
-        try:
-            with torch.cuda.stream(cap["stream"]):
-                self._segment_begin()
-                self._step_impl(g["in"], g["noise"], graph_lr=g["lr"])
-                self._segment_end()
-        except BaseException:
-            # leave the stream usable for the eager trainer: end the open capture (its graph is discarded), rejoin the side
-            # streams, and stop trying to capture
-            try:
-                with torch.cuda.stream(cap["stream"]):
-                    if cap["cur"] is not None:
-                        ops.Streams.join(dev, names=("wgrad", "aux1", "aux2", "aux", "pre"))
-                        cap["cur"].capture_end()
-            except Exception:
-                pass
-            self._graph_enabled, self._g = False, None
-            raise
-        finally:
-            self._cap = None
-        torch.cuda.current_stream(dev).wait_stream(cap["stream"])
-        torch.cuda.synchronize(dev)
-        return cap
-
-    def _segment_begin(self):
-        cap = self._cap
-        cap["cur"] = torch.cuda.CUDAGraph()
-        cap["cur"].capture_begin(pool=cap["pool"])
-
-    def _segment_end(self):
-        cap = self._cap
-        ops.Streams.join(self.device, names=("wgrad", "aux"))      # every forked stream rejoins before the capture ends
-        cap["cur"].capture_end()
-        cap["graphs"].append(cap["cur"])
-        cap["cur"] = None
-
-    def _boundary(self, kind, payload):
-        """Called from inside the step while it is being captured: close the running segment, note what has to happen between
-        it and the next one (kind "grads": all-reduce these keys' buckets; "scalars": average this tensor), open the next."""
-        self._segment_end()
-        self._cap["bounds"].append((kind, payload))
-        self._segment_begin()
-
-    def _replay_step(self, cap):
-        bank = self.model.bank
-        last_grads = max([i for i, (kind, _) in enumerate(cap["bounds"]) if kind == "grads"], default=-1)
-        handles = []
-        for i, graph in enumerate(cap["graphs"]):
-            graph.replay()
-            if i < len(cap["bounds"]):
-                kind, payload = cap["bounds"][i]
-                if kind == "grads":
-                    for k in payload:
-                        handles.append(D.allreduce_bucket(bank.groups[k]["flat"]["g"], self.world_size, self.process_group))
-                    if i == last_grads:
-                        D.wait_all(handles)             # the next segment is the optimizer
-                else:
-                    D.average_scalars(payload, self.world_size, self.process_group)
 
     def _after_graph_step(self):
         # (WeightVersion is not bumped: the step's own batched weight_prep has already refreshed every converted copy)
@@ -1063,7 +976,7 @@ class Trainer(object):
         cur = torch.cuda.current_stream(self.device)
         # (not in a captured step: replayed from a HIP graph the three branches cost more than they save -- 1 887 against 1 919 img/s
         # with one critic stream, eager 1 979 -- so a capture keeps the one-stream form)
-        multi = ops.Streams.enabled and ops.Streams.on_aux(self.device) and CRITIC_STREAMS and self._step_graph_lr is None
+        multi = ops.Streams.enabled and ops.Streams.on_aux(self.device) and CRITIC_STREAMS and c.graph_lr is None
         # (the two extra critic streams stay created even when the critics run as grouped launches: which streams share a hardware
         # queue depends on the creation order, and the order without them sits in the slower cluster -- docs/design/negative_results.md)
         sides = [cur] + ([ops.Streams.get("aux{}".format(i), self.device) for i in (1, 2)] if multi else [cur, cur])
@@ -1204,7 +1117,7 @@ class Trainer(object):
         rec_params = [bank.params[n] for k in rec_keys for n in bank.groups[k]["names"]]
         gr = torch.autograd.grad([c.auto_rec], [c.hard0, c.hard1] + rec_params)
         c.g_hard0, c.g_hard1 = gr[0].contiguous(), gr[1].contiguous()
-        return self._launch_reduce(rec_keys)
+        self.sync.segment_done(rec_keys)
 
     def _priors(self, c):
         """Mask priors: fused forward sums + fused analytic backward (model.py:652-797).  One backward launch per view emits both
@@ -1244,10 +1157,9 @@ class Trainer(object):
         if "decoder_visualize" in c.keys:
             dv_params = [bank.params[n] for n in bank.groups["decoder_visualize"]["names"]]
             torch.autograd.grad([c.l_mean], dv_params, grad_outputs=[c.dl_tot], retain_graph=True)
-        pending = self._launch_reduce([k for k in ("decoder_visualize",) if k in c.keys])
+        self.sync.segment_done([k for k in ("decoder_visualize",) if k in c.keys])
         with ops.skip_wgrad():
             c.gz = torch.autograd.grad([c.l_mean], [c.z_leaf], grad_outputs=[c.dl_rec])[0].float().view(2 * c.B, c.Z)
-        return pending
 
     def _bwd_pose(self, c):
         """A backward (model.py:739, 909, 930): d rec / d z (from B), the adversarial gradient on the joint sample of mi0 and the
@@ -1268,9 +1180,7 @@ class Trainer(object):
         gp1 = ops.latent_bwd(c.pe_v1, c.noise["eps_pi1"][None], [1.0], c.gz[B:].contiguous()[None], None, 0.0)
         g_pe = torch.cat([gp0, gp1], 0).view_as(c.pe)
         e0_params = [bank.params[n] for n in bank.groups["encoder_0"]["names"]]
-        if (self.world_size > 1 or D.FORCE_COLLECTIVES) and not self._early_hooked:      # layers exist once the first forward has run
-            self._hook_early_reduce()
-            self._early_hooked = True
+        self.sync.hook_head()           # (data parallel, once: the head's slice of the bucket starts its all-reduce from inside the backward pass)
         torch.autograd.grad([c.pe], e0_params, grad_outputs=[g_pe])
 
     def _next_state(self, c):
@@ -1279,8 +1189,8 @@ class Trainer(object):
         step used the pre-update state."""
         cfg, st, mi = self.config, c.st, c.mi
         stats = torch.stack([c.mim.detach(), c.ind_mim.detach(), c.acc0, c.acc1, c.loss_dis0.detach(), c.loss_dis1.detach()])
-        if getattr(self, "_cap", None) is not None and self.world_size > 1:
-            self._boundary("scalars", stats)             # (the tensor lives in the graphs' pool: same address at every replay)
+        if self.graph is not None and self.graph.capturing and self.world_size > 1:
+            self.graph.boundary("scalars", stats)             # (the tensor lives in the graphs' pool: same address at every replay)
         else:
             D.average_scalars(stats, self.world_size, self.process_group)
         new = dict(st)
@@ -1408,8 +1318,9 @@ class Trainer(object):
         """One training step on the launching stream (+ the "pre", "aux" and "wgrad" side streams): forward A -> D (aux) -> B ->
         C, backward C -> priors -> B -> A, each optimizer key's bucket reduced as soon as its segment is complete, Adam, state."""
         dev = self.device
-        self._step_graph_lr, self._adam_done, self._adam_stepped = graph_lr, set(), set()
+        self.sync.begin(graph_lr)
         c = self._step_begin(batch, noise)
+        c.graph_lr = graph_lr
         self._fwd_pose(c)
         # (enqueueing the mask decoder's forward pass BEFORE the critics' block measured neutral twice, UPS_CRITICS_LATE in round 5:
         # retired in round 6)
@@ -1422,24 +1333,16 @@ class Trainer(object):
             self._critics(c)
         self._fwd_masks(c)
         self._fwd_reconstruction(c)
-        pending = self._bwd_reconstruction(c)
+        self._bwd_reconstruction(c)
         self._priors(c)
-        pending += self._bwd_mask_decoder(c)
-        # the critics' block (aux stream) must be complete from here on: g_adv, the critic losses and their gradients
-        if JOIN_TIMING and graph_lr is None:       # debug: how long the launching stream sits at this join (tools/probes/join_wait.py)
-            ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
-            ev[0].record()
-            ops.Streams.join(dev, names=("aux",))
-            ev[1].record()
-            self._join_events = (getattr(self, "_join_events", []) + [ev])[-256:]       # (bounded: a debug aid for short runs)
-        else:
-            ops.Streams.join(dev, names=("aux",))
-        pending += self._launch_reduce([k for k in ("mi0_discriminator", "mi1_discriminator", "mi_estimator") + N.EXTRA_48C
-                                        if k in c.keys])
+        self._bwd_mask_decoder(c)
+        # the critics' block (aux stream) must be complete from here on: g_adv, the critic losses and their gradients (JOIN_TIMING: timed)
+        self.sync.join("join", names=("aux",))
+        self.sync.segment_done([k for k in ("mi0_discriminator", "mi1_discriminator", "mi_estimator") + N.EXTRA_48C if k in c.keys])
         self._bwd_pose(c)
         # ---- gradient all-reduce (data parallel) + TF Adam per key
-        pending += self._launch_reduce([k for k in ("encoder_0",) if k in c.keys])
-        self._finish_step(c.keys, pending, graph_lr)
+        self.sync.segment_done([k for k in ("encoder_0",) if k in c.keys])
+        self.sync.finish(c.keys)
         new = self._next_state(c)
         build_logs = self._log_thunk(c)
         st = c.st
@@ -1460,105 +1363,11 @@ class Trainer(object):
         self._debug = {"l_mean": c.lm, "l": c.l, "m": c.m, "hard": c.hard, "px": c.px, "generated": c.gen.detach(),
                        "feat": c.feat.detach(), "dl_tot": c.dl_tot, "dl_rec": c.dl_rec, "g_hard0": c.g_hard0, "g_hard1": c.g_hard1,
                        "pe": c.pe2}
-        if self._cap is not None:       # the capture owns these buffers: every replay refills them, _graph_step renders from them
-            self._cap["img_src"] = self._image_sources(c)
+        if self.graph is not None and self.graph.capturing:     # the capture owns these buffers: every replay refills them, _graph_step renders from them
+            self.graph.img_src = self._image_sources(c)
         elif self._want_images:
             self._render_images(self._image_sources(c), c.step)
         return _LazyLosses(self)
-
-    def _hook_early_reduce(self):
-        """The 1x1 head of encoder_0 (258 x 33152 weights = 34 of the key's 54.6 MB) is the FIRST weight gradient of the
-        last backward segment: its slice of the flat bucket starts its all-reduce as soon as it has been enqueued, so
-        only the remaining 20 MB follow the end of the backward pass."""
-        grp = self.model.bank.groups["encoder_0"]
-        head = max((n for n in grp["names"] if n.endswith("/V")), key=lambda n: int(n.split("conv2d_")[1].split("/")[0]))
-        prefix = head[:-2]
-        off = 0
-        for n in grp["names"]:
-            if n.startswith(prefix + "/"):
-                break
-            off += self.model.bank.params[n].numel()
-        tail = sum(self.model.bank.params[n].numel() for n in grp["names"] if n.startswith(prefix + "/"))
-        assert off + tail == grp["flat"]["g"].numel(), "the head's variables must close the flat bucket"
-        trainer = self
-
-        def launch():
-            if "encoder_0" in trainer._early or getattr(trainer, "_cap", None) is not None:
-                return                      # (graph capture: the whole bucket is reduced at the segment boundary)
-            if ops.Streams.enabled and DP_SIDE_LAUNCH:       # behind the head's weight gradient on ITS stream (see _launch_reduce)
-                side = ops.Streams.get("wgrad", trainer.device)
-                w2 = ops.Streams._pool.get(("wgrad2", torch.device(trainer.device).index))
-                if w2 is not None:
-                    side.wait_stream(w2)
-                with torch.cuda.stream(side):
-                    h = D.allreduce_bucket(grp["flat"]["g"][off:], trainer.world_size, trainer.process_group)
-            else:
-                ops.Streams.join(trainer.device, names=("wgrad",))
-                h = D.allreduce_bucket(grp["flat"]["g"][off:], trainer.world_size, trainer.process_group)
-            trainer._early["encoder_0"] = (off, h)
-
-        for key, lay in self.model.nets.layers.items():
-            if key[0] == prefix:
-                lay.after_wgrad = launch
-
-    def _launch_reduce(self, key_list):
-        """Called when the backward segment of these optimizer keys is complete: their weight gradients (side stream)
-        are joined and each key's flat gradient bucket starts its RCCL all-reduce (sum; 1/world is folded into Adam),
-        overlapping the backward segments that are still to run.  Returns the work handles."""
-        if not key_list:
-            return []
-        if getattr(self, "_cap", None) is not None:      # graph capture under data parallelism: a segment boundary
-            if self.world_size > 1 or D.FORCE_COLLECTIVES:
-                self._boundary("grads", list(key_list))
-            return []
-        if self.world_size == 1 and not D.FORCE_COLLECTIVES and LATE_JOIN:
-            # a single rank has nothing to reduce: the launching stream need not wait for the weight-gradient stream here (it
-            # would idle whenever that stream lags); both meet before the end of the step (_finish_step).  The tensors the side
-            # stream reads stay referenced until then (ops.Streams.keep).  The keys' Adam updates are queued right BEHIND their
-            # weight gradients on that stream (EARLY_ADAM): the fp32 master weights are not read again this step -- every
-            # convolution works on the converted copies, refreshed once all keys have stepped -- so the 0.9 GB optimizer stream
-            # runs in the shadow of the remaining backward pass instead of on an otherwise empty chip at the end.
-            if EARLY_ADAM and ops.Streams.enabled and self._step_graph_lr is None:
-                side = ops.Streams.get("wgrad", self.device)
-                side.wait_stream(torch.cuda.current_stream(self.device))     # (critics: their gradients were taken on "aux", joined by now)
-                side.wait_stream(ops.Streams.get("wgrad2", self.device))     # (the CoordConv rows of these keys' weight gradients)
-                with torch.cuda.stream(side):
-                    self._adam(key_list, None)
-                    ev = side.record_event()
-                # a converted-weight cache entry created later in this step (a new (dtype, size) instance, the depth-to-space or
-                # fp8 copies) reads the fp32 master: it must see the finished update, not race with it (ops.WeightCopy._wait_master)
-                for k in key_list:
-                    ops.Streams.master_busy[k] = ev
-                self._adam_done.update(key_list)
-            return []
-        bank = self.model.bank
-        handles = []
-        # The all-reduce of a bucket has to wait for the segment's weight gradients -- they run on the "wgrad" side stream -- but
-        # the LAUNCHING stream does not: the collective is enqueued from the side stream's position (torch's process group orders
-        # its own stream behind the stream that is current at the call), so the backward pass goes on while the bucket is reduced.
-        # (Until round 5 the launching stream joined the side stream here: under data parallelism it idled at every segment
-        # boundary for as long as the weight-gradient queue lagged -- the 2 % a single rank gains from LATE_JOIN.)
-        if ops.Streams.enabled and DP_SIDE_LAUNCH:
-            side = ops.Streams.get("wgrad", self.device)
-            side.wait_stream(torch.cuda.current_stream(self.device))      # (critics: their gradients were taken on "aux", joined by now)
-            w2 = ops.Streams._pool.get(("wgrad2", torch.device(self.device).index))
-            if w2 is not None:
-                side.wait_stream(w2)                                       # the CoordConv rows of these keys' weight gradients
-            ctx = torch.cuda.stream(side)
-        else:
-            ops.Streams.join(self.device, names=("wgrad",))
-            ctx = contextlib.nullcontext()
-        with ctx:
-            for k in key_list:
-                g = bank.groups[k]["flat"]["g"]
-                early = self._early.pop(k, None)
-                if early is not None:            # the tail slice is already in flight (see _hook_early_reduce)
-                    handles.append(early[1])
-                    self._reduce_marks.append((k + "[head]", (g.numel() - early[0]) * 4))      # one mark per handle (dp_wait_ms)
-                    g = g[:early[0]]
-                handles.append(D.allreduce_bucket(g, self.world_size, self.process_group))
-                self._reduce_marks.append((k, g.numel() * 4))
-        return handles
 
     def _adam(self, keys, graph_lr):
         """One fused TF-Adam launch per key on the current stream (Appendix A.12); advances the keys' step counters (eager mode)."""
@@ -1573,63 +1382,20 @@ class Trainer(object):
             if graph_lr is not None:
                 lr_t = graph_lr
             else:
-                grp["t"] += 1
-                self._adam_stepped.add(k)         # (for _after_failed_step: this key's counter and weights have moved)
-                t = grp["t"]
+                t = grp["t"] + 1
                 lr_t = lr * lr_scale.get(k, 1.0) * math.sqrt(1.0 - self.beta2 ** t) / (1.0 - self.beta1 ** t)
                 if self.grad_clip_norm > 0:         # tf.clip_by_global_norm over the key's variables (device side, no sync)
                     gn = torch.linalg.vector_norm(f["g"]) / self.world_size
                     f["g"].mul_(torch.clamp(self.grad_clip_norm / gn.clamp_min(1e-30), max=1.0))
             ops.adam_step(f["p"], f["g"], f["m"], f["v"], lr_t, self.beta1, self.beta2, self.adam_eps, 1.0 / self.world_size)
+            # enqueued: this key's weights and counter have moved (for _after_failed_step, key by key).  AFTER the call: adam_step raises on
+            # a rejected argument or a refused launch, i.e. with nothing enqueued; an asynchronous fault cannot be pinned to a key anyway
+            if graph_lr is None:
+                grp["t"] = t
+                self.sync.stepped.add(k)
 
-    def _finish_step(self, keys, handles, graph_lr=None):
-        """Wait for the buckets, then one fused Adam launch per key (tf.train.AdamOptimizer semantics, Appendix A.12).
-        graph_lr: device scalar holding lr_t (HIP-graph mode; the python step counters then advance outside)."""
-        if JOIN_TIMING and graph_lr is None:       # debug: the tail of the weight-gradient stream that nothing hides (join_wait.py)
-            ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
-            ev[0].record()
-            ops.Streams.join(self.device)
-            ev[1].record()
-            self._tail_events = (getattr(self, "_tail_events", []) + [ev])[-256:]
-        else:
-            timed = bool(handles) and graph_lr is None and any(h is not None for h in handles) and not torch.cuda.is_current_stream_capturing()
-            if timed:       # data parallel: what the launching stream WAITS at the end of the backward pass, split into its parts
-                evs = [torch.cuda.Event(enable_timing=True) for _ in range(len(handles) + 2)]
-                evs[0].record()
-            ops.Streams.join(self.device)
-            if timed:
-                evs[1].record()
-                for i, h in enumerate(handles):
-                    if h is not None:
-                        h.wait()
-                    evs[2 + i].record()
-                self._dp_wait_events = (getattr(self, "_dp_wait_events", []) + [(evs, list(self._reduce_marks))])[-64:]
-                handles = []
-        self._reduce_marks = []
-        D.wait_all(handles)
-        self._adam([k for k in keys if k not in self._adam_done], graph_lr)
-        self._adam_done, self._adam_stepped = set(), set()
-        ops.Streams.master_busy.clear()         # (the join above ordered this stream behind every early Adam)
-        ops.Streams.epoch += 1                  # lazy weight conversions of this step are ordered before everything that follows
-        # one launch for every layer's blocked-K weights + CoordConv tables, one each for the other copies; then the fp8 scales
-        ops.weights_changed(self.model.nets.prep, bump=graph_lr is None)
-
-    def dp_wait_ms(self):
-        """Data parallel: mean time per step the launching stream waited at the end of the backward pass -- for the weight-gradient
-        streams to drain (`side_streams`), then, bucket by bucket in launch order, for each gradient all-reduce that had not
-        finished by then (`<key>` with its bytes; 0 when the collective was fully hidden behind the backward pass).  Synchronises."""
-        rec = getattr(self, "_dp_wait_events", [])
-        if not rec:
-            return None
-        torch.cuda.synchronize(self.device)
-        out, n = OrderedDict(), 0
-        for evs, marks in rec:
-            n += 1
-            out["side_streams"] = out.get("side_streams", 0.0) + evs[0].elapsed_time(evs[1])
-            for i in range(len(evs) - 2):
-                key = "{}:{}B".format(*marks[i]) if i < len(marks) else "bucket{}".format(i)
-                out[key] = out.get(key, 0.0) + evs[1 + i].elapsed_time(evs[2 + i])
-        return OrderedDict((k, round(v / n, 4)) for k, v in out.items())
+    def dp_wait_ms(self):       # (bench.py reports it)
+        return self.sync.dp_wait_ms()
 
     # ------------------------------------------------------------------ image logs (model.py:968-1053; SB_model48c:1038-1094)
     def _image_sources(self, c):
@@ -1761,7 +1527,7 @@ class Trainer(object):
         out = OrderedDict()
         for k, v in self.log_ops.items():
             out[k] = float(v) if torch.is_tensor(v) else float(v)
-        out.update(getattr(self, "_val_logs", {}))      # val/overall, val/iou_<label> of the most recent validation (`val_freq`)
+        out.update(self._val_logs)      # val/overall, val/iou_<label> of the most recent validation (`val_freq`)
         return out
 
     # ------------------------------------------------------------------ periodic validation (`val_freq`, `val_csv`)
@@ -1858,7 +1624,7 @@ class Trainer(object):
         if not self.root or self.rank != 0:
             return
         path = os.path.join(self.root, "train", "checkpoints", "model.ckpt-{}".format(self.global_step))
-        if getattr(self, "_last_ckpt", None) == (path, self.global_step):
+        if self._last_ckpt == (path, self.global_step):
             return                        # this very state was just written (loop exit right after a periodic checkpoint)
         os.makedirs(os.path.dirname(path), exist_ok=True)
         tmp = path + ".tmp-{}".format(os.getpid())

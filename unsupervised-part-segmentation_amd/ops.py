@@ -59,7 +59,7 @@ class Streams(object):
     _pool = {}
     _raw = {}       # (name, device index) -> raw hipStream_t
     epoch = 0          # bumped by the trainer at the end of every step (all side streams joined): scopes WeightCopy.ready
-    master_busy = {}   # optimizer key -> event on the "wgrad" stream behind that key's early Adam launch (model.Trainer._launch_reduce)
+    master_busy = {}   # optimizer key -> event on the "wgrad" stream behind that key's early Adam launch (stepsync.GradSync: set in segment_done, cleared by finish / abort)
     _alive = {}     # device index -> tensors the "wgrad" stream still reads.  Holding references until the next join keeps
                     # their memory out of the allocator without record_stream (whose deferred frees made the caching
                     # allocator reserve ~9x the live set: 84 GB at B = 64); once the launching stream has waited for the
@@ -93,6 +93,21 @@ class Streams(object):
             cls._pool[key] = st
             cls._raw[key] = st.cuda_stream
         return st
+
+    @classmethod
+    def wgrad_behind(cls, device, current=True, create=False):
+        """Put the weight-gradient stream behind what a key's finished backward segment left in flight: the current stream
+        (`current`; not from inside the backward pass, where the hook of a layer runs right after its weight gradient was enqueued)
+        and then the CoordConv rows on "wgrad2".  `create`: make "wgrad2" if it does not exist yet -- the single-rank path does, the
+        data-parallel paths must not (which streams share a hardware queue depends on the order they are created in,
+        docs/design/negative_results.md).  Returns the "wgrad" stream."""
+        side = cls.get("wgrad", device)
+        if current:
+            side.wait_stream(torch.cuda.current_stream(device))
+        w2 = cls.get("wgrad2", device) if create else cls._pool.get(("wgrad2", torch.device(device).index))
+        if w2 is not None:
+            side.wait_stream(w2)
+        return side
 
     _pads = []
 

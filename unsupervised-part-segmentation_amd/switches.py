@@ -34,16 +34,16 @@ SWITCHES = OrderedDict([
     ("UPS_F8_PRODUCER", ("1", "ab", "ops.py", "0: fp8 copies converted by a separate pass instead of the producing epilogue")),
     ("UPS_TOWERS", ("1", "ab", "ops.py", "0: the critics' towers through the generic convolution path instead of the grouped launches")),
     ("UPS_STATE_KERNEL", ("1", "ab", "model.py", "0: the Lagrangian / EMA state update as ~30 torch launches instead of one kernel")),
-    ("UPS_LATE_JOIN", ("1", "ab", "model.py", "0: a single rank joins the weight-gradient stream at every segment boundary")),
-    ("UPS_EARLY_ADAM", ("1", "ab", "model.py", "0: every key's Adam at the end of the step instead of behind its weight gradients")),
+    ("UPS_LATE_JOIN", ("1", "ab", "stepsync.py", "0: a single rank joins the weight-gradient stream at every segment boundary")),
+    ("UPS_EARLY_ADAM", ("1", "ab", "stepsync.py", "0: every key's Adam at the end of the step instead of behind its weight gradients")),
     ("UPS_EARLY_ALPHA", ("1", "ab", "model.py", "0: the appearance code after the pose encoder instead of beside it on `aux`")),
     ("UPS_CRITIC_STREAMS", ("1", "ab", "model.py", "0: the three critics on one stream")),
     ("UPS_COORD_STREAM", ("1", "ab", "ops.py", "0: the CoordConv rows of the weight gradients on the weight-gradient stream itself")),
     ("UPS_NO_D2S", ("0", "ab", "ops.py", "1: the stride-2 layers' input gradient as four phase launches instead of one depth-to-space launch")),
-    ("UPS_DP_SIDE_LAUNCH", ("1", "ab", "model.py", "0: bucket all-reduces launched from the launching stream (it then waits for the weight gradients)")),
+    ("UPS_DP_SIDE_LAUNCH", ("1", "ab", "stepsync.py", "0: bucket all-reduces launched from the launching stream (it then waits for the weight gradients)")),
     ("UPS_DP_STANDIN", ("0", "debug", "dist.py", "1: every bucket all-reduce replaced by a device copy on its own stream (one-GPU stream-budget probe)")),
     ("UPS_FORCE_COLLECTIVES", ("0", "test", "dist.py", "1: issue the collectives at world size 1 (the RCCL call pattern test)")),
-    ("UPS_JOIN_TIMING", ("0", "debug", "model.py", "1: HIP events around the end-of-backward joins (tools/probes/join_wait.py)")),
+    ("UPS_JOIN_TIMING", ("0", "debug", "stepsync.py", "1: HIP events around the end-of-backward joins (tools/probes/join_wait.py)")),
     # ---- libupsparts_hip.so (the csrc/env.h helpers)
     ("UPS_ROWS_KERNEL", ("1", "test", "conv3x3_rows.hip", "0: row-stream layers through the patch / generic kernels; force: also at small batches (parity tests)")),
     ("UPS_S2_KERNEL", ("1", "ab", "conv3x3_s2.hip", "0: the other stride-2 forwards through the generic kernel")),
