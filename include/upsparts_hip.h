@@ -510,6 +510,43 @@ int ups_augment_field(const float* noise, const float* weights, int32_t n_fields
 int ups_part_confusion(const int64_t* pred, const uint8_t* gt, const uint8_t* lut, int32_t N, int64_t HW, int32_t P, int32_t G,
                        int32_t* counts, int32_t* invalid, void* stream);
 
+/* ---------------------------------------------------------------- label-free validation metrics (csrc/valmetrics.hip)
+ * Added without a new UPS_ABI_VERSION, as the ups_augment_* entries: no struct changed, and a binding that expects these symbols fails
+ * to load an older library by name.  The reference has no validation: the definitions here are the specification.
+ *
+ * ups_image_metrics: per-image error sums and SSIM sum of two image batches.
+ *   a, b   [N, H, W, ld] NHWC, each with its own dtype (UPS_F32 | UPS_BF16) and its own ld >= 3; channels 0..2 are R, G, B, the rest
+ *          is never read.  No alignment beyond the element's is assumed (ld = 3 fp32 rows are not 16-byte aligned).
+ *   weights  HOST array of the 11 normalised fp64 weights of the separable Gaussian window (sigma 1.5 in Wang et al. 2004; the
+ *          caller's numbers are used as they are, so a host restatement multiplies by the same values)
+ *   out    double [N, 3] = (sse, sae, ssim_sum) per image, written completely
+ *   scratch  ups_image_metrics_scratch_bytes(N, H, W) bytes, 8-byte aligned, caller-owned, overwritten
+ * All arithmetic is fp64 on the source values: x = clamp((v + 1) / 2, 0, 1); sse = sum (x - y)^2, sae = sum |x - y| over the 3 H W
+ * values; SSIM per channel over the VALID region (H - 10) x (W - 10), no padding: mu = sum w x, var_x = sum w x^2 - mu_x^2,
+ * cov = sum w x y - mu_x mu_y (no unbiased correction), C1 = 0.01^2, C2 = 0.03^2,
+ *   map = (2 mu_x mu_y + C1) (2 cov + C2) / ((mu_x^2 + mu_y^2 + C1) (var_x + var_y + C2)),   ssim_sum = sum of map over the valid
+ * pixels and the three channels.  No floating-point atomics: one partial per block in `scratch`, added in index order by a second
+ * launch -- two calls on the same inputs give the same bits.
+ * UPS_E_ARG, nothing launched: a NULL pointer, ld < 3, another dtype, N <= 0, H < 11 or W < 11, or 3 * N * tiles > 2^31 - 1 with
+ * tiles = ceil((H-10) / T) * ceil((W-10) / T), T = ups_image_metrics_tile() (then ups_image_metrics_scratch_bytes returns 0). */
+int32_t ups_image_metrics_tile(void);
+size_t ups_image_metrics_scratch_bytes(int32_t N, int32_t H, int32_t W);
+int ups_image_metrics(const void* a, int32_t dtype_a, int32_t lda, const void* b, int32_t dtype_b, int32_t ldb, int32_t N, int32_t H,
+                      int32_t W, const double* weights, double* out, void* scratch, void* stream);
+/* ups_part_usage: per-image part areas and mask sharpness.
+ *   soft   [N, HW, P] fp32  the soft-max of ups_part_softmax_fwd (out_parts_soft);   pred [N, HW] int64  its arg-max map
+ *   counts [N, P] int32, caller-zeroed or holding earlier launches' counts: += #{pixels k of image i : pred[i][k] == p}
+ *   invalid [1] int32: += number of pixels with pred outside [0, P); such a value is never used as an index
+ *   sharp  double [N, 2] = (sum_k max_p soft, sum_k -sum_p s ln s with 0 ln 0 = 0), fp64, natural log, written completely
+ *   scratch  ups_part_usage_scratch_bytes(N, HW) bytes, 8-byte aligned, caller-owned, overwritten
+ * Integer atomics for the counts; `sharp` by per-block partials added in index order (same bits on every call).  One block per
+ * chunk of ups_part_usage_chunk() pixels.  P > 32: UPS_E_UNSUPPORTED (the caller counts on the host).  UPS_E_ARG: a NULL pointer,
+ * N <= 0, P < 1, HW <= 0, HW > 2^31 - 1, 2 * N * chunks > 2^31 - 1. */
+int32_t ups_part_usage_chunk(void);
+size_t ups_part_usage_scratch_bytes(int32_t N, int64_t HW);
+int ups_part_usage(const float* soft, const int64_t* pred, int32_t N, int64_t HW, int32_t P, int32_t* counts, int32_t* invalid,
+                   double* sharp, void* scratch, void* stream);
+
 /* ---------------------------------------------------------------- mask priors (M:652-797), fused
  * One pass over l/m per view producing the partial sums, one fused backward producing dl.
  * See csrc/priors.hip for the slot layout of `sums`. */

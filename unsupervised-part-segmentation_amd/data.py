@@ -569,3 +569,67 @@ class ValidationSet(object):
         out = torch.empty((2, k, S, S, 3), dtype=torch.float32, device=device)
         L.call("ups_gather_views", L.ptr(u8), k, L.ptr(plan), k, S, L.ptr(out[0]), L.ptr(out[1]), None, L.stream())
         return out[0]
+
+
+def plan_validation_pairs(dataset, batch_size, max_images):
+    """The fixed (pose row, appearance row) plan of a validation csv: rows 0 .. n-1 with n = floor(min(len, max_images) / B) * B, each
+    with the partner ``plan_example`` draws for it on a fresh dataset (draw 0 of its per-index generator: it depends on the csv and
+    the dataset's seed alone).  -> int32 [n,2].  n < B is a ValueError: only whole chunks of batch_size pairs run."""
+    B = int(batch_size)
+    n = min(len(dataset), int(max_images)) // B * B
+    if n < B:
+        raise ValueError("validation pairs: {} row(s) (val_max_images {}) give no whole chunk of batch_size {}".format(
+            len(dataset), int(max_images), B))
+    pairs = np.empty((n, 2), dtype=np.int32)
+    for i in range(n):
+        pairs[i] = dataset.plan_example(i)[:2]
+    return pairs
+
+
+class ValidationPairs(object):
+    """``val_csv`` as (pose image, appearance image) pairs for the label-free metrics of `val_metrics` (Trainer.validate): the
+    sibling of ``ValidationSet`` that needs no label column.  Partners are drawn ONCE, here, by ``plan_validation_pairs`` with
+    ``data_seed = val_seed`` (default 1) and both flips off, so the plan is a function of the csv and ``val_seed``.  Every image a pair
+    names is decoded once into a uint8 store [m,S,S,3] (pinned when a device is there); ``pairs`` [n,2] int32 indexes that store.
+    ``chunk_views`` gives one chunk of batch_size pairs as float32 device views through ups_gather_views."""
+
+    def __init__(self, config, workers=8):
+        if not config.get("val_csv"):
+            raise ValueError("val_metrics: reconstruction / parts need `val_csv`")
+        self.batch_size = int(config["batch_size"])
+        ds = StochasticPairs(dict(config, data_csv=config["val_csv"], data_seed=int(config.get("val_seed", 1)),
+                                  data_flip_h=False, data_flip_v=False))
+        self.rows = plan_validation_pairs(ds, self.batch_size, config.get("val_max_images", 512))     # indices into the csv
+        used, inverse = np.unique(self.rows.reshape(-1), return_inverse=True)
+        self.pairs = inverse.reshape(-1, 2).astype(np.int32)                                         # indices into the store
+        S = int(ds.size)
+        store = np.empty((len(used), S, S, 3), dtype=np.uint8)
+        with cf.ThreadPoolExecutor(max_workers=max(1, min(int(workers), MAX_STORE_WORKERS))) as pool:
+            for k, img in enumerate(pool.map(ds.preprocess_u8, [ds.labels["file_path_"][int(r)] for r in used])):
+                store[k] = img
+        self.store = torch.from_numpy(store)
+        if torch.cuda.is_available():
+            self.store = self.store.pin_memory()
+        self._dev = None
+
+    def __len__(self):
+        return self.pairs.shape[0]
+
+    def chunks(self):
+        return len(self) // self.batch_size
+
+    def chunk_views(self, c, device):
+        """Chunk c (pairs [c B, (c + 1) B)) -> {"view0", "view1"} float32 [B,S,S,3] on `device`, current stream: the host path's
+        `u / 127.5 - 1` bit for bit (ups_gather_views, no flips).  The store and the plan are uploaded on first use and kept."""
+        from . import lib as L
+        device = torch.device(device)
+        if self._dev is None or self._dev[0] != device:
+            plan = np.zeros((len(self), 3), dtype=np.int32)
+            plan[:, :2] = self.pairs
+            self._dev = (device, self.store.to(device, non_blocking=True), torch.from_numpy(plan).to(device))
+        _, images, plan = self._dev
+        B, S = self.batch_size, images.shape[1]
+        out = torch.empty((2, B, S, S, 3), dtype=torch.float32, device=device)
+        L.call("ups_gather_views", L.ptr(images), images.shape[0], L.ptr(plan[c * B:(c + 1) * B]), B, S, L.ptr(out[0]), L.ptr(out[1]),
+               None, L.stream())
+        return {"view0": out[0], "view1": out[1]}

@@ -6,6 +6,10 @@ overlaps best (IoU over the whole evaluation set), the remapped prediction is sc
 number averages the labels except ``background`` (cub_semantic_ours.ipynb:615).  ``evaluate_parts`` is NumPy on the pixel maps;
 ``evaluate_from_counts`` computes the same dict from the per-image part x label histogram (``confusion_counts`` on the host,
 ups_part_confusion on the device through ``PartEvaluator``), which is all the protocol needs.
+
+Label-free metrics (`val_metrics` / `eval_metrics`: reconstruction, parts; no counterpart in the reference):
+``ReconstructionEvaluator`` / ``PartUsageEvaluator`` collect the per-image sums of ups_image_metrics / ups_part_usage on the device and
+``reconstruction_from_sums`` / ``usage_from_counts`` are the pure steps from those sums to the reported numbers.
 """
 import logging
 import os
@@ -262,6 +266,202 @@ class PartEvaluator(object):
         if self.n == 0:
             raise ValueError("PartEvaluator.result: no image was evaluated")
         return evaluate_from_counts(counts, background_label=self.background_label)
+
+
+# ------------------------------------------------------------------ label-free validation metrics (`val_metrics`, `eval_metrics`)
+def reconstruction_from_sums(rows, H, W):
+    """rows [n,3] = (sse, sae, ssim_sum) per image (ups_image_metrics) of H x W images -> {"mse", "l1", "psnr", "ssim"}: the means over
+    the images of mse_i = sse_i / (3 H W), l1_i = sae_i / (3 H W), psnr_i = 10 log10(1 / max(mse_i, 1e-10)) (images in [0, 1]: the
+    floor caps a perfect reconstruction at 100 dB) and ssim_i = ssim_sum_i / (3 (H - 10) (W - 10))."""
+    rows = np.asarray(rows, dtype=np.float64).reshape(-1, 3)
+    if rows.shape[0] == 0:
+        raise ValueError("reconstruction_from_sums: no image was evaluated")
+    if H < 11 or W < 11:
+        raise ValueError("reconstruction_from_sums: the 11 x 11 SSIM window needs H, W >= 11 (got {} x {})".format(H, W))
+    mse = rows[:, 0] / (3.0 * H * W)
+    l1 = rows[:, 1] / (3.0 * H * W)
+    psnr = 10.0 * np.log10(1.0 / np.maximum(mse, 1e-10))
+    ssim = rows[:, 2] / (3.0 * (H - 10) * (W - 10))
+    return {"mse": float(mse.mean()), "l1": float(l1.mean()), "psnr": float(psnr.mean()), "ssim": float(ssim.mean())}
+
+
+def usage_from_counts(counts, sharp, HW, min_area):
+    """counts [n,P] integers (pixels of image i whose arg-max part is p), sharp [n,2] = (sum of max_p soft, sum of the per-pixel
+    entropies) per image (ups_part_usage), HW pixels per image -> {"part_area": [P] with part_area[p] = sum_i counts[i,p] / (n HW),
+    "parts_active": #{p : part_area[p] >= min_area}, "confidence", "entropy": the per-pixel means over the set}."""
+    counts = np.asarray(counts).astype(np.int64)
+    sharp = np.asarray(sharp, dtype=np.float64).reshape(-1, 2)
+    n = counts.shape[0]
+    if n == 0 or sharp.shape[0] != n:
+        raise ValueError("usage_from_counts: counts [n >= 1,P] and sharp [n,2] expected (got {} and {})".format(counts.shape, sharp.shape))
+    px = np.int64(n) * np.int64(HW)
+    area = counts.sum(axis=0) / px
+    return {"part_area": [float(v) for v in area], "parts_active": int((area >= min_area).sum()),
+            "confidence": float(sharp[:, 0].sum() / px), "entropy": float(sharp[:, 1].sum() / px)}
+
+
+def part_usage_host(soft, pred, P):
+    """ups_part_usage in NumPy float64 (the host route for P > 32): (counts [N,P] int32, invalid, sharp [N,2])."""
+    soft = np.asarray(soft, dtype=np.float64)
+    N = soft.shape[0]
+    soft = soft.reshape(N, -1, P)
+    pred = np.asarray(pred).reshape(N, -1).astype(np.int64)
+    ok = (pred >= 0) & (pred < P)
+    counts = np.stack([np.bincount(pred[i][ok[i]], minlength=P) for i in range(N)]).astype(np.int32)
+    pos = soft > 0
+    ent = -(np.where(pos, soft, 0.0) * np.log(np.where(pos, soft, 1.0))).sum(axis=2)
+    sharp = np.stack([soft.max(axis=2).sum(axis=1), ent.sum(axis=1)], axis=1)
+    return counts, int(ok.size - ok.sum()), sharp
+
+
+class _RowBuffer(object):
+    """Per-image rows [n, width] in a device buffer that grows stream-ordered (as PartEvaluator's counts)."""
+
+    def __init__(self, device, width, dtype, zero):
+        self.device, self.width, self.dtype, self.zero = device, width, dtype, zero
+        self.n, self.buf = 0, self._new(64)
+
+    def _new(self, rows):
+        import torch
+        return (torch.zeros if self.zero else torch.empty)((rows, self.width), dtype=self.dtype, device=self.device)
+
+    def take(self, n):
+        """The next n rows (a view); the rows written so far are kept when the buffer has to grow."""
+        if self.n + n > self.buf.shape[0]:
+            grown = self._new(max(2 * self.buf.shape[0], self.n + n))
+            grown[:self.n] = self.buf[:self.n]
+            self.buf = grown
+        rows = self.buf[self.n:self.n + n]
+        self.n += n
+        return rows
+
+    def filled(self):
+        return self.buf[:self.n]
+
+
+class ReconstructionEvaluator(object):
+    """mse / l1 / psnr / ssim of generated images against their targets with the pixels left on the device: ``update`` runs
+    ups_image_metrics into a device buffer of (sse, sae, ssim_sum) rows, without synchronising with the host; ``result`` copies the
+    rows once and returns ``reconstruction_from_sums``."""
+
+    def __init__(self, device):
+        self.device = device
+        self.reset()
+
+    def reset(self):
+        import torch
+        self._rows, self.H, self.W = _RowBuffer(self.device, 3, torch.float64, False), None, None
+
+    @property
+    def n(self):
+        return self._rows.n
+
+    def update(self, generated, target, valid=None):
+        """generated, target [n,H,W,>=3] float32 / bfloat16 on the device, values in [-1, 1]; only the first `valid` images count."""
+        from . import ops
+        n = generated.shape[0] if valid is None else int(valid)
+        if n == 0:
+            return
+        H, W = int(generated.shape[1]), int(generated.shape[2])
+        if self.H is not None and (H, W) != (self.H, self.W):
+            raise ValueError("ReconstructionEvaluator.update: images of {} x {} after images of {} x {}".format(H, W, self.H, self.W))
+        self.H, self.W = H, W
+        ops.image_metrics(generated[:n], target[:n], out=self._rows.take(n))
+
+    def rows(self):
+        """[n,3] float64 NumPy: the one copy to the host."""
+        return self._rows.filled().cpu().numpy()
+
+    def result(self):
+        if self.n == 0:
+            raise ValueError("ReconstructionEvaluator.result: no image was evaluated")
+        return reconstruction_from_sums(self.rows(), self.H, self.W)
+
+
+class PartUsageEvaluator(object):
+    """Part areas, active parts, mask confidence and entropy with the pixels left on the device: ``update`` runs ups_part_usage into
+    device buffers that grow by one row per image; ``result`` makes one copy and returns ``usage_from_counts``.  n_parts above 32 (the
+    kernel's table) is computed by ``part_usage_host``, with one logged line."""
+
+    def __init__(self, device, n_parts, min_area=0.005):
+        self.device, self.P, self.min_area = device, int(n_parts), float(min_area)
+        if self.P < 1:
+            raise ValueError("PartUsageEvaluator: n_parts must be positive (got {})".format(self.P))
+        self.on_device = self.P <= 32
+        if not self.on_device:
+            LOG.info("PartUsageEvaluator: P = %d exceeds the device table (32): counting on the host", self.P)
+        self.reset()
+
+    def reset(self):
+        import torch
+        self.HW, self._host, self._host_invalid, self._n_host = None, [], 0, 0
+        self._counts = self._sharp = self._invalid = None
+        if self.on_device:
+            self._counts = _RowBuffer(self.device, self.P, torch.int32, True)
+            self._sharp = _RowBuffer(self.device, 2, torch.float64, False)
+            self._invalid = torch.zeros(1, dtype=torch.int32, device=self.device)
+
+    @property
+    def n(self):
+        return self._counts.n if self.on_device else self._n_host
+
+    def update(self, soft, pred, valid=None):
+        """soft [n,..,P] float32 (out_parts_soft), pred [n,..] int64 (out_parts_hard); only the first `valid` images count."""
+        from . import ops
+        n = pred.shape[0] if valid is None else int(valid)
+        if n == 0:
+            return
+        soft, pred = soft[:n], pred[:n]
+        if soft.shape[-1] != self.P or tuple(soft.shape[:-1]) != tuple(pred.shape):
+            raise ValueError("PartUsageEvaluator.update: soft {} and pred {} do not describe the same pixels of {} parts".format(
+                tuple(soft.shape), tuple(pred.shape), self.P))
+        HW = int(pred[0].numel())
+        if self.HW is not None and HW != self.HW:
+            raise ValueError("PartUsageEvaluator.update: maps of {} pixels after maps of {}".format(HW, self.HW))
+        self.HW = HW
+        if not self.on_device:
+            c, bad, s = part_usage_host(soft.cpu().numpy(), pred.cpu().numpy(), self.P)
+            self._host.append((c, s))
+            self._host_invalid += bad
+            self._n_host += n
+            return
+        ops.part_usage(soft, pred, counts=self._counts.take(n), invalid=self._invalid, sharp=self._sharp.take(n))
+
+    def sums(self):
+        """(counts [n,P] int32, sharp [n,2] float64, invalid) as NumPy: the one copy to the host (the integers ride in the float64
+        buffer: counts <= HW < 2^31 are exact there)."""
+        import torch
+        if not self.on_device:
+            if not self._host:
+                return np.zeros((0, self.P), np.int32), np.zeros((0, 2)), 0
+            return np.concatenate([c for c, _ in self._host]), np.concatenate([s for _, s in self._host]), self._host_invalid
+        n = self.n
+        both = torch.cat([self._sharp.filled().reshape(-1), self._counts.filled().reshape(-1).double(), self._invalid.double()]).cpu().numpy()
+        return both[2 * n:-1].astype(np.int32).reshape(n, self.P), both[:2 * n].reshape(n, 2), int(both[-1])
+
+    def result(self):
+        from .lib import UpsError
+        counts, sharp, invalid = self.sums()
+        if invalid != 0:
+            raise UpsError("PartUsageEvaluator: {} pixel(s) with a part id outside [0, {}) were not counted".format(invalid, self.P))
+        if self.n == 0:
+            raise ValueError("PartUsageEvaluator.result: no image was evaluated")
+        return usage_from_counts(counts, sharp, self.HW, self.min_area)
+
+
+def validation_logs(rec=None, usage=None, rec_loss=None):
+    """The `val/` keys of the label-free metrics: rec = ``reconstruction_from_sums`` (val/mse, val/l1, val/psnr, val/ssim), rec_loss the
+    perceptual reconstruction term (val/rec), usage = ``usage_from_counts`` (val/part_area_<p>, val/parts_active, val/confidence,
+    val/entropy).  All of them sort before val/steps_done."""
+    logs = {}
+    if rec is not None:
+        logs.update({"val/" + k: rec[k] for k in ("mse", "l1", "psnr", "ssim")})
+    if rec_loss is not None:
+        logs["val/rec"] = rec_loss
+    if usage is not None:
+        logs.update({"val/part_area_{}".format(p): v for p, v in enumerate(usage["part_area"])})
+        logs.update({"val/parts_active": usage["parts_active"], "val/confidence": usage["confidence"], "val/entropy": usage["entropy"]})
+    return logs
 
 
 def write_eval_tables(res, root, global_step, part_names=None, background_label=0):

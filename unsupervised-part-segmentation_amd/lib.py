@@ -155,6 +155,12 @@ _SIGS = {
     "ups_augment_views": ([_P, _L, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P, _I, _P], C.c_int),
     "ups_augment_field": ([_P, _P, _I, _I, _P, _P, _P], C.c_int),
     "ups_part_confusion": ([_P, _P, _P, _I, _L, _I, _I, _P, _P, _P], C.c_int),
+    "ups_image_metrics_tile": ([], _I),
+    "ups_image_metrics_scratch_bytes": ([_I, _I, _I], _Z),
+    "ups_image_metrics": ([_P, _I, _I, _P, _I, _I, _I, _I, _I, C.POINTER(C.c_double), _P, _P, _P], C.c_int),
+    "ups_part_usage_chunk": ([], _I),
+    "ups_part_usage_scratch_bytes": ([_I, _L], _Z),
+    "ups_part_usage": ([_P, _P, _I, _L, _I, _P, _P, _P, _P, _P], C.c_int),
     "ups_prior_sums_floats": ([_I, _I], _Z),
     "ups_prior_fwd": ([C.POINTER(PriorDesc), _P], C.c_int),
     "ups_prior_bwd": ([C.POINTER(PriorDesc), _P], C.c_int),

@@ -71,7 +71,7 @@ class TrainModel(object):
         self.df = N.is_48c(config)          # DeepFashion SB_model48c variant (two inputs, no rectangles, extra decoders)
         self.nets = N.Nets(config, self.device, seed if seed is not None else config.get("seed", 0))
         self.bank = self.nets.bank
-        self._last, self._tps = {}, {}
+        self._last, self._tps, self.generated_act = {}, {}, None
 
     # model.py:260-263
     @property
@@ -147,6 +147,7 @@ class TrainModel(object):
         feat = yp.float().view(P, B, A).permute(1, 0, 2).contiguous()
         inj = ops.UnpoolFn.apply(hard[:B].contiguous(), feat, self.act_dtype)
         gen = self.nets.dd(Act(inj, B, S, S, A + P)).t
+        self.generated_act = gen         # the decoder's own tensor [B,S,S,8] (activation layout): what Trainer.validate hands the trunk
         self._last = {"generated": gen[..., :3].float(), "m0_sample": m[:B], "out_parts_hard": amax,
                       "out_parts_soft": soft, "view0_mask00_rgb": mask2rgb(m[:B])}
         return self._last
@@ -362,6 +363,25 @@ def gram_weight_of(config, logger=None):
     return v if v > 0 else 0.0
 
 
+VAL_METRICS = ("iou", "reconstruction", "parts")
+
+
+def validation_metrics(config, key="val_metrics", default=("iou",)):
+    """The metric names of `val_metrics` (default ["iou"]: the part IoU alone, which needs label images) or of the runner's
+    `eval_metrics` (default none); ValueError on an unknown name, and on an empty `val_metrics`."""
+    v = config.get(key)
+    if v is None:
+        return list(default)
+    if isinstance(v, str) or not isinstance(v, (list, tuple)):
+        raise ValueError("{}: a list drawn from {} is expected (got {!r})".format(key, " | ".join(VAL_METRICS), v))
+    unknown = [m for m in v if m not in VAL_METRICS]
+    if unknown:
+        raise ValueError("{}: unknown metric(s) {} ({})".format(key, unknown, " | ".join(VAL_METRICS)))
+    if not v and key == "val_metrics":
+        raise ValueError("val_metrics is empty: with val_freq set, list at least one of {}".format(" | ".join(VAL_METRICS)))
+    return [m for m in VAL_METRICS if m in v]
+
+
 def check_validation_config(config):
     """The refusals of `val_freq` (ValueError with the reason), decided from the config alone, before anything touches the device."""
     if not int(config.get("val_freq", 0) or 0):
@@ -372,8 +392,14 @@ def check_validation_config(config):
     if bool(config.get("hip_graph", SW.flag("UPS_GRAPH"))):
         raise ValueError("val_freq cannot be combined with hip_graph: True: eager launches between replays of the captured "
                          "step have not been shown safe")
-    if not config.get("val_csv") or not config.get("data_gt_segmentation_column"):
+    metrics = validation_metrics(config)
+    if "iou" in metrics and (not config.get("val_csv") or not config.get("data_gt_segmentation_column")):
         raise ValueError("val_freq needs `val_csv` and `data_gt_segmentation_column` (the csv column with the label images)")
+    if not config.get("val_csv"):
+        raise ValueError("val_freq needs `val_csv`")
+    if "reconstruction" in metrics and int(config.get("spatial_size", 256)) < 11:
+        raise ValueError("val_metrics: reconstruction needs spatial_size >= 11, the 11 x 11 SSIM window (got {})".format(
+            config.get("spatial_size")))
 
 
 class Trainer(object):
@@ -462,7 +488,8 @@ class Trainer(object):
         # `log_images` (default off): the reference's img_ops (model.py:968-1053) as uint8 canvases on the steps that log scalars
         self.log_images = bool(config.get("log_images", False))
         self._want_images = False       # set for the duration of a train_step(..., images=True)
-        # `val_freq: K` with `val_csv`: the part IoU of a validation csv after every K-th step (``validate``)
+        # `val_freq: K` with `val_csv`: the metrics of `val_metrics` (default: the part IoU) on a validation csv after every K-th step
+        # (``validate``)
         self.val_freq = int(config.get("val_freq", 0) or 0)
         self._val, self._val_logs = None, OrderedDict()
         if self.val_freq > 0:
@@ -1527,43 +1554,103 @@ class Trainer(object):
         out = OrderedDict()
         for k, v in self.log_ops.items():
             out[k] = float(v) if torch.is_tensor(v) else float(v)
-        out.update(self._val_logs)      # val/overall, val/iou_<label> of the most recent validation (`val_freq`)
+        out.update(self._val_logs)      # the val/ keys of the most recent validation (`val_freq`)
         return out
 
     # ------------------------------------------------------------------ periodic validation (`val_freq`, `val_csv`)
     def _init_validation(self):
-        """On rank 0, the validation set: decoded once, kept as pinned uint8 (the refusals were checked when __init__ began)."""
+        """On rank 0, the validation set(s) and evaluators of `val_metrics`: decoded once, kept as pinned uint8 (the refusals were checked
+        when __init__ began)."""
         cfg = self.config
         check_validation_config(cfg)
         if self.rank != 0:              # rank 0 validates; the others meet it at the next step's first collective
             return
         from . import data as _data
         from . import evalutil
-        vs = _data.ValidationSet(cfg)
-        ev = evalutil.PartEvaluator(self.model, int(cfg.get("eval_n_labels", 32)), lut=cfg.get("eval_label_lut"))
-        self._val = {"set": vs, "evaluator": ev}
+        metrics = validation_metrics(cfg)
+        self._val = {"metrics": metrics}
+        if "iou" in metrics:
+            vs = _data.ValidationSet(cfg)
+            ev = evalutil.PartEvaluator(self.model, int(cfg.get("eval_n_labels", 32)), lut=cfg.get("eval_label_lut"))
+            self._val.update({"set": vs, "evaluator": ev})
+        if "reconstruction" in metrics or "parts" in metrics:       # the label-free metrics: one forward per chunk of B pairs
+            self._val["pairs"] = _data.ValidationPairs(cfg)
+            if "reconstruction" in metrics:
+                self._val["rec"] = evalutil.ReconstructionEvaluator(self.device)
+            if "parts" in metrics:
+                self._val["usage"] = evalutil.PartUsageEvaluator(self.device, self.model.n_parts,
+                                                                 float(cfg.get("val_min_part_area", 0.005)))
 
     @torch.no_grad()
     def validate(self):
-        """Part IoU (evalutil.PartEvaluator: ``model.segment`` + ups_part_confusion) of the validation set under the CURRENT
-        weights -> {"val/overall", "val/iou_<label>", "val/steps_done"}, also kept for ``fetch_logs``.  Runs on the main stream
+        """The metrics of `val_metrics` on the validation set under the CURRENT weights -> {"val/...", "val/steps_done"}, also kept for
+        ``fetch_logs``.  iou (the default): part IoU (evalutil.PartEvaluator: ``model.segment`` + ups_part_confusion) -> "val/overall",
+        "val/iou_<label>"; reconstruction / parts: ``_validate_pairs``, which needs no label images.  Runs on the main stream
         between two steps, draws nothing from the trainer's generators and touches neither optimizer nor Lagrangian / EMA state: the training
-        trajectory is the same with and without it.  One host synchronisation (the copy of the counts)."""
+        trajectory is the same with and without it.  One host synchronisation per evaluator (the copy of its counts or sums)."""
         if self._val is None:
             return OrderedDict()
-        vs, ev = self._val["set"], self._val["evaluator"]
-        ev.reset()
-        chunk = 2 * int(self.config["batch_size"])
-        for c0 in range(0, len(vs), chunk):
-            c1 = min(len(vs), c0 + chunk)
-            ev.update(vs.float_views(c0, c1, self.device), vs.labels[c0:c1])
-        res = ev.result()
-        logs = OrderedDict([("val/overall", res["overall"])])
-        for g in sorted(res["iou"]):
-            logs["val/iou_{}".format(g)] = res["iou"][g]
+        logs = OrderedDict()
+        if "evaluator" in self._val:
+            vs, ev = self._val["set"], self._val["evaluator"]
+            ev.reset()
+            chunk = 2 * int(self.config["batch_size"])
+            for c0 in range(0, len(vs), chunk):
+                c1 = min(len(vs), c0 + chunk)
+                ev.update(vs.float_views(c0, c1, self.device), vs.labels[c0:c1])
+            res = ev.result()
+            logs["val/overall"] = res["overall"]
+            for g in sorted(res["iou"]):
+                logs["val/iou_{}".format(g)] = res["iou"][g]
+        if "pairs" in self._val:
+            logs.update(self._validate_pairs())
         logs["val/steps_done"] = self.global_step       # which weights the numbers belong to: they stay in fetch_logs until the next report
         self._val_logs = logs
         return logs
+
+    def _validation_perceptual(self):
+        """What ``_perceptual_view`` needs of a step's context, fixed for validation: the 224 x 224 window of `resize256_crop224` has its
+        corner at (16, 16), the centre, instead of a draw from the trainer's generator."""
+        c = _Step()
+        c.pmode = self.perceptual_input
+        if c.pmode not in PERCEPTUAL_INPUTS:
+            raise NotImplementedError("perceptual_input: {} ({})".format(c.pmode, " | ".join(PERCEPTUAL_INPUTS)))
+        S = int(self.config["spatial_size"])
+        if c.pmode != "native" and S not in (128, 256):
+            raise NotImplementedError("perceptual_input: {} is restated for 128x128 and 256x256 inputs only (got {})".format(c.pmode, S))
+        c.resize2x = c.pmode != "native" and S == 128
+        c.crop_yx = None
+        if c.pmode == "resize256_crop224":
+            c.crop_yx = torch.tensor([16, 16], dtype=torch.int32, device=self.device)
+        return c
+
+    def _validate_pairs(self):
+        """The label-free metrics of `val_metrics` over the pair set: ONE ``model.forward(chunk, noise=None)`` per chunk of batch_size
+        pairs feeds both evaluators.  reconstruction: `generated` against view0 -> val/mse, val/l1, val/psnr, val/ssim
+        (ups_image_metrics) and val/rec, the step's own reconstruction term (``_perceptual_view`` + ``vgg.loss`` with `gram_weight`) on
+        those tensors, averaged over the chunks.  parts: out_parts_soft / out_parts_hard -> val/part_area_<p>, val/parts_active,
+        val/confidence, val/entropy (ups_part_usage).  One copy to the host per evaluator, and one for val/rec."""
+        from . import evalutil
+        val, model = self._val, self.model
+        pairs, rec, usage = val["pairs"], val.get("rec"), val.get("usage")
+        for ev in (rec, usage):
+            if ev is not None:
+                ev.reset()
+        pc = self._validation_perceptual() if rec is not None else None
+        rec_terms = []
+        for ci in range(pairs.chunks()):
+            chunk = pairs.chunk_views(ci, self.device)
+            out = model.forward(chunk, noise=None)
+            if rec is not None:
+                gen = model.generated_act
+                rec.update(gen, chunk["view0"])
+                tgt = chunk["view0"] if pc.pmode == "native" else self._perceptual_view(pc, model.to_act(chunk["view0"]))
+                rec_terms.append(self.vgg.loss(tgt.contiguous(), self._perceptual_view(pc, gen), model.act_dtype,
+                                               gram_weight=self.gram_weight).detach().double().reshape(1))
+            if usage is not None:
+                usage.update(out["out_parts_soft"], out["out_parts_hard"])
+        rec_loss = float(torch.cat(rec_terms).mean()) if rec_terms else None
+        return evalutil.validation_logs(rec.result() if rec is not None else None, usage.result() if usage is not None else None, rec_loss)
 
     def iterate(self, batch_iterator, num_steps=None, log_fn=print):
         """edflow's session loop with its hooks.  LoggingHook cadence as cub/train/log.txt:221-860 shows it (an IntervalHook whose

@@ -1820,6 +1820,85 @@ def part_confusion(pred, gt_u8, P, G, lut=None, counts=None, invalid=None):
     return counts
 
 
+# --------------------------------------------------------------------------- label-free validation metrics (csrc/valmetrics.hip)
+IMAGE_METRICS_TILE = 32         # valid pixels per tile edge of ups_image_metrics (checked against the library on first use)
+PART_USAGE_CHUNK = 1024         # pixels per block of ups_part_usage
+SSIM_WINDOW, SSIM_SIGMA = 11, 1.5
+_GEOMETRY_CHECKED = []
+
+
+def ssim_weights():
+    """The 11 normalised float64 weights of the separable SSIM window (Gaussian, sigma 1.5: Wang et al. 2004), as a NumPy array: the
+    numbers both the kernel (a host argument) and the host restatement multiply by."""
+    import numpy as np
+    k = np.arange(SSIM_WINDOW, dtype=np.float64) - SSIM_WINDOW // 2
+    w = np.exp(-(k * k) / (2.0 * SSIM_SIGMA * SSIM_SIGMA))
+    return w / w.sum()
+
+
+def _metrics_geometry():
+    if not _GEOMETRY_CHECKED:
+        lib = L.load()
+        got = (lib.ups_image_metrics_tile(), lib.ups_part_usage_chunk())
+        if got != (IMAGE_METRICS_TILE, PART_USAGE_CHUNK):
+            raise L.UpsError("the library's metric tile / chunk {} differ from ops.IMAGE_METRICS_TILE / PART_USAGE_CHUNK {}: rebuild"
+                             .format(got, (IMAGE_METRICS_TILE, PART_USAGE_CHUNK)))
+        _GEOMETRY_CHECKED.append(True)
+
+
+def image_metrics(a, b, out=None):
+    """out[i] = (sse, sae, ssim_sum) of images a[i], b[i] (ups_image_metrics; the sums evalutil.reconstruction_from_sums takes).
+    a, b [N,H,W,>=3] float32 or bfloat16 NHWC, each with its own dtype and channel count (channels 0..2 are read), values in [-1, 1]
+    (mapped to [0, 1] and clamped); H, W >= 11.  out [N,3] float64 (default: new; a row-offset view of a larger buffer is fine), written
+    completely.  Asynchronous on the current stream; the scratch is a fresh allocation per call (the caching allocator orders its reuse
+    on that stream).  Returns out."""
+    _metrics_geometry()
+    if (a.dim() != 4 or b.dim() != 4 or tuple(a.shape[:3]) != tuple(b.shape[:3]) or a.shape[0] == 0 or a.shape[3] < 3 or b.shape[3] < 3
+            or a.dtype not in _IMG_DTYPES or b.dtype not in _IMG_DTYPES):
+        raise L.UpsError("image_metrics: a, b [N >= 1,H,W,>=3] float32 / bfloat16 of one [N,H,W] (got {} {}, {} {})".format(
+            tuple(a.shape), a.dtype, tuple(b.shape), b.dtype))
+    N, H, W = a.shape[:3]
+    if out is None:
+        out = torch.empty((N, 3), dtype=torch.float64, device=a.device)
+    if out.dtype != torch.float64 or tuple(out.shape) != (N, 3):
+        raise L.UpsError("image_metrics: out [{},3] float64 expected (got {} {})".format(N, tuple(out.shape), out.dtype))
+    a, b = a.contiguous(), b.contiguous()
+    nbytes = L.load().ups_image_metrics_scratch_bytes(N, H, W)
+    scratch = torch.empty(max(1, nbytes // 8), dtype=torch.float64, device=a.device)
+    w = ssim_weights()
+    L.call("ups_image_metrics", L.ptr(a), L.dt(a), a.shape[3], L.ptr(b), L.dt(b), b.shape[3], N, H, W,
+           w.ctypes.data_as(C.POINTER(C.c_double)), L.ptr(out), L.ptr(scratch), L.stream())
+    return out
+
+
+def part_usage(soft, pred, counts=None, invalid=None, sharp=None):
+    """counts[i,p] += #{pixels of image i with pred == p}; sharp[i] = (sum of max_p soft, sum of -sum_p s ln s) over image i's pixels
+    (ups_part_usage; the statistics evalutil.usage_from_counts takes).  soft [N,..,P] float32 (out_parts_soft), pred [N,..] int64
+    (out_parts_hard) over the same pixels, P <= 32 (more: L.UpsError from the C entry -- evalutil.PartUsageEvaluator counts on the host
+    then).  counts [N,P] int32 (default: new zeros; given: added to), invalid [1] int32 (+= pixels with pred outside [0,P), counted
+    nowhere else), sharp [N,2] float64 (written).  Asynchronous on the current stream.  Returns (counts, invalid, sharp)."""
+    _metrics_geometry()
+    N, P = pred.shape[0], soft.shape[-1]
+    if (soft.dtype != torch.float32 or pred.dtype != torch.int64 or N == 0 or tuple(soft.shape[:-1]) != tuple(pred.shape)):
+        raise L.UpsError("part_usage: soft [N >= 1,..,P] float32 and pred [N,..] int64 over the same pixels (got {} {}, {} {})".format(
+            tuple(soft.shape), soft.dtype, tuple(pred.shape), pred.dtype))
+    if counts is None:
+        counts = torch.zeros((N, P), dtype=torch.int32, device=pred.device)
+    if invalid is None:
+        invalid = torch.zeros(1, dtype=torch.int32, device=pred.device)
+    if sharp is None:
+        sharp = torch.empty((N, 2), dtype=torch.float64, device=pred.device)
+    if (counts.dtype != torch.int32 or tuple(counts.shape) != (N, P) or invalid.dtype != torch.int32 or invalid.numel() != 1
+            or sharp.dtype != torch.float64 or tuple(sharp.shape) != (N, 2)):
+        raise L.UpsError("part_usage: counts [{0},{1}] int32, invalid [1] int32 and sharp [{0},2] float64 expected".format(N, P))
+    soft, pred = soft.contiguous(), pred.contiguous()
+    HW = pred.numel() // N
+    nbytes = L.load().ups_part_usage_scratch_bytes(N, HW)
+    scratch = torch.empty(max(1, nbytes // 8), dtype=torch.float64, device=pred.device)
+    L.call("ups_part_usage", L.ptr(soft), L.ptr(pred), N, HW, P, L.ptr(counts), L.ptr(invalid), L.ptr(sharp), L.ptr(scratch), L.stream())
+    return counts, invalid, sharp
+
+
 # --------------------------------------------------------------------------- training image logs (csrc/canvas.hip): uint8 canvases
 def canvas_grid(n, cols=None):
     """(rows, cols) of tf_batch_to_canvas for n tiles (re-derived, UNVERIFIED): cols=None -> the square grid of side ceil(sqrt(n)),

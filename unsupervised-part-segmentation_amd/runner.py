@@ -163,7 +163,9 @@ def evaluate(args):
     """``edflow -e eval.yaml -c ckpt`` (cub/code/eval/eval_iclr_01/infer.py:216-224, eval_01.py:152-190): the test-mode graph
     (no sampling noise) is run over the dataset, ``model.outputs[k]`` for k in ``fetch_output_keys`` is collected and
     ``{"inputs", "outputs"}`` is pickled to <root>/eval/<global_step>/model_outputs.p; with ground-truth label maps in the
-    batches (key ``gt_segmentation``) the part-IoU protocol of eval_01.py:229-383 is reported too (evalutil.py)."""
+    batches (key ``gt_segmentation``) the part-IoU protocol of eval_01.py:229-383 is reported too (evalutil.py).
+    ``eval_metrics: [reconstruction, parts]`` (default none) also writes metrics.yml: the label-free metrics of the trainer's
+    `val_metrics` (evalutil.ReconstructionEvaluator / PartUsageEvaluator) from the same forward passes, without the perceptual term."""
     import pickle
     import numpy as np
     from . import evalutil
@@ -189,6 +191,8 @@ def evaluate(args):
     it = Iterator(cfg, root, model)
     it.initialize(args.checkpoint)
     if cfg.get("eval_on_device", False):
+        if cfg.get("eval_metrics"):
+            raise ValueError("eval_metrics needs the host route of -e (its forward passes): it cannot be combined with eval_on_device")
         res = evaluate_on_device(model, batches_it, cfg, args.eval_batches)
         odir = os.path.join(root, "eval", str(it.global_step))
         os.makedirs(odir, exist_ok=True)
@@ -197,11 +201,25 @@ def evaluate(args):
         return res
     keys = cfg.get("fetch_output_keys", ["out_parts_hard", "out_parts_soft", "generated", "m0_sample"])
     outs, ins, gts = {k: [] for k in keys}, {"view0": [], "view1": []}, []
+    # `eval_metrics: [reconstruction, parts]` (default none): the label-free metrics of `val_metrics` from the same forward passes
+    from .model import validation_metrics
+    metrics = validation_metrics(cfg, "eval_metrics", ())
+    if "iou" in metrics:
+        raise ValueError("eval_metrics: the part IoU is what -e writes whenever the batches carry label maps; list reconstruction | parts")
+    if "reconstruction" in metrics and int(cfg["spatial_size"]) < 11:
+        raise ValueError("eval_metrics: reconstruction needs spatial_size >= 11, the 11 x 11 SSIM window")
+    rec_ev = evalutil.ReconstructionEvaluator(model.device) if "reconstruction" in metrics else None
+    use_ev = (evalutil.PartUsageEvaluator(model.device, model.n_parts, float(cfg.get("val_min_part_area", 0.005)))
+              if "parts" in metrics else None)
     for bi, batch in enumerate(batches_it):
         if args.eval_batches is not None and bi >= args.eval_batches:
             break
         valid = batch.pop("valid", None)           # ragged last batch: padded to the static batch size, only `valid` rows count
         o = model.forward(batch)
+        if rec_ev is not None:
+            rec_ev.update(model.generated_act, torch.as_tensor(batch["view0"]).to(model.device, torch.float32), valid=valid)
+        if use_ev is not None:
+            use_ev.update(o["out_parts_soft"], o["out_parts_hard"], valid=valid)
         for k in keys:
             outs[k].append((o[k].detach().float().cpu().numpy() if o[k].dtype.is_floating_point else o[k].cpu().numpy())[:valid])
         for k in ins:
@@ -213,6 +231,10 @@ def evaluate(args):
     os.makedirs(odir, exist_ok=True)
     with open(os.path.join(odir, "model_outputs.p"), "wb") as f:
         pickle.dump(data, f)
+    if metrics:
+        vals = evalutil.validation_logs(rec_ev.result() if rec_ev is not None else None, use_ev.result() if use_ev is not None else None)
+        with open(os.path.join(odir, "metrics.yml"), "w") as f:       # the `val/` names of Trainer.validate without the prefix
+            yaml.safe_dump({k[len("val/"):]: (int(v) if isinstance(v, int) else float(v)) for k, v in vals.items()}, f)
     if gts:
         gt = np.concatenate(gts)
         if cfg.get("eval_label_lut"):       # (the same table the device route hands to the kernel)
