@@ -9,6 +9,10 @@ sum of |products| of a case, in units of the smallest LSB among them, must stay 
 Leaky ReLU runs at slope 0.25 here (`ops.ConvLayer(..., slope=0.25)`): act(x), act'(x) and the inverted residual r / slope are
 then exact; the shipped 0.2 is not dyadic.  CoordConv cases use square maps of 9 / 17 / 33 / 65 pixels: the coordinates
 i / (H - 1) * 2 - 1 are dyadic only when H - 1 is a power of two.
+
+The fp8 paths have a lattice of their own at the end of this file (FP8_CASES): integers in [-7, 7] with a 7 wherever a scale is
+derived from a maximum, so that every per-row weight scale and every delayed tensor scale is a power of two and every quantisation
+lossless; `fp8_headroom` is the same condition stated in the quantised domain.
 """
 import zlib
 
@@ -132,10 +136,10 @@ def rounded(t, dtype):
 
 # ---------------------------------------------------------------------------------------------------------------------------------
 # headroom
-def lsb(t):
-    """The largest power of two <= 1 that divides every entry of t."""
+def lsb(t, hi=0):
+    """The largest power of two <= 2**hi that divides every entry of t."""
     t = t.detach().double()
-    for e in range(0, 20):
+    for e in range(-hi, 20):
         s = t * (2.0 ** e)
         if torch.equal(s, s.round()):
             return 2.0 ** -e
@@ -427,7 +431,7 @@ def first_diff(a, b, axes=None):
     """None when the two tensors hold the same bits, else a message: the number of differing elements, the first differing index
     decoded (for a 4-d tensor: image, y, x, channel) and the two values there."""
     assert a.shape == b.shape and a.dtype == b.dtype, (a.shape, b.shape, a.dtype, b.dtype)
-    iv = {2: torch.int16, 4: torch.int32, 8: torch.int64}[a.element_size()]
+    iv = {1: torch.int8, 2: torch.int16, 4: torch.int32, 8: torch.int64}[a.element_size()]
     ne = a.contiguous().view(iv) != b.contiguous().view(iv)
     if not bool(ne.any()):
         return None
@@ -436,3 +440,269 @@ def first_diff(a, b, axes=None):
     where = ", ".join("{}={}".format(k, v) for k, v in zip(names, idx)) if names else str(idx)
     return "{} of {} elements differ; first at ({}): got {!r} want {!r}".format(
         int(ne.sum()), ne.numel(), where, float(a[idx]), float(b[idx]))
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# the fp8 lattice: data on which every scale the fp8 kernels derive is a power of two and every quantisation is lossless
+#
+# weight_prep_f8_kernel scales a row by 448 / m (m = the row's |max|) and dequantises by m / 448: with m = 7 these are 64 and 2**-6.
+# The delayed scales are fmax * MARGIN / amax (MARGIN = 0.5; fmax = 448 for e4m3, 57344 for e5m2): with amax = 7 they are 32 and
+# 4096.  Integers in [-7, 7] times 64 and leaky_relu(., 0.25) of them times 32 are e4m3 values, integers in [-7, 7] times 4096
+# are e5m2 values.  So the accumulator sees integer multiples of one LSB, the dequantisation factors are exact, and the fp8
+# kernels must give the bits of the plain integer convolution.
+F8_AMP = 7
+E4M3_MAX, E5M2_MAX, F8_MARGIN = 448.0, 57344.0, 0.5
+F8_SW = E4M3_MAX / F8_AMP                       # 64: per-row weight scale
+F8_SA = E4M3_MAX * F8_MARGIN / F8_AMP           # 32: delayed scale of an activation tensor
+F8_SG = E5M2_MAX * F8_MARGIN / F8_AMP           # 4096: delayed scale of a gradient tensor
+E4M3, E5M2 = torch.float8_e4m3fn, torch.float8_e5m2
+
+
+def f8_weights(g, k, cin, cout, density=1.0):
+    """Integers in [-7, 7] [k, k, cin, cout]; every output-channel column over (taps, cin) and every input-channel row over
+    (taps, cout) holds a +-7: the forward copy is scaled per column, the transposed copy of the input gradient per row."""
+    V = ints(g, (k, k, cin, cout), F8_AMP, density)
+    co, ci = torch.arange(cout), torch.arange(cin)
+    t = co % (k * k)
+    V[t // k, t % k, (3 * co + 1) % cin, co] = F8_AMP * (1.0 - 2.0 * (co % 2)).double()
+    t = ci % (k * k)
+    V[t // k, t % k, ci, (5 * ci + 3) % cout] = F8_AMP * (1.0 - 2.0 * (ci // 2 % 2)).double()
+    assert bool((V.abs().amax(dim=(0, 1, 2)) == F8_AMP).all()) and bool((V.abs().amax(dim=(0, 1, 3)) == F8_AMP).all())
+    return V
+
+
+def f8_activations(g, shape, density=1.0):
+    """Integers in [-7, 7] with a +7 (the recorded maximum is of act(x): behind a leaky ReLU a -7 counts 1.75) and a -7."""
+    x = ints(g, shape, F8_AMP, density)
+    x.view(-1)[0], x.view(-1)[-1] = F8_AMP, -F8_AMP
+    return x
+
+
+def f8_out_grads(g, shape, density=1.0):
+    """Integers in [-7, 7] with both signs of 7."""
+    return f8_activations(g, shape, density)
+
+
+def is_pow2(t):
+    """Every entry of a float32 tensor is a power of two (mantissa bits zero, finite, positive)."""
+    t = t.float().contiguous().view(-1)
+    bits = t.view(torch.int32)
+    return bool(((bits & 0x007fffff) == 0).all() and (t > 0).all() and torch.isfinite(t).all())
+
+
+def f8_quantise(t, scale, dtype):
+    """(t * scale) as the fp8 type (saturating RNE, as v_cvt_pk_{fp8,bf8}_f32) and whether the round trip is lossless."""
+    fmax = E4M3_MAX if dtype == E4M3 else E5M2_MAX
+    s = t.double() * scale
+    q = s.clamp(-fmax, fmax).float().to(dtype)
+    return q, torch.equal(q.double(), s)
+
+
+class Fp8Case(object):
+    """One fp8 launch family member.  route: "convert" (the kernel quantises its 16-bit operand), "copy" (a pre-quantised
+    copy is handed in: the grid-size gates of launch_t choose the instance) or "wgrad".  dirs: which launches the case drives.
+    emit: which launches also write an fp8 copy of their output (the output's maximum is then arranged to be 7 * 2**k)."""
+    k, stride, in_post, out_act = 3, 1, False, False
+
+    def __init__(self, name, route, n, h, w, cin, cout, dirs=("fwd", "dgrad"), coords=False, act=None, res_self=False, emit=(),
+                 f16=False, xdens=1.0, wdens=1.0, gdens=1.0, splitk=None, instance=""):
+        self.name, self.route, self.n, self.h, self.w, self.cin, self.cout = name, route, n, h, w, cin, cout
+        self.dirs, self.coords, self.act, self.res_self, self.emit, self.f16 = dirs, coords, act, res_self, emit, f16
+        self.xdens, self.wdens, self.gdens, self.splitk, self.instance = xdens, wdens, gdens, splitk, instance
+        assert not res_self or cin == cout
+
+    def __repr__(self):
+        return self.name
+
+
+FP8_CASES = [
+    # ---- in-kernel conversion (Fp8State(True, copy_only=False)): launch_bn<T, BN, 1, TS, 1 / 2>
+    Fp8Case("f8_cvt_ragged_hw", "convert", 2, 16, 32, 64, 192, act=LR, emit=("fwd", "dgrad"),
+            instance="fwd e4m3 <128,1> with a ragged second N-tile (192 = 128 + 64), h != w; dgrad e5m2 <64,1>, three chunks"),
+    Fp8Case("f8_cvt_chunks4", "convert", 2, 16, 16, 256, 64, emit=("fwd", "dgrad"),
+            instance="fwd e4m3 <64,1>, four channel chunks; dgrad e5m2 <128,1>, two N-tiles"),
+    Fp8Case("f8_cvt_res_lrelu", "convert", 2, 32, 16, 128, 128, act=LR, res_self=True, emit=("fwd", "dgrad"),
+            instance="fwd e4m3 <128,1>, leaky ReLU on load + residual; dgrad e5m2 <128,1> with act' and the residual gradient"),
+    Fp8Case("f8_cvt_coords", "convert", 3, 16, 16, 64, 64, coords=True, act=LR, emit=("fwd", "dgrad"),
+            instance="fwd e4m3 <64,1> with the CoordConv table (zero coordinate rows); dgrad e5m2 <64,1> (forward ci_log = 64)"),
+    # ---- pre-quantised input, K = 32 MFMA, one block per CU (small grids)
+    Fp8Case("f8_copy_occ1_64to128", "copy", 2, 32, 32, 64, 128, act=LR, emit=("fwd", "dgrad"),
+            instance="fwd <128,1,PRE> e4m3; dgrad <64,1,PRE> e5m2 (8 tiles: below every 512-block gate)"),
+    Fp8Case("f8_copy_occ1_128to64", "copy", 2, 32, 32, 128, 64, act=LR, emit=("fwd", "dgrad"),
+            instance="fwd <64,1,PRE> e4m3 (ci % 128 == 0 but a small grid: K = 32); dgrad <128,1,PRE> e5m2"),
+    # ---- pre-quantised input, K = 32 MFMA, two blocks per CU (>= 512 blocks, ci % 128 != 0)
+    Fp8Case("f8_copy_occ2_192to136", "copy", 64, 32, 32, 192, 136, dirs=("fwd",), act=LR,
+            instance="fwd <128,2,PRE> e4m3, K = 32: 256 tiles x 2 N-tiles (one ragged), three chunks"),
+    Fp8Case("f8_copy_occ2_64to64", "copy", 128, 32, 32, 64, 64, emit=("fwd", "dgrad"),
+            instance="fwd <64,2,PRE> e4m3 and dgrad <64,2,PRE> e5m2, K = 32: 512 tiles"),
+    Fp8Case("f8_copy_occ2_dgrad_136", "copy", 64, 32, 32, 136, 192, dirs=("dgrad",), act=LR,
+            instance="dgrad <128,2,PRE> e5m2, K = 32 (forward co = 192): 256 tiles x 2 N-tiles (one ragged)"),
+    # ---- block-scaled K = 128 MFMA (ci % 128 == 0, >= 512 blocks): F8 = 3 (e4m3) / 4 (e5m2)
+    Fp8Case("f8_scaled_128to136", "copy", 64, 32, 32, 128, 136, dirs=("fwd",), act=LR,
+            instance="fwd <128,2,F8=3>: one double chunk, ragged second N-tile"),
+    Fp8Case("f8_scaled_256to136", "copy", 64, 32, 32, 256, 136, dirs=("fwd",),
+            instance="fwd <128,2,F8=3>: two double chunks, ragged second N-tile"),
+    Fp8Case("f8_scaled_128to64", "copy", 128, 32, 32, 128, 64, act=LR, emit=("fwd",),
+            instance="fwd <64,2,F8=3>: 512 tiles; dgrad <128,2,PRE> e5m2 on K = 32 (forward co = 64)"),
+    Fp8Case("f8_scaled_dgrad_64", "copy", 128, 32, 32, 64, 128, act=LR, emit=("dgrad",),
+            instance="dgrad <64,2,F8=4> (forward co = 128: one double chunk); fwd <128,2,PRE> e4m3 on K = 32"),
+    Fp8Case("f8_scaled_dgrad_136", "copy", 64, 32, 32, 136, 256, dirs=("dgrad",), act=LR,
+            instance="dgrad <128,2,F8=4>: two double chunks (forward co = 256), ragged second N-tile (forward ci = 136)"),
+    # ---- conv_wgrad3x3_f8_kernel<fp16 input, activation on load>; splitk is what ups_conv_wgrad_plan gives
+    Fp8Case("f8_wgrad_bf16_plain", "wgrad", 2, 16, 32, 64, 128, dirs=("wgrad",), splitk=2,
+            instance="wgrad8 <false,false>: 8 units, split-K 2"),
+    Fp8Case("f8_wgrad_bf16_lrelu_odd", "wgrad", 3, 16, 48, 128, 128, dirs=("wgrad",), act=LR, splitk=4,
+            instance="wgrad8 <false,true>: odd n, w != h, 18 units over 4 splits (a short last split)"),
+    Fp8Case("f8_wgrad_f16_plain_coords", "wgrad", 3, 32, 32, 64, 128, dirs=("wgrad",), coords=True, f16=True, splitk=6,
+            instance="wgrad8 <true,false>: CoordConv rows beside it from the fp32 coordinate kernels"),
+    Fp8Case("f8_wgrad_f16_lrelu_256", "wgrad", 5, 32, 32, 256, 256, dirs=("wgrad",), act=LR, f16=True, splitk=8,
+            instance="wgrad8 <true,true>: 256 -> 256, 8 tile pairs, 40 units: split-K 10 & ~7 = 8"),
+]
+FP8_BY_NAME = {c.name: c for c in FP8_CASES}
+assert len(FP8_BY_NAME) == len(FP8_CASES)
+
+
+def fp8_case_inputs(case):
+    """(x, V, b, g) float64 lattice tensors; CoordConv rows of V are zero (16-aligned maps: no dyadic coordinates)."""
+    g = gen(case.name)
+    x = f8_activations(g, (case.n, case.h, case.w, case.cin), case.xdens)
+    V = torch.zeros(3, 3, case.cin + (2 if case.coords else 0), case.cout, dtype=torch.float64)
+    V[:, :, :case.cin] = f8_weights(g, 3, case.cin, case.cout, case.wdens)
+    b = biases(g, case.cout)
+    go = f8_out_grads(g, (case.n, case.h, case.w, case.cout), case.gdens)
+    return x, V, b, go
+
+
+def _flipped(W):
+    """The weights of the input gradient as a forward convolution of the output gradient (3x3, stride 1, 'SAME')."""
+    return W.flip(0, 1).transpose(2, 3).contiguous()
+
+
+def _tap_wgrad(x, g):
+    """dV[r][s] = sum over pixels of x[pix + (r - 1, s - 1)]^T g[pix]."""
+    n, h, w, ci = x.shape
+    xp = torch.nn.functional.pad(x, (0, 0, 1, 1, 1, 1))
+    G = g.reshape(-1, g.shape[-1])
+    return torch.stack([torch.stack([xp[:, r:r + h, s:s + w].reshape(-1, ci).t() @ G for s in range(3)]) for r in range(3)])
+
+
+def _big(case):
+    return case.n * case.h * case.w * max(case.cin, case.cout) > _REF_KEEP
+
+
+def fp8_headroom(case, inputs=None):
+    """{"fwd", "dgrad", "wgrad", "bgrad"} (the launches the case drives): the largest sum of |products| in units of the smallest LSB
+    among them, IN THE QUANTISED DOMAIN the accumulator sees -- (act(x) * s_a)(w * 64), (g * s_g)(w * 64), (act(x) * s_x)(g * s_g),
+    and g * s_g against the ones operand of the bias sum -- computed as convolutions of |x| with |w|; and of the epilogue's sums
+    (dequantised accumulator + bias + residual, act' * accumulator + residual gradient) in units of their own LSB.
+    Every entry must be below 2**24.  (In float32 for the large cases: a sum of non-negative integers that reaches 2**24 in exact
+    arithmetic cannot round to less, so the comparison with LIMIT is still exact.)"""
+    x, V, b, go = inputs if inputs is not None else fp8_case_inputs(case)
+    T = torch.float32 if _big(case) else torch.float64
+    W = (V[:, :, :case.cin] * F8_SW).abs().to(T)
+    xa = act_fn(x, case.act)
+    A, G = (xa * F8_SA).abs().to(T), (go * F8_SG).abs().to(T)
+    uA, uW, uG = lsb(A, 20), lsb(W, 20), lsb(G, 20)
+    out = {}
+    if "fwd" in case.dirs:
+        acc = conv_same(A, W, None)
+        top = acc.double() / (F8_SA * F8_SW) + b.abs() + (x.abs() if case.res_self else 0.0)
+        tmax = float(top.max()) + (2.0 * _arranged_top(top) if "fwd" in case.emit else 0.0)     # (the arranged bias: |b_c| <= 2 top)
+        out["fwd"] = max(float(acc.max()) / (uA * uW), tmax / min(lsb(xa) * lsb(V), lsb(b)))
+    if "dgrad" in case.dirs:
+        acc = conv_same(G, _flipped(W), None)
+        slope_bits = SLOPE if case.act == "leaky_relu" else 1.0
+        top = acc.double() / (F8_SG * F8_SW) + (go.abs() if case.res_self else 0.0)
+        tmax = _arranged_top(top) if "dgrad" in case.emit else float(top.max())                # (the arranged residual gradient)
+        out["dgrad"] = max(float(acc.max()) / (uG * uW), tmax / (lsb(go) * lsb(V) * slope_bits))
+    if "wgrad" in case.dirs:
+        out["wgrad"] = float(_tap_wgrad(A, G).max()) / (uA * uG)
+        out["bgrad"] = float(G.sum(dim=(0, 1, 2)).max()) / uG
+    return out
+
+
+def _arranged_top(t):
+    """7 * 2**k >= max |t|: the maximum an emitting launch's output is arranged to have, so that ITS delayed scale is dyadic."""
+    m, top = float(t.abs().max()), float(F8_AMP)
+    while top < m:
+        top *= 2.0
+    return top
+
+
+def fp8_reference(case, inputs, T=torch.float64):
+    """The emulation the fp8 kernel tests state, on the lattice: quantise with .to(torch.float8_*), accumulate exactly, dequantise,
+    bias / residual / act', round once to bf16 (weight and bias gradient stay fp32).  T = float32 is used for the large cases once
+    fp8_headroom has shown every sum below 2**24 LSBs: float32 accumulation is then exact too, in any order.
+    Returns a dict: y / gx / gV / gb (float64, unrounded), "lossless" (every quantisation round-trips), and for the emitting launches
+    the arrangement that makes the OUTPUT's maximum 7 * 2**k: "b" (one seeded channel's bias moved so that the maximum of
+    leaky_relu(y) is "y_top"), "res_g" (a residual-gradient tensor, zero but for one element where the sum is zero, which puts
+    "gx_top" there; None if no element qualifies)."""
+    x, V, b, go = inputs
+    cin = case.cin
+    xa = act_fn(x, case.act)
+    xq, okx = f8_quantise(xa, F8_SA, E4M3)
+    gq, okg = f8_quantise(go, F8_SG, E5M2)
+    wq, okw = f8_quantise(V[:, :, :cin], F8_SW, E4M3)       # (m = 7 in every column AND every row: both copies are V * 64)
+    out = {"lossless": okx and okg and okw, "b": b, "res_g": None}
+    if "fwd" in case.dirs:
+        pre0 = conv_same(xq.to(T), wq.to(T), None).double() * ((1.0 / F8_SW) * (1.0 / F8_SA))
+        if case.res_self:
+            pre0 = pre0 + x
+        if "fwd" in case.emit:
+            c = int(torch.randint(0, case.cout, (1,), generator=gen(case.name + "/emit")))
+            top = _arranged_top(lrelu(pre0 + b))
+            b = b.clone()
+            b[c] = top - float(pre0[..., c].max())
+            out["b"], out["y_top"], out["emit_channel"] = b, top, c
+        out["y"] = pre0 + b
+    if "dgrad" in case.dirs:
+        s = conv_same(gq.to(T), _flipped(wq.to(T)), None).double() * ((1.0 / F8_SW) * (1.0 / F8_SG))
+        if case.act == "leaky_relu":
+            s = s * torch.where(x > 0, 1.0, SLOPE).double()
+        if case.res_self:
+            s = s + go
+        if "dgrad" in case.emit:
+            top = _arranged_top(s)
+            zero = ((s == 0) & (go == 0) if case.res_self else (s == 0)).view(-1).nonzero()     # (its sum with go[e] stays a bf16 value)
+            if zero.numel():
+                r = torch.zeros_like(s)
+                r.view(-1)[int(zero[0])] = top
+                out["res_g"], out["gx_top"] = r, top
+                s = s + r
+        out["gx"] = s
+    if "wgrad" in case.dirs:
+        out["gV"] = _tap_wgrad(xq.to(T), gq.to(T)).double() * ((1.0 / F8_SA) * (1.0 / F8_SG))
+        out["gb"] = gq.to(T).sum(dim=(0, 1, 2)).double() * (1.0 / F8_SG)
+    return out
+
+
+def plain_reference(case, inputs, ref, T=torch.float64):
+    """The same launches as the plain integer convolution (no quantisation anywhere), with the arrangement `ref` made (bias,
+    residual gradient), by the tap loop; tests/test_host_exact_fp8.py holds it to conv_block + autograd where the case is small."""
+    x, V, b, go = inputs
+    Vm = V[:, :, :case.cin]
+    out = {}
+    if "fwd" in case.dirs:
+        out["y"] = conv_same(act_fn(x, case.act).to(T), Vm.to(T), None).double() + ref["b"] + (x if case.res_self else 0.0)
+    if "dgrad" in case.dirs:
+        s = conv_same(go.to(T), _flipped(Vm.to(T)), None).double()
+        if case.act == "leaky_relu":
+            s = s * torch.where(x > 0, 1.0, SLOPE).double()
+        out["gx"] = s + (go if case.res_self else 0.0) + (ref["res_g"] if ref["res_g"] is not None else 0.0)
+    if "wgrad" in case.dirs:
+        out["gV"] = _tap_wgrad(act_fn(x, case.act).to(T), go.to(T)).double()
+        out["gb"] = go.sum(dim=(0, 1, 2))
+    return out
+
+
+def fp8_case_reference(case):
+    """(inputs, reference dict, headroom dict) of an fp8 case, cached like case_reference (the large cases: recomputed)."""
+    if case.name in _REF:
+        return _REF[case.name]
+    inputs = fp8_case_inputs(case)
+    hr = fp8_headroom(case, inputs)
+    exact32 = _big(case) and max(hr.values()) < LIMIT
+    out = (inputs, fp8_reference(case, inputs, torch.float32 if exact32 else torch.float64), hr)
+    if not _big(case):
+        _REF[case.name] = out
+    return out
