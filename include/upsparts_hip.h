@@ -547,6 +547,37 @@ size_t ups_part_usage_scratch_bytes(int32_t N, int64_t HW);
 int ups_part_usage(const float* soft, const int64_t* pred, int32_t N, int64_t HW, int32_t P, int32_t* counts, int32_t* invalid,
                    double* sharp, void* scratch, void* stream);
 
+/* ---------------------------------------------------------------- segmentation export (csrc/segexport.hip)
+ * Added without a new UPS_ABI_VERSION, as the ups_augment_* entries: no struct changed, and a binding that expects these symbols fails
+ * to load an older library by name.  The reference never renders a part map above the model's resolution: the definitions here are
+ * the specification (tests/segexport_ref.py restates them in NumPy float64, and the bytes are equal).
+ *
+ * ups_segment_render: one launch renders n images, image i at its own size h_i x w_i, from the soft-max maps.
+ *   soft   [n, S, S, P] fp32, contiguous, finite: out_parts_soft (ups_part_softmax_fwd)
+ *   table_host / table  [n, ups_segment_table_words() = 4] int32 rows (pixel_offset, h, w, first_block): the SAME numbers on the host
+ *          (read by the launcher's checks) and on the device (read by the kernel).  pixel_offset: where image i starts in every packed
+ *          plane, a multiple of 16, ascending, images not overlapping; first_block: the sum over the images before i of
+ *          ceil(h * w / ups_segment_chunk())
+ *   total  pixels of each packed plane: every pixel_offset + h * w <= total <= 2^31 - 1
+ *   src    uint8 [total, 3] packed RGB source images at the output sizes, or NULL;   colors  uint8 [P, 3] (required with overlay)
+ *   labels uint8 [total], overlay uint8 [total, 3], confidence uint8 [total]: each may be NULL (skipped); only the h * w pixels of
+ *          each image are written, the alignment gaps between images keep their bytes
+ *   counts int32 [n, P] or NULL, caller-zeroed or holding earlier launches' counts: += #{pixels of image i with label p}
+ * For output pixel (y, x):  sy = ((y + 0.5) * S) / h - 0.5 clamped to [0, S-1], y0 = floor(sy), y1 = min(y0 + 1, S-1), fy = sy - y0
+ * (x alike);  v_p = (1-fy) ((1-fx) a00 + fx a01) + fy ((1-fx) a10 + fx a11) in fp64 on the fp32 values, no contraction;
+ * label = first p with maximal v_p;  confidence = clamp(floor(v_label * 255 + 0.5), 0, 255);
+ * overlay_c = clamp(floor(alpha * colors[label][c] + (1 - alpha) * src_c + 0.5), 0, 255), or colors[label][c] when src is NULL.
+ * The same formula shrinks (h < S) without antialiasing; at h = w = S the label is the first maximal index of soft itself.
+ * Integer atomics only (an LDS histogram per block, one global add per block and part).
+ * UPS_E_UNSUPPORTED: P > 255.  UPS_E_ARG, nothing launched: P < 1, n < 1, S < 1, S * S * P >= 2^29, a NULL soft or table, all four outputs NULL, overlay
+ * without colors, alpha outside [0, 1], h or w < 1, a pixel_offset that is negative, no multiple of 16, not ascending or past total, a
+ * first_block that is not the prefix sum, a plane, src or counts pointer that is not 4-byte aligned. */
+int32_t ups_segment_chunk(void);
+int32_t ups_segment_table_words(void);
+int ups_segment_render(const float* soft, int32_t n, int32_t S, int32_t P, const int32_t* table_host, const int32_t* table,
+                       int64_t total, const uint8_t* src, const uint8_t* colors, double alpha, uint8_t* labels, uint8_t* overlay,
+                       uint8_t* confidence, int32_t* counts, void* stream);
+
 /* ---------------------------------------------------------------- mask priors (M:652-797), fused
  * One pass over l/m per view producing the partial sums, one fused backward producing dl.
  * See csrc/priors.hip for the slot layout of `sums`. */

@@ -63,14 +63,30 @@ def have_pil():
         return False
 
 
+class Paletted(object):
+    """A label map uint8 [H,W] with its palette uint8 [P,3]: ``encode_png`` writes it as a mode-P PNG -- viewers show the colours, the
+    bytes are the labels (the segmentation export's label maps)."""
+
+    def __init__(self, array, palette):
+        self.array, self.palette = array, np.asarray(palette, dtype=np.uint8).reshape(-1, 3)
+
+
 def encode_png(path, array):
-    """uint8 [H,W,3] or [H,W,1] / [H,W] -> PNG, written under a temporary name and renamed."""
+    """uint8 [H,W,3] or [H,W,1] / [H,W] -> PNG, written under a temporary name and renamed.  A ``Paletted`` map -> a palette PNG."""
     from PIL import Image
+    palette = None
+    if isinstance(array, Paletted):
+        array, palette = array.array, array.palette
     a = np.asarray(array)
     if a.ndim == 3 and a.shape[2] == 1:
         a = a[:, :, 0]
     tmp = path + ".tmp-{}".format(os.getpid())
-    Image.fromarray(a).save(tmp, format="PNG")
+    if palette is None:
+        img = Image.fromarray(a)
+    else:
+        img = Image.fromarray(np.ascontiguousarray(a, dtype=np.uint8), mode="P")
+        img.putpalette(palette.tobytes())
+    img.save(tmp, format="PNG")
     os.replace(tmp, path)
 
 
@@ -78,10 +94,11 @@ class ImageWriter(object):
     """One worker thread behind a bounded queue (depth 2).  ``submit`` hands over the canvases of one step -- host arrays, or pinned
     tensors with the event of the copy that fills them -- and BLOCKS while the queue is full: nothing is ever dropped.  ``flush``
     returns once everything submitted has been written; ``close`` also ends the thread.  An exception in the worker is re-raised by
-    the next submit / flush / close."""
+    the next submit / flush / close.  ``path_fn(root, name, step)`` names the files (default: ``image_path``, the training logs'
+    rule); the file's directory is created."""
 
-    def __init__(self, root, encode=encode_png, depth=QUEUE_DEPTH):
-        self.root, self.encode = root, encode
+    def __init__(self, root, encode=encode_png, depth=QUEUE_DEPTH, path_fn=image_path):
+        self.root, self.encode, self.path_fn = root, encode, path_fn
         self.q = queue.Queue(maxsize=depth)
         self.error = None
         self.written = []
@@ -98,9 +115,11 @@ class ImageWriter(object):
                 if self.error is None:
                     if ready is not None:
                         ready.synchronize()                     # the device-to-host copies of this step (side stream)
-                    os.makedirs(os.path.join(self.root, "train"), exist_ok=True)
+                    if self.path_fn is image_path:
+                        os.makedirs(os.path.join(self.root, "train"), exist_ok=True)
                     for name, a in images.items():
-                        path = image_path(self.root, name, step)
+                        path = self.path_fn(self.root, name, step)
+                        os.makedirs(os.path.dirname(path), exist_ok=True)
                         self.encode(path, a.numpy() if hasattr(a, "numpy") else a)
                         self.written.append(path)
             except BaseException as e:      # noqa: B902 -- reported to the training thread

@@ -161,6 +161,9 @@ _SIGS = {
     "ups_part_usage_chunk": ([], _I),
     "ups_part_usage_scratch_bytes": ([_I, _L], _Z),
     "ups_part_usage": ([_P, _P, _I, _L, _I, _P, _P, _P, _P, _P], C.c_int),
+    "ups_segment_chunk": ([], _I),
+    "ups_segment_table_words": ([], _I),
+    "ups_segment_render": ([_P, _I, _I, _I, C.POINTER(_I), _P, _L, _P, _P, C.c_double, _P, _P, _P, _P, _P], C.c_int),
     "ups_prior_sums_floats": ([_I, _I], _Z),
     "ups_prior_fwd": ([C.POINTER(PriorDesc), _P], C.c_int),
     "ups_prior_bwd": ([C.POINTER(PriorDesc), _P], C.c_int),

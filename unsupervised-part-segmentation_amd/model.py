@@ -72,6 +72,7 @@ class TrainModel(object):
         self.nets = N.Nets(config, self.device, seed if seed is not None else config.get("seed", 0))
         self.bank = self.nets.bank
         self._last, self._tps, self.generated_act = {}, {}, None
+        self._seg_stream = None             # export_segments: the side stream of its device-to-host copies (made on first use)
 
     # model.py:260-263
     @property
@@ -156,11 +157,12 @@ class TrainModel(object):
     # training graph's _cross_generated, SB_model48i/model.py:488-500).  Only unpool_features and the hourglass decoder depend on
     # the (pose, appearance) pair: n poses and m appearances are encoded once each, K = n * m combinations are decoded.  Test-mode
     # semantics as forward(batch, noise=None): latent means, no sampling noise, this model's Fp8State active.
-    def _encode(self, *groups, masks=True):
+    def _encode(self, *groups, masks=True, soft=False):
         """groups: (views [n_g,S,S,3], want_feat) -> one dict per group.  The pose path (e_pi, dv, soft-max) runs ONCE over all groups
         concatenated, as ``forward`` runs it over view0 and view1 together: the convolutions' split-K factors depend on the batch, so
         only the same batch composition gives ``forward``'s bits.  e_alpha runs per group that wants features (forward: view1).
-        masks=False (``segment``): only "out_parts_hard" per group -- no hard masks, no bit sets, nothing for e_alpha to read."""
+        masks=False (``segment``): only "out_parts_hard" per group -- no hard masks, no bit sets, nothing for e_alpha to read;
+        with soft=True (``segment_soft``) also "out_parts_soft", the fp32 soft-max the arg-max is taken of."""
         cfg = self.config
         ops.Fp8.activate(self.fp8)
         vs = [g[0].to(self.device, torch.float32).contiguous() for g in groups]
@@ -172,15 +174,15 @@ class TrainModel(object):
         lm = self.nets.dv(self.latent_act(pe[:, :Z].contiguous())).t
         if masks:
             _, m, hard, _, bits = ops.part_softmax(lm, None, want_bits=P <= 32)
-        _, soft, _, amax = ops.part_softmax(lm.contiguous(), None, want_hard=False, want_argmax=True)
+        _, smax, _, amax = ops.part_softmax(lm.contiguous(), None, want_hard=False, want_argmax=True)
         outs, o = [], 0
         for vg, (_, want_feat) in zip(vs, groups):
             sl = slice(o, o + vg.shape[0])
             o += vg.shape[0]
             if not masks:
-                outs.append({"out_parts_hard": amax[sl]})
+                outs.append({"out_parts_hard": amax[sl], "out_parts_soft": smax[sl]} if soft else {"out_parts_hard": amax[sl]})
                 continue
-            out = {"hard": hard[sl].contiguous(), "out_parts_hard": amax[sl], "out_parts_soft": soft[sl], "m0_sample": m[sl]}
+            out = {"hard": hard[sl].contiguous(), "out_parts_hard": amax[sl], "out_parts_soft": smax[sl], "m0_sample": m[sl]}
             if want_feat:
                 yp = self.nets.e_alpha(self.part_images(img[sl], vg, out["hard"], None if bits is None else bits[sl].contiguous())).t
                 out["feat"] = yp.float().view(P, vg.shape[0], A).permute(1, 0, 2).contiguous()
@@ -205,20 +207,73 @@ class TrainModel(object):
         ``forward({"view0": views[:B], "view1": views[B:]})["out_parts_hard"]``.  A shorter last pass is padded to 2 * batch_size with
         copies of its first image and the padding is dropped, so every pass plans alike.  Test-mode semantics (latent means, no
         noise).  Under precision: fp8 a pass records activation maxima like any forward."""
+        return self._segment(views, False)[0]
+
+    def _segment(self, views, want_soft):
         B = int(self.config["batch_size"])
         views = torch.as_tensor(views)
         n, S = views.shape[0], views.shape[1]
         out = torch.empty((n, S, S), dtype=torch.int64, device=self.device)
+        soft = torch.empty((n, S, S, self.n_parts), dtype=torch.float32, device=self.device) if want_soft else None
         for c0 in range(0, n, 2 * B):
             v = views[c0:c0 + 2 * B].to(self.device, torch.float32)
             k = v.shape[0]
             if k < 2 * B:
                 v = torch.cat([v, v[:1].expand(2 * B - k, S, S, v.shape[3])], 0)
-            a, b = self._encode((v[:B], False), (v[B:], False), masks=False)
+            a, b = self._encode((v[:B], False), (v[B:], False), masks=False, soft=want_soft)
             out[c0:c0 + min(k, B)] = a["out_parts_hard"][:k]
             if k > B:
                 out[c0 + B:c0 + k] = b["out_parts_hard"][:k - B]
-        return out
+            if want_soft:
+                soft[c0:c0 + min(k, B)] = a["out_parts_soft"][:k]
+                if k > B:
+                    soft[c0 + B:c0 + k] = b["out_parts_soft"][:k - B]
+        return out, soft
+
+    @torch.no_grad()
+    def segment_soft(self, views):
+        """``segment`` that keeps the soft map: (``out_parts_hard`` int64 [n,S,S], ``out_parts_soft`` float32 [n,S,S,P]) on the device.
+        The same passes of 2 * batch_size images and the same padding as ``segment``, so both are ``forward``'s bits for the batch
+        composition its docstring names; the arg-max is the first maximal index of the soft map."""
+        return self._segment(views, True)
+
+    @torch.no_grad()
+    def export_segments(self, views, sizes, sources=None, outputs=("labels", "overlay"), alpha=0.5, colors=None, maps=None,
+                        after_launch=None):
+        """Part maps of `views` [n,S,S,3] rendered at their own sizes: one ``segment_soft`` and ONE ups_segment_render launch
+        (``ops.segment_render``: label = first maximal part of the bilinearly resampled soft map, decided in fp64).
+        sizes [(h_i, w_i)]; sources: None or n uint8 [h_i,w_i,3] images the overlay blends with (weight 1 - alpha);
+        outputs: any of labels / overlay / confidence; colors uint8 [P,3] (default: the palette of the training image logs).
+        maps: the (hard, soft) of an earlier ``segment_soft(views)`` (the pass is then not run again); after_launch: called once the
+        kernel is launched and before the copies are queued (a profiler's lap).
+        The per-part pixel counts are always taken.  The planes are copied into pinned host buffers on a side stream behind an event
+        (as the image logs' canvases): nothing here waits for the device.  Returns {"table", "total", "host": {name: pinned
+        tensor, "counts" included}, "views": {name: [per-image host views]}, "ready": the copies' event, "soft", "hard": the device
+        maps of ``segment_soft``}: read the host buffers after ``ready.synchronize()``."""
+        outputs = tuple(outputs)
+        if not outputs or any(k not in ("labels", "overlay", "confidence") for k in outputs):
+            raise L.UpsError("export_segments: outputs is a non-empty subset of labels / overlay / confidence (got {})".format(outputs))
+        dev = self.device
+        hard, soft = self.segment_soft(views) if maps is None else maps
+        if colors is None and "overlay" in outputs:
+            colors = IL.mask_color_bytes(IL.mask_colors01(self.n_parts))
+        res = ops.segment_render(soft, sizes, src=sources if "overlay" in outputs else None, colors=colors, alpha=alpha,
+                                 want=outputs + ("counts",))
+        if after_launch is not None:
+            after_launch()
+        if self._seg_stream is None:
+            self._seg_stream = torch.cuda.Stream(dev)
+        main, side = torch.cuda.current_stream(dev), self._seg_stream
+        side.wait_stream(main)
+        host = OrderedDict()
+        with torch.cuda.stream(side):
+            for k in outputs + ("counts",):
+                res[k].record_stream(side)
+                host[k] = torch.empty(res[k].shape, dtype=res[k].dtype, pin_memory=True)
+                host[k].copy_(res[k], non_blocking=True)
+            ready = side.record_event()
+        return {"table": res["table"], "total": res["total"], "host": host, "ready": ready, "soft": soft, "hard": hard,
+                "views": {k: ops.segment_views(host[k], res["table"]) for k in outputs}}
 
     @torch.no_grad()
     def encode_appearance(self, views):

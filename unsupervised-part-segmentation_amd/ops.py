@@ -1899,6 +1899,113 @@ def part_usage(soft, pred, counts=None, invalid=None, sharp=None):
     return counts, invalid, sharp
 
 
+# --------------------------------------------------------------------------- segmentation export (csrc/segexport.hip)
+SEGMENT_CHUNK = 1024            # pixels per block of ups_segment_render (checked against the library on first use)
+SEGMENT_ALIGN = 16              # an image's pixel offset in the packed planes is a multiple of it
+SEGMENT_OUTPUTS = ("labels", "overlay", "confidence", "counts")
+_SEGMENT_CHECKED = []
+
+
+def segment_table(sizes):
+    """sizes [(h, w)] -> (table int32 NumPy [n,4], total): row i = (pixel_offset, h, w, first_block) of image i in the packed planes of
+    ups_segment_render.  An image starts where the previous one ends, rounded up to a multiple of 16 pixels (so every image starts
+    16-byte aligned in the uint8 planes and a lane stores 4 labels as one dword); first_block is the prefix sum of
+    ceil(h * w / SEGMENT_CHUNK); total is the length of a plane in pixels (a multiple of 16).  Host arithmetic only."""
+    import numpy as np
+    rows, off, blk = [], 0, 0
+    for hw in sizes:
+        h, w = int(hw[0]), int(hw[1])
+        if h < 1 or w < 1:
+            raise L.UpsError("segment_table: sizes (h, w) with h, w >= 1 (got {})".format((h, w)))
+        rows.append((off, h, w, blk))
+        blk += -(-(h * w) // SEGMENT_CHUNK)
+        off = -(-(off + h * w) // SEGMENT_ALIGN) * SEGMENT_ALIGN
+    if not rows or off > 0x7fffffff or blk > 0x7fffffff:
+        raise L.UpsError("segment_table: 1 .. 2^31 - 1 pixels in all (got {} images, {} pixels)".format(len(rows), off))
+    return np.asarray(rows, dtype=np.int32).reshape(-1, 4), off
+
+
+def segment_pack_sources(sources, table, total):
+    """Source images [(h_i, w_i, 3) uint8 NumPy arrays or tensors] -> one pinned uint8 host tensor [total, 3] packed by `table`
+    (the alignment gaps are zero)."""
+    import numpy as np
+    host = torch.zeros((total, 3), dtype=torch.uint8)
+    if torch.cuda.is_available():
+        host = host.pin_memory()
+    flat = host.numpy()
+    if len(sources) != len(table):
+        raise L.UpsError("segment_render: {} source images for {} sizes".format(len(sources), len(table)))
+    for (off, h, w, _), s in zip(table.tolist(), sources):
+        a = s.cpu().numpy() if torch.is_tensor(s) else np.asarray(s)
+        if a.dtype != np.uint8 or a.shape != (h, w, 3):
+            raise L.UpsError("segment_render: a source image of uint8 [{},{},3] expected (got {} {})".format(h, w, a.dtype, a.shape))
+        flat[off:off + h * w] = a.reshape(-1, 3)
+    return host
+
+
+def segment_render(soft, sizes, src=None, colors=None, alpha=0.5, want=("labels",), out=None):
+    """Label maps / overlays / confidence maps / part counts of n images, image i at its own size sizes[i] = (h, w), in one launch
+    (ups_segment_render; the definitions: csrc/segexport.hip, restated by tests/segexport_ref.py with equal bytes).
+    soft [n,S,S,P] float32 on the device (out_parts_soft); src: None, a list of uint8 [h_i,w_i,3] images (packed here) or an already
+    packed uint8 [total,3] device tensor; colors [P,3] uint8 (device tensor or array; required for the overlay); 0 <= alpha <= 1: the
+    colour's weight.  want: any of SEGMENT_OUTPUTS.  out: {name: tensor} of planes to reuse (uint8 [total] / [total,3], counts int32
+    [n,P] which is ADDED to); a missing plane is allocated (planes as zeros, so the alignment gaps are defined).
+    Returns {"table" (NumPy), "table_dev", "total", <the wanted packed tensors>, "views": {name: [per-image views [h,w] / [h,w,3]]}}.
+    Asynchronous on the current stream."""
+    if not _SEGMENT_CHECKED:
+        lib = L.load()
+        got = (lib.ups_segment_chunk(), lib.ups_segment_table_words())
+        if got != (SEGMENT_CHUNK, 4):
+            raise L.UpsError("the library's segment chunk / table words {} differ from ops' {}: rebuild".format(got, (SEGMENT_CHUNK, 4)))
+        _SEGMENT_CHECKED.append(True)
+    want = tuple(want)
+    if not want or any(k not in SEGMENT_OUTPUTS for k in want):
+        raise L.UpsError("segment_render: want is a non-empty subset of {} (got {})".format(SEGMENT_OUTPUTS, want))
+    if not torch.is_tensor(soft) or not soft.is_cuda or soft.dim() != 4 or soft.dtype != torch.float32 or soft.shape[1] != soft.shape[2]:
+        raise L.UpsError("segment_render: soft [n,S,S,P] float32 on the device expected (got {})".format(
+            (tuple(soft.shape), soft.dtype) if torch.is_tensor(soft) else type(soft)))
+    n, S, _, P = soft.shape
+    if len(sizes) != n:
+        raise L.UpsError("segment_render: {} sizes for {} maps".format(len(sizes), n))
+    dev = soft.device
+    table, total = segment_table(sizes)
+    table_dev = torch.from_numpy(table).to(dev)
+    soft = soft.contiguous()
+    if "overlay" in want and colors is None:
+        raise L.UpsError("segment_render: the overlay needs `colors` [P,3] uint8")
+    if colors is not None:
+        colors = torch.as_tensor(colors).to(dev).contiguous()
+        if colors.dtype != torch.uint8 or tuple(colors.shape) != (P, 3):
+            raise L.UpsError("segment_render: colors [{},3] uint8 expected (got {} {})".format(P, tuple(colors.shape), colors.dtype))
+    if src is not None and not torch.is_tensor(src):
+        src = segment_pack_sources(src, table, total).to(dev, non_blocking=True)
+    if src is not None and (not src.is_cuda or src.dtype != torch.uint8 or tuple(src.shape) != (total, 3)):
+        raise L.UpsError("segment_render: packed sources uint8 [{},3] on the device expected (got {} {})".format(
+            total, tuple(src.shape), src.dtype))
+    shapes = {"labels": ((total,), torch.uint8), "overlay": ((total, 3), torch.uint8), "confidence": ((total,), torch.uint8),
+              "counts": ((n, P), torch.int32)}
+    res = {"table": table, "table_dev": table_dev, "total": total}
+    for k in want:
+        t = None if out is None else out.get(k)
+        if t is None:
+            t = torch.zeros(shapes[k][0], dtype=shapes[k][1], device=dev)
+        if not t.is_cuda or t.dtype != shapes[k][1] or tuple(t.shape) != shapes[k][0] or not t.is_contiguous():
+            raise L.UpsError("segment_render: out[{!r}] {} {} expected (got {} {})".format(k, shapes[k][1], shapes[k][0], t.dtype,
+                                                                                         tuple(t.shape)))
+        res[k] = t
+    L.call("ups_segment_render", L.ptr(soft), n, S, P, table.ctypes.data_as(C.POINTER(C.c_int32)), L.ptr(table_dev), total,
+           L.ptr(src.contiguous()) if src is not None else None, L.ptr(colors), float(alpha), L.ptr(res.get("labels")),
+           L.ptr(res.get("overlay")), L.ptr(res.get("confidence")), L.ptr(res.get("counts")), L.stream())
+    res["views"] = {k: segment_views(res[k], table) for k in want if k != "counts"}
+    return res
+
+
+def segment_views(plane, table):
+    """The per-image views [h,w] (or [h,w,3]) of a packed plane [total] (or [total,3]), device or host, by `table`."""
+    tail = tuple(plane.shape[1:])
+    return [plane[off:off + h * w].view((h, w) + tail) for off, h, w, _ in table.tolist()]
+
+
 # --------------------------------------------------------------------------- training image logs (csrc/canvas.hip): uint8 canvases
 def canvas_grid(n, cols=None):
     """(rows, cols) of tf_batch_to_canvas for n tiles (re-derived, UNVERIFIED): cols=None -> the square grid of side ceil(sqrt(n)),

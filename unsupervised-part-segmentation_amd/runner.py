@@ -16,12 +16,16 @@ is given (then it raises).
 ``--transfer <yaml> -c <ckpt> [--parts 0,3,..]`` is the work-alike of final_eval/eval_transfer.py: one ``TrainModel.transfer_matrix``
 call per block of ``data.TransferData``, the cells pickled to <root>/comparison_matrix/<global_step:06>/data.p with the reference
 MatrixHook's key set (its plotting script reads the file) and drawn by ``evalutil.write_transfer_matrix``.
+
+``--segment <yaml> -c <ckpt>`` has no counterpart in the reference: the images listed in ``segment_csv`` are segmented and their part
+maps written as PNG files at the resolution of the source photographs (``segment``).
 """
 import argparse
 import importlib
 import logging
 import os
 import time
+from collections import OrderedDict
 
 import torch
 import yaml
@@ -112,6 +116,9 @@ def main(argv=None):
                     help="evaluation yaml(s): test-mode forward over the dataset, outputs pickled (edflow -e work-alike)")
     ap.add_argument("--transfer", nargs="+", default=None,
                     help="transfer yaml(s): pose i x appearance j comparison matrices (final_eval/eval_transfer.py work-alike)")
+    ap.add_argument("--segment", nargs="+", default=None,
+                    help="segmentation yaml(s): label maps / overlays / confidence maps of the images in segment_csv, as PNG files "
+                         "at source resolution under <root>/segment/<global_step>/")
     ap.add_argument("--parts", default=None, help="--transfer: comma-separated part ids taken from the column image (default: all)")
     ap.add_argument("--eval-batches", type=int, default=None, help="number of batches to evaluate (default: one epoch)")
     ap.add_argument("-c", "--checkpoint", default=None)
@@ -120,8 +127,10 @@ def main(argv=None):
     ap.add_argument("--set", nargs="*", default=[], help="key=value overrides (yaml-parsed)")
     ap.add_argument("--strict-dataset", action="store_true")
     args = ap.parse_args(argv)
-    if (args.train is not None) + (args.eval is not None) + (args.transfer is not None) != 1:
-        ap.error("exactly one of -t / -e / --transfer is required")
+    if (args.train is not None) + (args.eval is not None) + (args.transfer is not None) + (args.segment is not None) != 1:
+        ap.error("exactly one of -t / -e / --transfer / --segment is required")
+    if args.segment is not None:
+        return segment(args)
     if args.transfer is not None:
         return transfer(args)
     if args.eval is not None:
@@ -344,6 +353,183 @@ def transfer(args):
     evalutil.write_transfer_matrix(data, os.path.join(odir, "comparison_matrix.png"), gk, k0, k1)
     print("[INFO] comparison matrix data written to", os.path.join(odir, "data.p"))
     return data
+
+
+SEGMENT_OUTPUTS = ("labels", "overlay", "confidence")
+
+
+def segment_options(cfg):
+    """The `segment_*` keys of a yaml, validated: {"csv", "size", "max_side", "outputs", "alpha"}.  ValueError on anything else."""
+    csv_path = cfg.get("segment_csv")
+    if not csv_path:
+        raise ValueError("--segment: `segment_csv` (one image path per line, relative to data_root) is required")
+    size = cfg.get("segment_size", "source")
+    if isinstance(size, (list, tuple)):
+        if len(size) != 2 or any(not isinstance(v, int) or isinstance(v, bool) or v < 1 for v in size):
+            raise ValueError("segment_size: source | model | [h, w] with h, w >= 1 (got {!r})".format(size))
+        size = (int(size[0]), int(size[1]))
+    elif size not in ("source", "model"):
+        raise ValueError("segment_size: source | model | [h, w] (got {!r})".format(size))
+    max_side = cfg.get("segment_max_side", 1024)
+    if not isinstance(max_side, int) or isinstance(max_side, bool) or max_side < 1:
+        raise ValueError("segment_max_side: an integer >= 1 (got {!r})".format(max_side))
+    outputs = cfg.get("segment_outputs", ["labels", "overlay"])
+    if isinstance(outputs, str):
+        outputs = [outputs]
+    outputs = tuple(outputs)
+    if not outputs or len(set(outputs)) != len(outputs) or any(k not in SEGMENT_OUTPUTS for k in outputs):
+        raise ValueError("segment_outputs: a non-empty list of distinct names of {} (got {!r})".format(SEGMENT_OUTPUTS, list(outputs)))
+    alpha = cfg.get("segment_alpha", 0.5)
+    if isinstance(alpha, bool) or not isinstance(alpha, (int, float)) or not 0.0 <= float(alpha) <= 1.0:
+        raise ValueError("segment_alpha: a number in [0, 1] (got {!r})".format(alpha))
+    return {"csv": csv_path, "size": size, "max_side": int(max_side), "outputs": outputs, "alpha": float(alpha)}
+
+
+def segment_output_size(h, w, opt, S):
+    """The rendered size of an h x w source under `segment_size` / `segment_max_side`: (h', w', scaled).  A size whose longer side
+    exceeds max_side is scaled down to it, proportions kept (rounded, at least 1)."""
+    if opt["size"] == "model":
+        h, w = S, S
+    elif opt["size"] != "source":
+        h, w = opt["size"]
+    m = max(h, w)
+    if m <= opt["max_side"]:
+        return int(h), int(w), False
+    return max(1, (h * opt["max_side"] + m // 2) // m), max(1, (w * opt["max_side"] + m // 2) // m), True
+
+
+def segment_png_path(root, name, step):
+    """ImageWriter path rule of the export: name = (kind, relative path) -> <root>/segment/<step>/<kind>/<relative path>.png"""
+    kind, rel = name
+    return os.path.join(root, "segment", str(step), kind, rel + ".png")
+
+
+def write_segment_index(path, rows, n_parts):
+    """index.csv: one row per image -- file, h, w and area_<p> = count_p / (h w) from the kernel's counts."""
+    import csv
+    with open(path, "w", newline="") as f:
+        wr = csv.writer(f)
+        wr.writerow(["file", "h", "w"] + ["area_{}".format(p) for p in range(n_parts)])
+        for rel, h, w, counts in rows:
+            wr.writerow([rel, h, w] + [repr(int(c) / float(h * w)) for c in counts])
+
+
+def segment_files(model, cfg, root, step, profile=None):
+    """The export itself: every image of `segment_csv` is decoded ONCE with PIL, resized to S x S by the dataset's preprocess_image
+    rule (bilinear, / 127.5 - 1) for the model and kept at its output size as uint8 for the overlay; passes of 2 * batch_size images
+    go through ``TrainModel.export_segments`` (one pose pass and one ups_segment_render launch each) and the planes, copied into
+    pinned buffers behind an event, are encoded by the bounded writer thread (it blocks, never drops, and is joined before return).
+    A missing file raises FileNotFoundError before anything is computed: there is no synthetic fall-back on this route.
+    profile: a dict that receives wall-clock seconds per phase (decode, model passes, packing and upload of the sources, kernel,
+    copies, encode); the phases are then SYNCHRONISED so that the device time is attributed, which a normal run does not do.
+    Returns the index rows."""
+    import numpy as np
+    from PIL import Image
+    from . import imglog as IL
+    from . import ops
+    opt = segment_options(cfg)
+    S, B = int(cfg["spatial_size"]), int(cfg["batch_size"])
+    data_root = cfg["data_root"]
+    rels = _data.TransferData._read_list(opt["csv"])
+    if not rels:
+        raise ValueError("--segment: {} lists no image".format(opt["csv"]))
+    for rel in rels:
+        if not os.path.isfile(os.path.join(data_root, rel)):
+            raise FileNotFoundError("--segment: {} (listed in {}) does not exist".format(os.path.join(data_root, rel), opt["csv"]))
+    palette = IL.mask_color_bytes(IL.mask_colors01(model.n_parts))
+    writer = IL.ImageWriter(root, path_fn=segment_png_path)
+    rows, pending, warned = [], [], False
+    t = dict.fromkeys(("decode", "model", "upload", "kernel", "copies", "encode"), 0.0)
+    dev = model.device
+
+    def lap(key, t0):
+        if profile is not None:
+            torch.cuda.synchronize(dev)
+            t[key] += time.perf_counter() - t0
+        return time.perf_counter()
+    try:
+        for c0 in range(0, len(rels), 2 * B):
+            chunk = rels[c0:c0 + 2 * B]
+            t0 = time.perf_counter()
+            views, sizes, sources = [], [], []
+            for rel in chunk:
+                img = Image.open(os.path.join(data_root, rel)).convert("RGB")
+                views.append(np.asarray(img.resize((S, S), Image.BILINEAR), dtype=np.float32) / 127.5 - 1.0)
+                h, w, scaled = segment_output_size(img.height, img.width, opt, S)
+                if scaled and not warned:
+                    warned = True
+                    LOG.warning("--segment: sources larger than segment_max_side = %d are rendered scaled down to it (first: %s, "
+                                "%d x %d -> %d x %d)", opt["max_side"], rel, img.height, img.width, h, w)
+                sizes.append((h, w))
+                if "overlay" in opt["outputs"]:
+                    sources.append(np.asarray(img if (img.height, img.width) == (h, w) else img.resize((w, h), Image.BILINEAR),
+                                              dtype=np.uint8))
+            t0 = lap("decode", t0)
+            vt = torch.from_numpy(np.stack(views))
+            if profile is None:
+                res = model.export_segments(vt, sizes, sources=sources or None, outputs=opt["outputs"], alpha=opt["alpha"], colors=palette)
+            else:                           # the phases apart: the pose pass, the kernel and the copies each behind a synchronisation
+                maps = model.segment_soft(vt)
+                t0 = lap("model", t0)
+                packed = None
+                if sources:
+                    table, total = ops.segment_table(sizes)
+                    packed = ops.segment_pack_sources(sources, table, total).to(dev)
+                t0 = lap("upload", t0)
+                laps = []
+                res = model.export_segments(vt, sizes, sources=packed, outputs=opt["outputs"], alpha=opt["alpha"],
+                                            colors=palette, maps=maps, after_launch=lambda: laps.append(lap("kernel", t0)))
+                res["ready"].synchronize()
+                lap("copies", laps[0])
+            images = OrderedDict()
+            for i, rel in enumerate(chunk):
+                for kind in opt["outputs"]:
+                    v = res["views"][kind][i]
+                    images[(kind, rel)] = IL.Paletted(v, palette) if kind == "labels" else v
+            writer.submit(step, images, res["ready"])
+            pending.append((chunk, sizes, res["host"]["counts"], res["ready"]))       # (the planes live on in the writer's queue only)
+            if profile is not None:         # encoded here and now, not beside the next pass
+                t0 = time.perf_counter()
+                writer.flush()
+                t["encode"] += time.perf_counter() - t0
+        writer.flush()
+    finally:
+        writer.close()
+    for chunk, sizes, counts, ready in pending:
+        ready.synchronize()
+        for i, rel in enumerate(chunk):
+            rows.append((rel, sizes[i][0], sizes[i][1], [int(c) for c in counts[i].tolist()]))
+    odir = os.path.join(root, "segment", str(step))
+    os.makedirs(odir, exist_ok=True)
+    write_segment_index(os.path.join(odir, "index.csv"), rows, model.n_parts)
+    if profile is not None:
+        profile.update(t)
+    return rows
+
+
+def segment(args):
+    """``--segment``: see ``segment_files``.  Outputs: <root>/segment/<global_step>/{labels,overlay,confidence}/<relative path>.png
+    (labels: a palette PNG whose bytes are the part ids) and index.csv.  Returns {"rows", "root", "dir", "model"}."""
+    cfg = load_config(args.segment)
+    for kv in args.set:
+        k, v = kv.split("=", 1)
+        cfg[k] = yaml.safe_load(v)
+    cfg["test_mode"] = True
+    segment_options(cfg)            # a wrong key fails before a device is touched
+    if not cfg.get("data_root"):
+        raise ValueError("--segment: `data_root` is required")
+    dist_setup()
+    root = args.project or os.path.join("logs", time.strftime("%Y-%m-%dT%H-%M-%S") + "_segment")
+    Model, Iterator = get_obj_from_str(cfg["model"]), get_obj_from_str(cfg["iterator"])
+    model = Model(cfg)
+    it = Iterator(cfg, root, model)
+    it.initialize(args.checkpoint)
+    if args.checkpoint is None:
+        LOG.warning("--segment without -c: the part maps of freshly initialised weights")
+    rows = segment_files(model, cfg, root, it.global_step)
+    odir = os.path.join(root, "segment", str(it.global_step))
+    print("[INFO] {} images segmented into {}".format(len(rows), odir))
+    return {"rows": rows, "root": root, "dir": odir, "model": model}
 
 
 if __name__ == "__main__":
