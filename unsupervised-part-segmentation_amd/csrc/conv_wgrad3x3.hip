@@ -12,6 +12,8 @@
 // fragments the channel-slice-0 waves already hold.
 #include <stdlib.h>
 
+#include <type_traits>
+
 #include "common.h"
 
 namespace {
@@ -39,6 +41,7 @@ __device__ inline int g_w(unsigned long long wi, int t) { return (int)((wi >> (4
 constexpr int lds_stride3(int row_bytes) { return ((row_bytes + 63) / 128) * 128 + 64; }
 
 typedef __attribute__((address_space(3))) s16x4 lds3_s16x4;
+typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
 
 // element j of lane l = M[row0 + 8*(l>>5) + j][c0 + (l&31)] of a row-major LDS tile (row stride rs bytes)
 __device__ inline bf16x8 tr_frag3(const unsigned char* tile, int rs, int row0, int c0, int lane) {
@@ -70,6 +73,24 @@ __device__ inline bf16x8 tr_frag_d(const unsigned char* tile, int row0, int wco,
     const unsigned char* a0 = tile + row * RS + ((wco ^ d_swz<BN>(row)) << 6) + 32 * (g & 1) + 8 * pp;
     s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds3_s16x4*)a0);
     s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds3_s16x4*)(a0 + 4 * RS));     // d_swz(row + 4) == d_swz(row)
+    union { s16x4 s[2]; bf16x8 b; } u;
+    u.s[0] = lo; u.s[1] = hi;
+    return u.b;
+}
+
+// the same two fragments from a pointer that already holds the lane's part of the address (the pipelined loop forms it once per
+// unit; the window is then an immediate offset): X fragment at patch pixel row0, dout fragment at tile pixel row0 (multiple of 16)
+__device__ inline unsigned tr_lane_x(int rs, int c0, int lane) {
+    const int g = lane >> 4, i = lane & 15, h = g >> 1;
+    return (unsigned)((8 * h + (i >> 2)) * rs + (c0 + 16 * (g & 1) + 4 * (i & 3)) * 2);
+}
+template <int BN> __device__ inline unsigned tr_lane_d(int wco, int lane) {
+    const int g = lane >> 4, i = lane & 15, h = g >> 1, q = i >> 2, pp = i & 3;
+    return (unsigned)((8 * h + q) * (BN * 2) + ((wco ^ d_swz<BN>(q)) << 6) + 32 * (g & 1) + 8 * pp);     // d_swz(16 r + 8 h + q) == d_swz(q)
+}
+__device__ inline bf16x8 tr_frag_at(const unsigned char* a0, int rs) {
+    s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds3_s16x4*)a0);
+    s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds3_s16x4*)(a0 + 4 * rs));
     union { s16x4 s[2]; bf16x8 b; } u;
     u.s[0] = lo; u.s[1] = hi;
     return u.b;
@@ -128,9 +149,19 @@ __global__ __launch_bounds__(512) void conv_wgrad3x3_kernel(const Wg3K p, const 
         if (tid + 512 * k >= PPIX * CPX || ci0 + cc * 8 >= p.ci) fl |= 16u;
         xr[k] = (unsigned)(py * p.w + px);
         xs[k] = (unsigned)(pix * RSX + cc * 16) | (fl << 16);
+        if constexpr (WK == 1 && SLIDE) {
+            // pipelined loop: the lanes past the item count store too (zeros; no predicated store, so no branch in the row
+            // loop), each into a 16-byte slot of its own in the row padding [CB * 2, RSX) that no fragment read touches
+            static_assert(RSX >= CB * 2 + 64 && (512 * NX - PPIX * CPX + 3) / 4 <= PPIX, "dump slots in the row padding");
+            const int past = tid + 512 * k - PPIX * CPX;
+            if (past >= 0) xs[k] = (unsigned)((past >> 2) * RSX + CB * 2 + (past & 3) * 16) | (fl << 16);
+        }
     }
     const unsigned x_rowb = (unsigned)p.ldi * 2u;                     // bytes per pixel of the input
     const unsigned x_chb = (unsigned)(ci0 + (tid % CPX) * 8) * 2u;    // 512 % CPX == 0: one chunk column per thread
+    unsigned xo[NX];                                                  // pipelined loop: an item's byte offset from the patch origin
+#pragma unroll
+    for (int k = 0; k < NX; ++k) xo[k] = __umul24(xr[k], x_rowb) + x_chb;
     // dout tile by LDS-DMA (global_load_lds_dwordx4: no VGPRs, no ds_write): wave-instruction j = wid + 8 q fills the LDS
     // slots j*64 + lane (16 B each) of the unpadded tile; slot (row, s) receives chunk s ^ (d_swz(row) << 2) (source-side
     // swizzle).  dd[q] = the lane's byte offset from the unit's first dout pixel.
@@ -145,7 +176,10 @@ __global__ __launch_bounds__(512) void conv_wgrad3x3_kernel(const Wg3K p, const 
     const unsigned smem_lds = (unsigned)(unsigned long long)(__attribute__((address_space(3))) unsigned char*)smem;
 
     uint4 rx[NX];
-    uint4 rxn[NX];            // pipelined SLIDE variant: the X items of the unit after next
+    // pipelined SLIDE variant: the X items of the unit after next.  One 128-bit register operand each, for the load and for the
+    // counted wait alike: with the words as twelve separate operands of the wait the compiler has placed register moves between
+    // a load and its wait (they copy what the load has not written yet; tools/check_listing.py, rule asm-loads)
+    u32x4 rxn[NX];
     bool rxok[NX];
     const uint4 zero4 = make_uint4(0u, 0u, 0u, 0u);
 
@@ -157,37 +191,78 @@ __global__ __launch_bounds__(512) void conv_wgrad3x3_kernel(const Wg3K p, const 
         img = t / p.tiles_y;
         y0 = ty * 16 + half * TH; x0 = tx * TW;
     };
-    // X loads of unit u into registers, UNCONDITIONALLY (lanes whose item lies outside the image read the tensor's first bytes and
-    // drop them): the number of vector-memory operations per wave is then static, and a counted s_waitcnt can leave exactly
-    // these loads in flight across a barrier (pipelined SLIDE variant below)
-    auto load_x = [&](int u) __attribute__((always_inline)) {
-        int img, y0, x0;
-        unit_origin(u, img, y0, x0);
-        const unsigned edge = (y0 == 0 ? 1u : 0u) | (y0 + TH == p.h ? 2u : 0u) | (x0 == 0 ? 4u : 0u) | (x0 + TW == p.w ? 8u : 0u) | 16u;
-        const long long org = ((long long)img * p.h + (y0 - 1)) * p.w + (x0 - 1);
-        const unsigned char* xb = (const unsigned char*)(in + org * p.ldi);
-#pragma unroll
-        for (int k = 0; k < NX; ++k) {
-            unsigned r = xr[k], f = xs[k];
-            asm volatile("" : "+v"(r), "+v"(f));
-            const bool ok = ((f >> 16) & edge) == 0u;
-            const unsigned char* src = ok ? xb + (__umul24(r, x_rowb) + x_chb) : (const unsigned char*)in;
-            uint4 v;
-            asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(v) : "v"(src) : "memory");
-            rxn[k] = v;
-            rxok[k] = ok;
-        }
+    // ---- unit walker of the pipelined loop.  A block walks consecutive units, so a unit's origin follows from the one before
+    // it by add / compare / select on scalars; unit_origin()'s divisions run once, for u_begin.  Unit order: the two 8-row
+    // halves of a tile, the tiles of a tile row, the tile rows of an image, the images; pixel (h, x) of image i is pixel (0, x) of
+    // image i + 1, so the image boundary needs no step of its own.  xo / dq: byte offset of the X patch origin (one row and one
+    // pixel before the unit: may lie before the tensor) / of the unit's first dout pixel.  A step past u_end - 1 stays where it
+    // is: the loop stages "the next unit" unconditionally, and a block's last units re-stage its last unit into the buffers
+    // nobody reads any more.  All step sizes fit 32 bits (eligible(): 19 * w * ldi * 2 and 17 * w * ldo * 2 < 2^31).
+    struct Walk3 { int half, tx, ty, idx; unsigned edge; long long xo, dq; };   // edge: the unit's border flags, as in xs[]
+    struct WalkStep { int go, right, wrap, pix; };
+    const int d_rowb = p.ldo * 2;
+    // (integer arithmetic on 0 / 1 flags throughout: the walker stays on the scalar unit)
+    auto walk_edge = [&](const Walk3& W) {
+        return ((W.ty | W.half) == 0 ? 1u : 0u) | (((W.ty - (p.tiles_y - 1)) | (W.half ^ 1)) == 0 ? 2u : 0u) |
+               (W.tx == 0 ? 4u : 0u) | (W.tx == p.tiles_x - 1 ? 8u : 0u) | 16u;
     };
-    auto dma_d = [&](int u, int buf) __attribute__((always_inline)) {
+    auto walk_init = [&](int u) {
         int img, y0, x0;
         unit_origin(u, img, y0, x0);
-        const unsigned char* db = (const unsigned char*)(dout + (((long long)img * p.h + y0) * p.w + x0) * p.ldo);
-#pragma unroll
-        for (int q = 0; q < NWD; ++q) {
-            const unsigned lds_dst = __builtin_amdgcn_readfirstlane(smem_lds + (unsigned)(2 * XB + buf * DB + (wid + 8 * q) * 1024));
-            asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2"
-                         :: "s"(lds_dst), "v"(dd[q]), "s"(db) : "memory", "m0");
-        }
+        Walk3 W;
+        W.half = u & 1; W.tx = x0 / TW; W.ty = y0 / 16; W.idx = u;
+        W.edge = walk_edge(W);
+        W.xo = (((long long)img * p.h + (y0 - 1)) * p.w + (x0 - 1)) * (long long)x_rowb;
+        W.dq = (((long long)img * p.h + y0) * p.w + x0) * (long long)d_rowb;
+        return W;
+    };
+    // a step in three pieces (the loop gives each an MFMA gap of its own): which way, the two offsets, the position
+    auto walk_dir = [&](const Walk3& W, WalkStep& S) __attribute__((always_inline)) {
+        S.go = __builtin_amdgcn_readfirstlane(W.idx + 1 < u_end ? 1 : 0);
+        const int down = S.go & (W.half ^ 1);                 // upper half -> lower half of the same tile
+        S.right = S.go & W.half;                              // lower half -> upper half of the next tile
+        S.wrap = W.tx + 1 == p.tiles_x ? S.right : 0;         // ... which starts the next tile row (pixel (y, w) = (y + 1, 0))
+        S.pix = __builtin_amdgcn_readfirstlane((down - S.right) * 8 * p.w + S.right * TW + S.wrap * 15 * p.w);
+    };
+    auto walk_off = [&](Walk3& W, const WalkStep& S) __attribute__((always_inline)) {
+        W.xo += (long long)(S.pix * (int)x_rowb);
+        W.dq += (long long)(S.pix * d_rowb);
+    };
+    auto walk_pos = [&](Walk3& W, const WalkStep& S) __attribute__((always_inline)) {
+        W.idx += S.go;
+        W.half ^= S.go;
+        W.ty = S.wrap ? (W.ty + 1 == p.tiles_y ? 0 : W.ty + 1) : W.ty;
+        W.tx = S.wrap ? 0 : W.tx + S.right;
+    };
+    auto walk_step = [&](Walk3& W) __attribute__((always_inline)) {
+        WalkStep S;
+        walk_dir(W, S); walk_off(W, S); walk_pos(W, S);
+        W.edge = walk_edge(W);
+    };
+    // X load of item k of the unit at W into registers, UNCONDITIONALLY (lanes whose item lies outside the image read the tensor's
+    // first bytes and drop them): the number of vector-memory operations per wave is then static, and a counted s_waitcnt can
+    // leave exactly these loads in flight across a barrier (pipelined SLIDE variant below)
+    auto load_x1 = [&](const Walk3& W, int k) __attribute__((always_inline)) {
+        const unsigned char* xb = (const unsigned char*)in + W.xo;
+        unsigned r = xo[k], f = xs[k];
+        asm volatile("" : "+v"(r), "+v"(f));
+        const bool ok = ((f >> 16) & W.edge) == 0u;
+        unsigned long long a = (unsigned long long)(xb + r);
+        asm volatile("" : "+v"(a));                           // the address is formed for every lane: a select, not a branch
+        const unsigned char* src = ok ? (const unsigned char*)a : (const unsigned char*)in;
+        asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(rxn[k]) : "v"(src) : "memory");
+        rxok[k] = ok;
+    };
+    // dout DMA piece q of the unit at W into D buffer `buf`.  Piece q covers the tile rows 2q, 2q + 1 at the lane offsets of piece 0
+    // (L = (wid + 8 q) * 64 + lane: tile row (wid >> 2) + 2 q, pixel and swizzle independent of q), so dd[0] serves all four and
+    // the row pair goes into the scalar base
+    static_assert(!(WK == 1 && SLIDE) || (CPD == 16 && NWD == 4), "DMA piece q = piece 0 moved down 2 q rows");
+    const int d_pair = 2 * p.w * d_rowb;
+    auto dma_d1 = [&](const Walk3& W, int buf, int q) __attribute__((always_inline)) {
+        const unsigned char* db = (const unsigned char*)dout + (W.dq + (long long)(q * d_pair));
+        const unsigned lds_dst = __builtin_amdgcn_readfirstlane(smem_lds + (unsigned)(2 * XB + buf * DB + (wid + 8 * q) * 1024));
+        asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2"
+                     :: "s"(lds_dst), "v"(dd[0]), "s"(db) : "memory", "m0");
     };
     auto store_xn = [&](int buf) __attribute__((always_inline)) {
         unsigned char* X = Xbuf + buf * XB;
@@ -195,7 +270,7 @@ __global__ __launch_bounds__(512) void conv_wgrad3x3_kernel(const Wg3K p, const 
         for (int k = 0; k < NX; ++k) {
             unsigned f = xs[k];
             asm volatile("" : "+v"(f));
-            uint4 v = rxok[k] ? rxn[k] : zero4;
+            uint4 v = rxok[k] ? make_uint4(rxn[k][0], rxn[k][1], rxn[k][2], rxn[k][3]) : zero4;
             if (p.in_f16) v = ups_act_chunk_f16_to_bf16(v, act_ns, p.act_in != UPS_ACT_NONE);
             else if (p.act_in != UPS_ACT_NONE) v = ups_act_chunk(v, act_ns, (bf16*)nullptr);
             if (k + 1 < NX || tid + 512 * k < PPIX * CPX) *(uint4*)(X + (f & 0xffffu)) = v;
@@ -256,73 +331,157 @@ __global__ __launch_bounds__(512) void conv_wgrad3x3_kernel(const Wg3K p, const 
 
     if constexpr (WK == 1 && SLIDE) {
       if (!p.mask) {
-        // Software-pipelined staging: the X items of unit u+1 are converted and written to LDS in the MIDDLE of unit u's MFMAs
-        // (they were requested during unit u-1), the loads of unit u+2 are issued right behind and stay in flight across the
-        // barrier (counted wait: only the dout DMA of unit u+1, issued first, has to have landed).  One block per CU runs its
-        // eight waves in lock-step between barriers, so a load -> wait -> convert -> ds_write phase at the end of every unit
-        // left the matrix pipe idle for its whole length.
-        static_assert(NX == 3 && (NWD == 4 || NWD == 2 || NWD == 1), "pipelined staging: item / DMA piece counts");
-#define UPS_WAIT_X(N) asm volatile("s_waitcnt vmcnt(" #N ")" : "+v"(rxn[0].x), "+v"(rxn[0].y), "+v"(rxn[0].z), "+v"(rxn[0].w), \
-                                   "+v"(rxn[1].x), "+v"(rxn[1].y), "+v"(rxn[1].z), "+v"(rxn[1].w), "+v"(rxn[2].x), "+v"(rxn[2].y), \
-                                   "+v"(rxn[2].z), "+v"(rxn[2].w) :: "memory")
+        // Software-pipelined staging.  One block per CU runs its eight waves in lock-step between barriers, so whatever a unit
+        // does outside its MFMAs leaves the matrix pipe idle for its whole length: ALL staging of the following units sits in
+        // the gaps behind the MFMAs of unit u's rows, a few instructions per gap, in the order of the table below (explicit
+        // placement: a scheduling barrier on both sides of every MFMA).  The unit loop has no branch but its own: the bias
+        // sum, the input format and the activation pick one of eight copies of the loop, once; "the next unit" is staged
+        // unconditionally (Walk3: the walkers stop at the block's last unit).
+        //   row 0, gaps 0 1       this unit's fragment reads of patch rows 1 / 2 (+ the dout fragment of row 1)
+        //   row 0, gaps 0 2 4 6   dout DMA pieces 0..3 of unit u+1 -> Dbuf[buf^1]
+        //   row 1 + k (k = 0..2)  gap 0 (k = 0 only): counted wait for the X items of unit u+1
+        //                         gaps 0..3: item k, one 32-bit word per gap: select, convert, activation; gap 3: ds_write_b128
+        //                         -> Xbuf[buf^1];   gap 4: X load of item k of unit u+2 into the registers just freed
+        //   row 4 / 5, gaps 0..2  step the u+1 / u+2 walker (gap 3 of row 5: the border flags of unit u+3's X loads)
+        //   every row, gaps 5..8  bias sum of the row's dout fragment (the copies of the channel-slice-0 waves only)
+        // LDS hazards: Xbuf[buf^1] and Dbuf[buf^1] were last read by unit u-1, whose closing barrier every wave has passed
+        // before row 0; the X stores are complete (lgkmcnt(0)) and the DMA has landed (vmcnt(3)) before the barrier closing u.
+        // Vector-memory issue order per wave and unit: D(u+1) x 4, then X(u+2) x 3; X(u+1) x 3 are older than both.
+        static_assert(TH == 8 && NX == 3 && NWD == 4, "pipelined staging: unit height, item / DMA piece counts");
+#define UPS_WAIT_X(N) asm volatile("s_waitcnt vmcnt(" #N ")" : "+v"(rxn[0]), "+v"(rxn[1]), "+v"(rxn[2]) :: "memory")
         if (u_begin < u_end) {
-            load_x(u_begin); dma_d(u_begin, 0);
+            Walk3 W1 = walk_init(u_begin);
+#pragma unroll
+            for (int k = 0; k < NX; ++k) load_x1(W1, k);
+#pragma unroll
+            for (int q = 0; q < NWD; ++q) dma_d1(W1, 0, q);
             UPS_WAIT_X(0);
             store_xn(0);
-            if (u_begin + 1 < u_end) load_x(u_begin + 1);
-        }
-        UPS_WAIT_X(0);
-        __syncthreads();
-        for (int u = u_begin; u < u_end; ++u) {
-            const int buf = (u - u_begin) & 1;
-            if (u + 1 < u_end) dma_d(u + 1, buf ^ 1);
-            const unsigned char* X = Xbuf + buf * XB;
-            const unsigned char* D = Dbuf + buf * DB;
-            bf16x8 aw[3][3];
+            walk_step(W1);                                    // u_begin + 1 (or u_begin again: a one-unit block)
 #pragma unroll
-            for (int dxi = 0; dxi < 3; ++dxi) {
-                aw[0][dxi] = tr_frag3(X, RSX, dxi, w_ci * 32, lane);
-                aw[1][dxi] = tr_frag3(X, RSX, PWID + dxi, w_ci * 32, lane);
-            }
-            bf16x8 bcur = tr_frag_d<BN>(D, 0, w_co, lane);
-#pragma unroll
-            for (int ks = 0; ks < TH; ++ks) {
-                if (ks == TH / 2) {
-                    if (u + 1 < u_end) {
-                        // the X items of unit u+1 (requested half a unit ago or earlier) are older than this unit's NWD dout DMA
-                        // pieces; the registers are operands of the wait so that no use of them is scheduled above it (the
-                        // loads are inline asm: the compiler's own wait-count bookkeeping does not see them)
-                        if (NWD == 4) UPS_WAIT_X(4); else if (NWD == 2) UPS_WAIT_X(2); else UPS_WAIT_X(1);
-                        store_xn(buf ^ 1);
+            for (int k = 0; k < NX; ++k) load_x1(W1, k);
+            Walk3 W2 = W1;
+            walk_step(W2);
+            UPS_WAIT_X(0);
+            __syncthreads();
+
+            unsigned x_lane = tr_lane_x(RSX, w_ci * 32, lane), d_lane = tr_lane_d<BN>(w_co, lane);
+            asm volatile("" : "+v"(x_lane), "+v"(d_lane));     // one register each: no per-window copies hoisted out of the loop
+            auto run = [&](auto mode_c, auto bias_c) __attribute__((always_inline)) {
+                constexpr int MODE = decltype(mode_c)::value;          // bit 0: activation on load, bit 1: fp16 input
+                constexpr bool BIAS = decltype(bias_c)::value;
+                // one 32-bit word (two channels) of a staged item: what ups_act_chunk / ups_act_chunk_f16_to_bf16 do to it
+                auto cvt_word = [&](unsigned w) __attribute__((always_inline)) -> unsigned {
+                    if constexpr (MODE == 0) return w;
+                    else if constexpr (MODE == 1) {
+                        ups_f32x2 x = {__uint_as_float(w << 16), __uint_as_float(w & 0xffff0000u)};
+                        const ups_f32x2 sx = x * act_ns;
+                        const float lo = ups_vmax(x[0], sx[0]), hi = ups_vmax(x[1], sx[1]);
+                        unsigned o;
+                        asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(o) : "v"(lo), "v"(hi));
+                        return o;
+                    } else {
+                        float lo, hi;
+                        ups_unpack2<f16>(w, lo, hi);
+                        if constexpr (MODE == 3) { lo = ups_vmax(lo, act_ns * lo); hi = ups_vmax(hi, act_ns * hi); }
+                        return Chunk<bf16>::pk(lo, hi);
                     }
-                    if (u + 2 < u_end) load_x(u + 2);
-                    __builtin_amdgcn_sched_barrier(0);
+                };
+                for (int u = u_begin; u < u_end; ++u) {
+                    const int buf = (u - u_begin) & 1;
+                    const unsigned char* X = Xbuf + buf * XB + x_lane;      // (+ the lane's part of every fragment address)
+                    const unsigned char* D = Dbuf + buf * DB + d_lane;
+                    unsigned char* Xn = Xbuf + (buf ^ 1) * XB;
+                    // before the first MFMA only what it needs: the dout fragment of row 0 and patch row 0.  Patch rows 1 and 2
+                    // and the dout fragment of row 1 are requested behind row 0's first two MFMAs (three and six MFMAs ahead of
+                    // their first use)
+                    bf16x8 aw[3][3];
+                    bf16x8 bcur = tr_frag_at(D, RSD);
+#pragma unroll
+                    for (int dxi = 0; dxi < 3; ++dxi) aw[0][dxi] = tr_frag_at(X + dxi * RSX, RSX);
+                    WalkStep S1, S2;
+#pragma unroll
+                    for (int ks = 0; ks < TH; ++ks) {
+                        // the dout fragment of the NEXT row is requested a row ahead, into a register pair of its own
+                        bf16x8 bnext = bcur;
+                        if (ks > 0) {
+#pragma unroll
+                            for (int dxi = 0; dxi < 3; ++dxi) aw[(ks + 2) % 3][dxi] = tr_frag_at(X + ((ks + 2) * PWID + dxi) * RSX, RSX);
+                            if (ks + 1 < TH) bnext = tr_frag_at(D + (ks + 1) * TW * RSD, RSD);
+                        }
+                        const bf16x8 b = bcur;
+                        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                        for (int t = 0; t < 9; ++t) {
+                            acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(aw[(ks + t / 3) % 3][t % 3], b, acc[t], 0, 0, 0);
+                            __builtin_amdgcn_sched_barrier(0);
+                            if (ks == 0 && t == 0) {
+#pragma unroll
+                                for (int dxi = 0; dxi < 3; ++dxi) aw[1][dxi] = tr_frag_at(X + (PWID + dxi) * RSX, RSX);
+                            }
+                            if (ks == 0 && t == 1) {
+#pragma unroll
+                                for (int dxi = 0; dxi < 3; ++dxi) aw[2][dxi] = tr_frag_at(X + (2 * PWID + dxi) * RSX, RSX);
+                                bnext = tr_frag_at(D + TW * RSD, RSD);
+                            }
+                            if (ks == 0 && (t & 1) == 0 && t < 8) dma_d1(W1, buf ^ 1, t >> 1);
+                            if (ks >= 1 && ks <= 3) {
+                                const int k = ks - 1;
+                                if (t < 4) {
+                                    // vmcnt(4): the X items of unit u+1 (requested a unit ago) are older than the four DMA pieces of
+                                    // row 0, the only younger operations in flight.  The registers are operands of the wait so that
+                                    // no use of them is scheduled above it (the loads are inline asm: the compiler's own wait-count
+                                    // bookkeeping does not see them)
+                                    if (k == 0 && t == 0) UPS_WAIT_X(4);
+                                    // (converted in place: the item's registers are free until its reload in gap 4)
+                                    rxn[k][t] = cvt_word(rxok[k] ? rxn[k][t] : 0u);
+                                }
+                                if (t == 3) {
+                                    unsigned f = xs[k];
+                                    asm volatile("" : "+v"(f));
+                                    *(u32x4*)(Xn + (f & 0xffffu)) = rxn[k];
+                                }
+                                if (t == 4) load_x1(W2, k);
+                            }
+                            if (ks == 4 && t == 0) walk_dir(W1, S1);
+                            if (ks == 4 && t == 1) walk_off(W1, S1);
+                            if (ks == 4 && t == 2) walk_pos(W1, S1);
+                            if (ks == 5 && t == 0) walk_dir(W2, S2);
+                            if (ks == 5 && t == 1) walk_off(W2, S2);
+                            if (ks == 5 && t == 2) walk_pos(W2, S2);
+                            if (ks == 5 && t == 3) W2.edge = walk_edge(W2);
+                            if constexpr (BIAS) {
+                                // (same order of additions as ever: rows in order, j = 0..7 within a row)
+                                if (t >= 5) { bsum += (float)b[2 * (t - 5)]; bsum += (float)b[2 * (t - 5) + 1]; }
+                            }
+                            __builtin_amdgcn_sched_barrier(0);
+                        }
+                        bcur = bnext;
+                    }
+                    // vmcnt(3): the four DMA pieces of unit u+1 (row 0) are older than the three X loads of unit u+2 (rows 1..3),
+                    // which stay in flight across the barrier; nothing else was issued since
+                    asm volatile("s_waitcnt vmcnt(3)" ::: "memory");
+                    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+                    __builtin_amdgcn_s_barrier();
                 }
-#pragma unroll
-                for (int dxi = 0; dxi < 3; ++dxi) aw[(ks + 2) % 3][dxi] = tr_frag3(X, RSX, (ks + 2) * PWID + dxi, w_ci * 32, lane);
-                // the dout fragment of the NEXT row is requested now: all nine MFMAs of a row wait for theirs
-                const bf16x8 bnext = tr_frag_d<BN>(D, (ks + 1 < TH ? ks + 1 : ks) * TW, w_co, lane);
-                const bf16x8 b = bcur;
-#pragma unroll
-                for (int t = 0; t < 9; ++t)
-                    acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(aw[(ks + t / 3) % 3][t % 3], b, acc[t], 0, 0, 0);
-                if (do_bias) {
-#pragma unroll
-                    for (int j = 0; j < 8; ++j) bsum += (float)b[j];
-                }
-                bcur = bnext;
-                __builtin_amdgcn_sched_barrier(0);
+            };
+            // (readfirstlane: the choice is wave-uniform by construction; the copies are then alternatives of a scalar branch,
+            // and nothing one copy needs stays live through another)
+            const int sel = __builtin_amdgcn_readfirstlane((p.act_in != UPS_ACT_NONE ? 1 : 0) | (p.in_f16 ? 2 : 0) | (do_bias ? 4 : 0));
+            switch (sel) {
+                case 0: run(std::integral_constant<int, 0>{}, std::false_type{}); break;
+                case 1: run(std::integral_constant<int, 1>{}, std::false_type{}); break;
+                case 2: run(std::integral_constant<int, 2>{}, std::false_type{}); break;
+                case 3: run(std::integral_constant<int, 3>{}, std::false_type{}); break;
+                case 4: run(std::integral_constant<int, 0>{}, std::true_type{}); break;
+                case 5: run(std::integral_constant<int, 1>{}, std::true_type{}); break;
+                case 6: run(std::integral_constant<int, 2>{}, std::true_type{}); break;
+                default: run(std::integral_constant<int, 3>{}, std::true_type{}); break;
             }
-            // the dout DMA of unit u+1 (older than the NX loads of unit u+2) must have landed; those loads stay in flight
-            if (u + 2 < u_end) {
-                if (NX == 3) asm volatile("s_waitcnt vmcnt(3)" ::: "memory");
-                else asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
-            } else {
-                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            }
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            __builtin_amdgcn_s_barrier();
+            // the redundant loads and DMA pieces of the last units: nothing of this block is in flight past this point
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         }
+#undef UPS_WAIT_X
         goto reduce_parts;
       }
     }

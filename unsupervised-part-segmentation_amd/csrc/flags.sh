@@ -21,7 +21,7 @@ ups_quiet() { "$@" 2> >(grep -v "is not a recognized feature for this target" >&
 # listing gates (tools/check_listing.py <rules> <listing>): which rules a file's device listing must pass before the library is linked
 ups_file_gates() {
   case "$1" in
-    conv3x3_rows) echo "no-packed-fp32 asm-loads" ;;
+    conv3x3_rows|conv_wgrad3x3) echo "no-packed-fp32 asm-loads" ;;   # (files whose inline-asm register loads have counted waits)
     *) case " $UPS_NOPK_FILES " in *" $1 "*) echo "no-packed-fp32" ;; esac ;;
   esac
 }
