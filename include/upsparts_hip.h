@@ -578,6 +578,39 @@ int ups_segment_render(const float* soft, int32_t n, int32_t S, int32_t P, const
                        int64_t total, const uint8_t* src, const uint8_t* colors, double alpha, uint8_t* labels, uint8_t* overlay,
                        uint8_t* confidence, int32_t* counts, void* stream);
 
+/* ---------------------------------------------------------------- part-appearance index (csrc/partindex.hip)
+ * Nearest neighbours and k-means on a bank of per-part appearance codes (TrainModel.encode_parts): what deepfashion/code/eval/eval_02's
+ * make_clusters does off-line with scikit-learn.  Restated in NumPy float64 by tests/partindex_ref.py with equal bits.
+ *   bank      feat [N, P, A] fp32, finite (no alignment beyond the element's is assumed); valid [N, P] uint8: an entry with valid == 0
+ *             (an absent part: it has a code, but no meaning) is never a query, a neighbour or a cluster member
+ *   distance  d(x, y) = sum_{a = 0 .. A-1} (double(x_a) - double(y_a))^2: fp64, accumulated in ascending a from 0.0, every
+ *             subtraction, multiplication and addition rounded once (no contraction), so a loop over a in NumPy gives the same bits.
+ *             There is NO matrix-core form |x|^2 + |y|^2 - 2 x.y: it is not bit-equal to any restatement and it cancels for close
+ *             codes.  No distance matrix is written.
+ * ups_part_knn: for a valid query (q, p) the K items g with gvalid[g, p] (and g != q when exclude_same_index) that are smallest in
+ *   the total order (d, g) -- distance, then gallery index -- in that order: idx [Nq, P, K] int32, dist [Nq, P, K] double.  Slots
+ *   beyond the number of eligible items, and every slot of an invalid query, are -1 / +inf.  Both outputs are written completely.
+ * ups_part_kmeans_step: cent [P, k, A] double.  label [N, P] int32 = the FIRST j with minimal d(feat[n, p], cent[p, j]), -1 where
+ *   invalid; mind [N, P] double = that distance, +inf where invalid (both written completely).  prev_label [N, P] or NULL: changed [1]
+ *   int32 (required with prev_label) += #{label != prev_label}.  counts [P, k] int32 += the members (integer atomics: caller-zeroed),
+ *   sums [P, k, A] double = the members' codes, converted to double and added, inertia [P] double = sum of mind over the valid items
+ *   (both written).  Floating-point sums use no atomics: one partial per block of ups_part_kmeans_chunk() items (members in index
+ *   order) in `scratch` (ups_part_kmeans_scratch_bytes, overwritten before it is read), added in block order by a second launch:
+ *   two calls give the same bits.  counts, sums and inertia may be NULL together (assignment only; scratch may then be NULL too).
+ *   The new centroid, sums / counts in fp64 with an empty cluster keeping its own, is the caller's.
+ * ups_part_knn_tile(): queries per block = gallery items per staged tile;  ups_part_kmeans_chunk(): items per block.
+ * UPS_E_UNSUPPORTED: K > 32, k > 64, A > 512.  UPS_E_ARG, nothing launched: a NULL required pointer, Nq, Ng, N, P, A, K or k < 1,
+ * Nq P A, Ng P A, Nq P K, N P A, P k A or the scratch index past 2^31 - 1, counts / sums / inertia given only in part, sums without
+ * scratch, prev_label without changed.  ups_part_kmeans_scratch_bytes returns 0 for sizes the step refuses. */
+int32_t ups_part_knn_tile(void);
+int32_t ups_part_kmeans_chunk(void);
+int ups_part_knn(const float* q, const uint8_t* qvalid, int32_t Nq, const float* g, const uint8_t* gvalid, int32_t Ng, int32_t P,
+                 int32_t A, int32_t K, int32_t exclude_same_index, int32_t* idx, double* dist, void* stream);
+size_t ups_part_kmeans_scratch_bytes(int32_t N, int32_t P, int32_t A, int32_t k);
+int ups_part_kmeans_step(const float* feat, const uint8_t* valid, int32_t N, int32_t P, int32_t A, const double* cent, int32_t k,
+                         const int32_t* prev_label, int32_t* label, double* mind, int32_t* counts, double* sums, double* inertia,
+                         int32_t* changed, void* scratch, void* stream);
+
 /* ---------------------------------------------------------------- mask priors (M:652-797), fused
  * One pass over l/m per view producing the partial sums, one fused backward producing dl.
  * See csrc/priors.hip for the slot layout of `sums`. */

@@ -164,6 +164,11 @@ _SIGS = {
     "ups_segment_chunk": ([], _I),
     "ups_segment_table_words": ([], _I),
     "ups_segment_render": ([_P, _I, _I, _I, C.POINTER(_I), _P, _L, _P, _P, C.c_double, _P, _P, _P, _P, _P], C.c_int),
+    "ups_part_knn_tile": ([], _I),
+    "ups_part_kmeans_chunk": ([], _I),
+    "ups_part_knn": ([_P, _P, _I, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P], C.c_int),
+    "ups_part_kmeans_scratch_bytes": ([_I, _I, _I, _I], _Z),
+    "ups_part_kmeans_step": ([_P, _P, _I, _I, _I, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P], C.c_int),
     "ups_prior_sums_floats": ([_I, _I], _Z),
     "ups_prior_fwd": ([C.POINTER(PriorDesc), _P], C.c_int),
     "ups_prior_bwd": ([C.POINTER(PriorDesc), _P], C.c_int),

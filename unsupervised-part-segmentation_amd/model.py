@@ -282,6 +282,34 @@ class TrainModel(object):
         return self._encode((views, False), (views, True))[1]["feat"]
 
     @torch.no_grad()
+    def encode_parts(self, views):
+        """views [n,S,S,3] -> {"feat" [n,P,A] fp32 (one appearance code per image and part, as ``encode_appearance``), "area" [n,P]
+        int32 (the pixels of ``out_parts_hard`` equal to p: ``ops.part_usage``'s counts), "out_parts_hard" int64 [n,S,S]} on the
+        device: the bank of ``partindex.PartIndex``.  Passes of 2 * batch_size images, ONE ``_encode((v[:B], True), (v[B:], True))``
+        each -- the batch ``forward`` gives the pose path, so the convolutions plan alike, and the pose path is paid once, not twice
+        as in ``encode_appearance``.  A shorter last pass is padded with copies of its first image, as in ``segment``, and the
+        padding is dropped.  Test-mode semantics.  Under precision: fp8 a pass records activation maxima like any forward."""
+        B, P = int(self.config["batch_size"]), self.n_parts
+        views = torch.as_tensor(views)
+        n, S = views.shape[0], views.shape[1]
+        feat = torch.empty((n, P, int(self.config.get("local_app_size", 64))), dtype=torch.float32, device=self.device)
+        area = torch.zeros((n, P), dtype=torch.int32, device=self.device)
+        hard = torch.empty((n, S, S), dtype=torch.int64, device=self.device)
+        for c0 in range(0, n, 2 * B):
+            v = views[c0:c0 + 2 * B].to(self.device, torch.float32)
+            k = v.shape[0]
+            if k < 2 * B:
+                v = torch.cat([v, v[:1].expand(2 * B - k, S, S, v.shape[3])], 0)
+            for o, g in zip((0, B), self._encode((v[:B], True), (v[B:], True))):
+                m = min(k - o, B)
+                if m > 0:
+                    feat[c0 + o:c0 + o + m] = g["feat"][:m]
+                    hard[c0 + o:c0 + o + m] = g["out_parts_hard"][:m]
+                    ops.part_usage(g["out_parts_soft"][:m].contiguous(), g["out_parts_hard"][:m].contiguous(),
+                                   counts=area[c0 + o:c0 + o + m])
+        return {"feat": feat, "area": area, "out_parts_hard": hard}
+
+    @torch.no_grad()
     def decode_mixed(self, hard, feat, pose_idx, app_idx, chunk=None):
         """generated [K,S,S,3] fp32: image k has the masks hard[pose_idx[k]] and, for part p, the appearance feat[app_idx[k][p]][p].
         pose_idx [K], app_idx [K,P]: host integers.  Decoded in chunks of at most `chunk` images (default: the config's batch_size;

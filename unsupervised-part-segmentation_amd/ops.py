@@ -1899,6 +1899,71 @@ def part_usage(soft, pred, counts=None, invalid=None, sharp=None):
     return counts, invalid, sharp
 
 
+# --------------------------------------------------------------------------- part-appearance index (csrc/partindex.hip)
+PART_KNN_MAX_K, PART_KMEANS_MAX_K = 32, 64
+
+
+def _bank(what, feat, valid):
+    if (feat.dim() != 3 or feat.dtype != torch.float32 or feat.shape[0] == 0 or valid.dtype != torch.uint8
+            or tuple(valid.shape) != tuple(feat.shape[:2])):
+        raise L.UpsError("{}: codes [N >= 1,P,A] float32 and valid [N,P] uint8 (got {} {}, {} {})".format(
+            what, tuple(feat.shape), feat.dtype, tuple(valid.shape), valid.dtype))
+    return feat.contiguous(), valid.contiguous()
+
+
+def part_knn(q, qvalid, g=None, gvalid=None, K=8, exclude_same_index=None):
+    """Per part, the K nearest valid gallery codes of every valid query code (ups_part_knn; the definitions: include/upsparts_hip.h,
+    restated by tests/partindex_ref.py with equal bits).  q [Nq,P,A] float32 and qvalid [Nq,P] uint8 on the device; g, gvalid: the
+    gallery, or None: the query bank itself with self excluded (exclude_same_index then defaults to True, else to False).
+    Returns (idx [Nq,P,K] int32, dist [Nq,P,K] float64): ascending in (distance, gallery index), padded with -1 / +inf.  fp64 direct
+    squared distances; no distance matrix is written.  Asynchronous on the current stream."""
+    if (g is None) != (gvalid is None):
+        raise L.UpsError("part_knn: g and gvalid are given together")
+    if exclude_same_index is None:
+        exclude_same_index = g is None
+    q, qvalid = _bank("part_knn", q, qvalid)
+    g, gvalid = (q, qvalid) if g is None else _bank("part_knn", g, gvalid)
+    if tuple(g.shape[1:]) != tuple(q.shape[1:]) or g.device != q.device:
+        raise L.UpsError("part_knn: query {} and gallery {} differ in [P,A] or device".format(tuple(q.shape), tuple(g.shape)))
+    Nq, P, A = q.shape
+    K = int(K)
+    idx = torch.empty((Nq, P, max(K, 0)), dtype=torch.int32, device=q.device)
+    dist = torch.empty((Nq, P, max(K, 0)), dtype=torch.float64, device=q.device)
+    L.call("ups_part_knn", L.ptr(q), L.ptr(qvalid), Nq, L.ptr(g), L.ptr(gvalid), g.shape[0], P, A, K, int(bool(exclude_same_index)),
+           L.ptr(idx), L.ptr(dist), L.stream())
+    return idx, dist
+
+
+def part_kmeans_step(feat, valid, cent, prev_label=None, accumulate=True, changed=None):
+    """One k-means step of every part on centroids cent [P,k,A] float64 (ups_part_kmeans_step).  feat [N,P,A] float32, valid [N,P]
+    uint8.  Returns a dict: "label" [N,P] int32 (first nearest centroid, -1 where invalid), "mind" [N,P] float64 (+inf where invalid),
+    "changed" [1] int32 (+= #{label != prev_label}; given or new zero) and, with accumulate, "counts" [P,k] int32, "sums" [P,k,A]
+    float64 (the members' codes added up) and "inertia" [P] float64.  accumulate=False is the assignment alone (the k-means++
+    seeding).  The scratch of the per-block partials is a fresh allocation per call (the caching allocator orders its reuse on the
+    stream); no floating-point atomics: two calls give the same bits.  Asynchronous on the current stream."""
+    feat, valid = _bank("part_kmeans_step", feat, valid)
+    N, P, A = feat.shape
+    if cent.dim() != 3 or cent.dtype != torch.float64 or cent.shape[0] != P or cent.shape[2] != A or cent.shape[1] == 0:
+        raise L.UpsError("part_kmeans_step: cent [{},k >= 1,{}] float64 expected (got {} {})".format(P, A, tuple(cent.shape), cent.dtype))
+    if prev_label is not None and (prev_label.dtype != torch.int32 or tuple(prev_label.shape) != (N, P)):
+        raise L.UpsError("part_kmeans_step: prev_label [{},{}] int32 expected".format(N, P))
+    cent = cent.contiguous()
+    k, dev = cent.shape[1], feat.device
+    out = {"label": torch.empty((N, P), dtype=torch.int32, device=dev), "mind": torch.empty((N, P), dtype=torch.float64, device=dev),
+           "changed": torch.zeros(1, dtype=torch.int32, device=dev) if changed is None else changed}
+    scratch = None
+    if accumulate:
+        out["counts"] = torch.zeros((P, k), dtype=torch.int32, device=dev)
+        out["sums"] = torch.empty((P, k, A), dtype=torch.float64, device=dev)
+        out["inertia"] = torch.empty((P,), dtype=torch.float64, device=dev)
+        nbytes = L.load().ups_part_kmeans_scratch_bytes(N, P, A, k)
+        scratch = torch.empty(max(1, nbytes // 8), dtype=torch.float64, device=dev)
+    L.call("ups_part_kmeans_step", L.ptr(feat), L.ptr(valid), N, P, A, L.ptr(cent), k,
+           L.ptr(None if prev_label is None else prev_label.contiguous()), L.ptr(out["label"]), L.ptr(out["mind"]),
+           L.ptr(out.get("counts")), L.ptr(out.get("sums")), L.ptr(out.get("inertia")), L.ptr(out["changed"]), L.ptr(scratch), L.stream())
+    return out
+
+
 # --------------------------------------------------------------------------- segmentation export (csrc/segexport.hip)
 SEGMENT_CHUNK = 1024            # pixels per block of ups_segment_render (checked against the library on first use)
 SEGMENT_ALIGN = 16              # an image's pixel offset in the packed planes is a multiple of it

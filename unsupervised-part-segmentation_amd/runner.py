@@ -19,6 +19,9 @@ MatrixHook's key set (its plotting script reads the file) and drawn by ``evaluti
 
 ``--segment <yaml> -c <ckpt>`` has no counterpart in the reference: the images listed in ``segment_csv`` are segmented and their part
 maps written as PNG files at the resolution of the source photographs (``segment``).
+
+``--index <yaml> -c <ckpt>`` is the work-alike of deepfashion/code/eval/eval_02's ``make_clusters`` and more: the part-appearance codes of
+the images in ``index_csv``, their per-part nearest neighbours and k-means clusters (``index``; ``partindex.py``).
 """
 import argparse
 import importlib
@@ -119,6 +122,9 @@ def main(argv=None):
     ap.add_argument("--segment", nargs="+", default=None,
                     help="segmentation yaml(s): label maps / overlays / confidence maps of the images in segment_csv, as PNG files "
                          "at source resolution under <root>/segment/<global_step>/")
+    ap.add_argument("--index", nargs="+", default=None,
+                    help="index yaml(s): the part-appearance codes of the images in index_csv, their per-part nearest neighbours and "
+                         "k-means clusters under <root>/index/<global_step>/")
     ap.add_argument("--parts", default=None, help="--transfer: comma-separated part ids taken from the column image (default: all)")
     ap.add_argument("--eval-batches", type=int, default=None, help="number of batches to evaluate (default: one epoch)")
     ap.add_argument("-c", "--checkpoint", default=None)
@@ -127,8 +133,11 @@ def main(argv=None):
     ap.add_argument("--set", nargs="*", default=[], help="key=value overrides (yaml-parsed)")
     ap.add_argument("--strict-dataset", action="store_true")
     args = ap.parse_args(argv)
-    if (args.train is not None) + (args.eval is not None) + (args.transfer is not None) + (args.segment is not None) != 1:
-        ap.error("exactly one of -t / -e / --transfer / --segment is required")
+    if ((args.train is not None) + (args.eval is not None) + (args.transfer is not None) + (args.segment is not None)
+            + (args.index is not None) != 1):
+        ap.error("exactly one of -t / -e / --transfer / --segment / --index is required")
+    if args.index is not None:
+        return index(args)
     if args.segment is not None:
         return segment(args)
     if args.transfer is not None:
@@ -530,6 +539,34 @@ def segment(args):
     odir = os.path.join(root, "segment", str(it.global_step))
     print("[INFO] {} images segmented into {}".format(len(rows), odir))
     return {"rows": rows, "root": root, "dir": odir, "model": model}
+
+
+def index(args):
+    """``--index``: the part-appearance index of the images in ``index_csv`` (``partindex.index_files``; the keys and their defaults:
+    ``partindex.INDEX_DEFAULTS``).  Outputs under <root>/index/<global_step>/: features.npz, index.csv, neighbours.npz, clusters.p
+    and the contact sheets.  A wrong key raises ValueError before the model is built; a missing image raises FileNotFoundError, as
+    on --segment.  Returns {"root", "dir", "model", "index", "neighbours", "clusters"}."""
+    from . import partindex
+    cfg = load_config(args.index)
+    for kv in args.set:
+        k, v = kv.split("=", 1)
+        cfg[k] = yaml.safe_load(v)
+    cfg["test_mode"] = True
+    partindex.index_options(cfg)    # a wrong key fails before a device is touched
+    if not cfg.get("data_root"):
+        raise ValueError("--index: `data_root` is required")
+    dist_setup()
+    root = args.project or os.path.join("logs", time.strftime("%Y-%m-%dT%H-%M-%S") + "_index")
+    Model, Iterator = get_obj_from_str(cfg["model"]), get_obj_from_str(cfg["iterator"])
+    model = Model(cfg)
+    it = Iterator(cfg, root, model)
+    it.initialize(args.checkpoint)
+    if args.checkpoint is None:
+        LOG.warning("--index without -c: the part codes of freshly initialised weights")
+    odir = os.path.join(root, "index", str(it.global_step))
+    res = partindex.index_files(model, cfg, odir)
+    print("[INFO] {} images indexed into {}".format(res["index"].N, odir))
+    return dict(res, root=root, dir=odir, model=model)
 
 
 if __name__ == "__main__":
