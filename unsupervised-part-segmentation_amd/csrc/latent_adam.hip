@@ -209,7 +209,7 @@ extern "C" int ups_latent_fwd(const float* params, const float* eps, const float
 extern "C" int ups_latent_bwd(const float* params, const float* eps, const float* level, const float* g_samples,
                               const float* g_kl_dev, float g_kl_scale, int32_t S, int32_t B, int32_t dim, float* g_params,
                               void* stream) {
-    UPS_CHECK_ARG(params && eps && level && g_samples && g_params && S >= 1 && S <= MAXS);
+    UPS_CHECK_ARG(params && eps && level && g_samples && g_params && S >= 1 && S <= MAXS && B > 0 && dim > 0);
     Levels lv;
     for (int s = 0; s < MAXS; ++s) lv.v[s] = s < S ? level[s] : 0.f;
     hipLaunchKernelGGL(latent_bwd_kernel, dim3(B, ups_cdiv(dim, 32)), dim3(256), 0, (hipStream_t)stream, params, eps, lv,
@@ -285,7 +285,7 @@ extern "C" int ups_state_update(const float* stats, const float* old_state, floa
 
 extern "C" int ups_gauss_hm(const float* pts, const float* stddev, float* out, int32_t B, int32_t h, int32_t w, int32_t K,
                             void* stream) {
-    UPS_CHECK_ARG(pts && stddev && out);
+    UPS_CHECK_ARG(pts && stddev && out && B > 0 && h > 0 && w > 0 && K > 0);
     hipLaunchKernelGGL(gauss_hm_kernel, dim3(ups_cdiv((long long)B * h * w * K, 256)), dim3(256), 0, (hipStream_t)stream, pts,
                        stddev, out, B, h, w, K);
     UPS_LAUNCH_CHECK();
@@ -293,7 +293,7 @@ extern "C" int ups_gauss_hm(const float* pts, const float* stddev, float* out, i
 }
 extern "C" int ups_gauss_hm3(const float* mu, const float* L, float* out, int32_t B, int32_t h, int32_t w, int32_t K,
                              void* stream) {
-    UPS_CHECK_ARG(mu && L && out);
+    UPS_CHECK_ARG(mu && L && out && B > 0 && h > 0 && w > 0 && K > 0);
     hipLaunchKernelGGL(gauss_hm3_kernel, dim3(ups_cdiv((long long)B * h * w * K, 256)), dim3(256), 0, (hipStream_t)stream, mu, L,
                        out, B, h, w, K);
     UPS_LAUNCH_CHECK();
