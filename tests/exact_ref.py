@@ -227,7 +227,7 @@ CASES = [
     Case("patch_kchunks16", "conv", 2, 16, 16, 512, 512, act="relu", wdens=0.5, instance="patch, kchunks 16 (one block per CU, 3-stage ring)"),
     Case("patch_occ2_bn64", "conv", 32, 64, 64, 64, 64, act="relu", res_self=True, instance="patch <64,2>: 512 blocks"),
     Case("patch_occ2_bn128_thin", "conv", 16, 64, 64, 32, 136,
-         instance="patch <128,2> through the single-chunk gate (ci <= 32, co_fill > 64, UPS_PATCH_THIN128): 512 blocks, LDS-DMA patch"),
+         instance="patch <128,2> through the single-chunk gate (ci <= 32, co_fill > 64, at least 512 blocks of 128 columns): 512 blocks, LDS-DMA patch"),
     Case("patch_occ2_bn128", "conv", 16, 64, 64, 40, 136, act=LR,
          instance="patch <128,2> through the ci > 32 gate: 512 blocks, two chunks, static-tap form, ragged second N-tile"),
     Case("patch_thin_1536", "conv", 24, 128, 128, 32, 32, act=LR, res_self=True,

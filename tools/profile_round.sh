@@ -101,7 +101,7 @@ for m in dgrad; do          # fp8 mode's launch of the same layer (its forward s
 done
 (echo "== bf16, activation-on-load (round-2 form)"; python3 tools/bench_conv.py --iters 10; echo "== the model form: post-activation storage; fp16 forward tensors for the 3x3 layers"; python3 tools/bench_conv.py --iters 10 --post --f16) > $O/${TAG}_bench_conv.txt 2>&1
 python3 tools/bench_conv.py --fp8 --iters 10 --only dv_rb128,dv_rb64,dv_rb32,dv_rb16,ea_rb2,vgg3_2,vgg4_2 > $O/${TAG}_bench_conv_fp8.txt 2>&1
-(echo "== forward operand arrives as an e4m3 copy: block-scaled K = 128 MFMA"; python3 tools/bench_conv.py --fp8 --fp8-copy --iters 10 --only dv_rb128,dv_rb64,dv_rb32,dv_rb16,ea_rb2,vgg3_2,vgg4_2; echo "== the same with UPS_F8_SCALED=0 (K = 32 fp8 MFMA)"; UPS_F8_SCALED=0 python3 tools/bench_conv.py --fp8 --fp8-copy --iters 10 --only dv_rb128,dv_rb64,dv_rb32,dv_rb16,ea_rb2,vgg3_2,vgg4_2) > $O/${TAG}_bench_conv_fp8_copy.txt 2>&1
+(echo "== forward operand arrives as an e4m3 copy: block-scaled K = 128 MFMA"; python3 tools/bench_conv.py --fp8 --fp8-copy --iters 10 --only dv_rb128,dv_rb64,dv_rb32,dv_rb16,ea_rb2,vgg3_2,vgg4_2) > $O/${TAG}_bench_conv_fp8_copy.txt 2>&1
 python3 tools/bench_first.py > $O/${TAG}_bench_first.txt 2>&1
 # fp8 mode: one-stream kernel trace grouped by (kernel, grid)
 UPS_NO_OVERLAP=1 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats8 -- python3 bench.py --precision fp8 --no-cpu-baseline --steps 10 --warmup 6 > $O/bench_fp8_nooverlap.log 2>&1

@@ -1313,13 +1313,6 @@ int launch_bn(const PatchK& k, hipStream_t s) {
         kchunks, nblocks);
 }
 
-// UPS_PATCH_STATIC=0: the descriptor-driven tap loop everywhere (A/B runs)
-static int static_taps_on() { return UPS_ENV_ON_CACHED("UPS_PATCH_STATIC"); }
-// UPS_PATCH_DMA=0: register-staged patch everywhere (A/B runs)
-static int dma_patch_on() { return UPS_ENV_ON_CACHED("UPS_PATCH_DMA"); }
-// UPS_PATCH_OCC=1 forces the one-block-per-CU configuration (A/B runs)
-static int patch_occ() { return UPS_ENV_OFF_CACHED("UPS_PATCH_OCC") ? 1 : 2; }
-
 template <typename T, int SUB>
 int launch_small(const PatchK& k, hipStream_t s) {
     // whole 8x8 / 4x4 images packed 4 / 16 to a tile: narrower N-tiles when the grid would not fill the chip
@@ -1333,13 +1326,13 @@ int launch_small(const PatchK& k, hipStream_t s) {
 // on the way (no activation-on-load, no part mask, whole 32-channel chunks), the halo patch by LDS-DMA
 template <typename T, int BN, int OCC>
 int launch_v(const PatchK& k, hipStream_t s) {
-    const bool dmap = dma_patch_on() && k.act_in == UPS_ACT_NONE && !k.mask && !k.mask_grad && k.ci % 32 == 0;
-    if (static_taps_on() && dmap) {
+    const bool dmap = k.act_in == UPS_ACT_NONE && !k.mask && !k.mask_grad && k.ci % 32 == 0;
+    if (dmap) {
         if (k.taps_static == 1) return launch_bn<T, BN, OCC, TS, 0, false, 1, true>(k, s);
         if (k.taps_static == 2) return launch_bn<T, BN, OCC, TS, 0, false, 2, true>(k, s);
     }
     // (without the DMA patch only the forward order of the widest two-blocks-per-CU instance has a static form: the others spill)
-    if (static_taps_on() && k.taps_static == 1 && BN == 128 && OCC == 2) return launch_bn<T, BN, OCC, TS, 0, false, (BN == 128 && OCC == 2) ? 1 : 0>(k, s);
+    if (k.taps_static == 1 && BN == 128 && OCC == 2) return launch_bn<T, BN, OCC, TS, 0, false, (BN == 128 && OCC == 2) ? 1 : 0>(k, s);
     return launch_bn<T, BN, OCC, TS>(k, s);
 }
 
@@ -1351,11 +1344,10 @@ int launch_t(const PatchK& k, hipStream_t s) {
       if constexpr (__is_same(T, bf16)) {
         if (k.f8_deq && k.in_f8) {      // pre-quantised input: bf16-sized staging, two blocks per CU on large grids
             const int tiles8 = k.n * ((k.w + TS - 1) / TS) * ((k.h + TS - 1) / TS);
-            const bool big128 = patch_occ() == 2 && tiles8 * ups_cdiv(k.co_fill, 128) >= 512;
-            const bool big64 = patch_occ() == 2 && tiles8 * ups_cdiv(k.co_fill, 64) >= 512;
-            // whole 128-channel double chunks on a grid of two blocks per CU: the block-scaled K = 128 MFMA (UPS_F8_SCALED=0: off)
-            const bool scaled = UPS_ENV_ON_CACHED("UPS_F8_SCALED");
-            if (scaled && k.ci % 128 == 0) {
+            const bool big128 = tiles8 * ups_cdiv(k.co_fill, 128) >= 512;
+            const bool big64 = tiles8 * ups_cdiv(k.co_fill, 64) >= 512;
+            // whole 128-channel double chunks on a grid of two blocks per CU: the block-scaled K = 128 MFMA
+            if (k.ci % 128 == 0) {
                 if (k.co_fill > 64 && big128) return k.f8_e5m2 ? launch_bn<T, 128, 2, TS, 4, true>(k, s) : launch_bn<T, 128, 2, TS, 3, true>(k, s);
                 if (k.co_fill <= 64 && big64) return k.f8_e5m2 ? launch_bn<T, 64, 2, TS, 4, true>(k, s) : launch_bn<T, 64, 2, TS, 3, true>(k, s);
             }
@@ -1381,14 +1373,12 @@ int launch_t(const PatchK& k, hipStream_t s) {
         // single-chunk layers (ci <= 32, e.g. the dgrad of the P-channel logit conv) use 64-wide tiles and one patch buffer
         const int tiles = k.n * ((k.w + TS - 1) / TS) * ((k.h + TS - 1) / TS);
         if (k.co_fill > 64 && k.ci > 32) {
-            if (patch_occ() == 2 && !k.out_f8_amax && tiles * ups_cdiv(k.co_fill, 128) >= 512) return launch_v<T, 128, 2>(k, s);
+            if (!k.out_f8_amax && tiles * ups_cdiv(k.co_fill, 128) >= 512) return launch_v<T, 128, 2>(k, s);
             // a grid of one 128-wide block per CU: 64-wide tiles put two blocks on every CU instead (4 waves per SIMD)
-            const bool mid = UPS_ENV_ON_CACHED("UPS_PATCH_MID");
-            if (mid && patch_occ() == 2 && tiles * ups_cdiv(k.co_fill, 64) >= 512) return launch_v<T, 64, 2>(k, s);
+            if (tiles * ups_cdiv(k.co_fill, 64) >= 512) return launch_v<T, 64, 2>(k, s);
             {   // at most one 128-wide block per CU, many channel chunks: 64-wide tiles with chunk-granular weight stages (CSTD)
-                const bool cst = UPS_ENV_ON_CACHED("UPS_PATCH_CST");
-                const bool dmap = dma_patch_on() && k.act_in == UPS_ACT_NONE && !k.mask && !k.mask_grad && k.ci % 32 == 0;
-                if (cst && static_taps_on() && dmap && !k.out_f8_amax && k.ci >= 128 && tiles * ups_cdiv(k.co_fill, 128) <= 256) {
+                const bool dmap = k.act_in == UPS_ACT_NONE && !k.mask && !k.mask_grad && k.ci % 32 == 0;
+                if (dmap && !k.out_f8_amax && k.ci >= 128 && tiles * ups_cdiv(k.co_fill, 128) <= 256) {
                     if (k.taps_static == 1) return launch_bn<T, 64, 1, TS, 0, false, 1, true, true>(k, s);
                     if (k.taps_static == 2) return launch_bn<T, 64, 1, TS, 0, false, 2, true, true>(k, s);
                 }
@@ -1397,24 +1387,17 @@ int launch_t(const PatchK& k, hipStream_t s) {
         }
         if (k.co_fill > 32) {
             // a single input chunk with many outputs (the input gradient of the P-channel logit convolution: 16 -> 256 channels,
-            // a store-bound launch): 128-wide tiles halve the number of blocks and patch loads (0.55 -> 0.48 ms; UPS_PATCH_THIN128=0: off)
-            const bool thin128 = UPS_ENV_ON_CACHED("UPS_PATCH_THIN128");
+            // a store-bound launch): 128-wide tiles halve the number of blocks and patch loads (0.55 -> 0.48 ms)
             // (not when the launch has to write an fp8 copy of its output: the 128-wide two-blocks-per-CU instance cannot -- EMITS)
-            if (thin128 && k.co_fill > 64 && patch_occ() == 2 && tiles * ups_cdiv(k.co_fill, 128) >= 512) {
+            if (k.co_fill > 64 && tiles * ups_cdiv(k.co_fill, 128) >= 512) {
                 // a launch that writes an fp8 copy takes the descriptor-tap form of the 128-wide instance (the one that emits)
                 if (k.out_f8_amax) return launch_bn<T, 128, 2, TS>(k, s);
                 return launch_v<T, 128, 2>(k, s);
             }
-            return (patch_occ() == 2 && k.ci > 32 && tiles * ups_cdiv(k.co_fill, 64) >= 512) ? launch_v<T, 64, 2>(k, s)
-                                                                                              : launch_v<T, 64, 1>(k, s);
+            return (k.ci > 32 && tiles * ups_cdiv(k.co_fill, 64) >= 512) ? launch_v<T, 64, 2>(k, s) : launch_v<T, 64, 1>(k, s);
         }
-        {   // few outputs over many input chunks (the P-channel logit convolution: 256 -> 10 at 128x128): the 32-wide instance keeps one
-            // block per CU busy with one exposed patch round trip per chunk; UPS_PATCH_THINOUT=64 / 128 tries the two-blocks-per-CU
-            // instances on it (three quarters / seven eighths of their MFMA columns idle, but the launch is latency-bound)
-            const int thinout = (int)UPS_ENV_INT_CACHED("UPS_PATCH_THINOUT", 0);
-            if (thinout == 64 && k.ci > 32 && patch_occ() == 2 && tiles >= 512) return launch_v<T, 64, 2>(k, s);
-            if (thinout == 128 && k.ci > 32 && patch_occ() == 2 && tiles >= 512 && !k.out_f8_amax) return launch_v<T, 128, 2>(k, s);
-        }
+        // few outputs over many input chunks (the P-channel logit convolution: 256 -> 10 at 128x128): the 32-wide instance keeps one
+        // block per CU busy with one exposed patch round trip per chunk
         return launch_v<T, 32, 1>(k, s);
     } else {
         if (k.co_fill > 64) return launch_bn<T, 128, 1, TS>(k, s);
@@ -1447,14 +1430,12 @@ int ups_conv3x3_patch_try(const ups_conv_desc* d, hipStream_t s) {
     }
     const bool small = d->hi == d->wi && (d->hi == 8 || d->hi == 4) && d->n % ((TS / d->hi) * (TS / d->hi)) == 0;
     {
-        const bool small_on = !UPS_ENV_OFF_CACHED("UPS_NO_SMALL_PATCH");
-        // ragged tiles (UPS_PATCH_RAGGED=0: off): plain forward / input-gradient launches only -- no depth-to-space output, part
+        // ragged tiles: plain forward / input-gradient launches only -- no depth-to-space output, part
         // masks, fp8 operands or copies (their store loops and scale maxima assume whole tiles), at least one whole tile row's worth
         // of pixels so that the launch is not mostly padding
-        const bool ragged_on = UPS_ENV_ON_CACHED("UPS_PATCH_RAGGED");
-        const bool ragged_ok = ragged_on && d->hi >= 12 && d->wi >= 12 && !d->d2s && !d->mask_bits && !d->mask_grad && !d->f8_deq &&
+        const bool ragged_ok = d->hi >= 12 && d->wi >= 12 && !d->d2s && !d->mask_bits && !d->mask_grad && !d->f8_deq &&
                                !d->in_f8 && !d->out_f8 && !d->out_f8_amax;
-        if ((d->hi % TS || d->wi % TS) && !(small && small_on) && !ragged_ok) return 1;
+        if ((d->hi % TS || d->wi % TS) && !small && !ragged_ok) return 1;
     }
     bool seen[9] = {false, false, false, false, false, false, false, false, false};
     for (int t = 0; t < 9; ++t) {
@@ -1518,17 +1499,15 @@ int ups_conv3x3_patch_try(const ups_conv_desc* d, hipStream_t s) {
     k.out_act = d->out_act; k.res_act = d->res_act;
     {   // residual block: res == in, channel chunk c <-> output channels 32c.. (no CoordConv channels are part of `in`), whole chunks,
         // 16-bit, one tile per image, an N-tile of at least two 16-channel blocks per wave (BN >= 64 in launch_t's choice below)
-        const bool rp_on = UPS_ENV_ON_CACHED("UPS_RES_PATCH");
-        k.res_patch = rp_on && d->res && d->res == d->in && d->ldr == d->ldi && d->ci == d->co_fill && d->co == d->co_fill && d->ci % 32 == 0 &&
+        k.res_patch = d->res && d->res == d->in && d->ldr == d->ldi && d->ci == d->co_fill && d->co == d->co_fill && d->ci % 32 == 0 &&
                       d->dtype != UPS_F32 && !small && !d->dact && !d->mask_bits && !d->mask_grad && !d->d2s && !d->f8_deq && !d->out_f32 &&
                       d->act_in == UPS_ACT_NONE &&    // (with activation-on-load the patch holds act(x), the residual wants x)
-                      dma_patch_on() && static_taps_on() && (fwd || flip);       // ... and only the DMA-patch instances implement it
+                      (fwd || flip);       // ... and only the DMA-patch instances implement it
         // round 6: the input gradient of a residual block whose act' arrives as sign bytes (leaky ReLU: 1 / slope exists)
-        const bool rp2_on = UPS_ENV_ON_CACHED("UPS_RES_PATCH_DGRAD");
-        if (rp_on && rp2_on && !k.res_patch && d->res && d->res == d->in && d->ldr == d->ldi && d->ci == d->co_fill && d->co == d->co_fill &&
+        if (!k.res_patch && d->res && d->res == d->in && d->ldr == d->ldi && d->ci == d->co_fill && d->co == d->co_fill &&
             d->ci % 32 == 0 && d->dtype == UPS_BF16 && !small && d->dact && k.dact_bits && d->dact_kind == UPS_ACT_LRELU && d->act_slope > 0.f &&
             (d->ldd & 63) == 0 && (((uintptr_t)k.dact_bits) & 7) == 0 && !d->mask_bits && !d->mask_grad && !d->d2s && !d->f8_deq && !d->out_f32 &&
-            !d->res_act && d->act_in == UPS_ACT_NONE && dma_patch_on() && static_taps_on() && flip && !fwd)
+            !d->res_act && d->act_in == UPS_ACT_NONE && flip && !fwd)
             k.res_patch = 2;
     }
     if ((d->out_act || d->res_act) && (d->mask_grad || d->d2s)) return 1;

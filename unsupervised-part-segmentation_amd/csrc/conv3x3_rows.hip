@@ -1125,12 +1125,8 @@ int ups_conv3x3_thinout_try(const ups_conv_desc* d, hipStream_t s) {
     k.bias = d->bias; k.coord_tab = d->coord_tab;
     k.n = d->n; k.h = d->hi; k.wd = d->wi; k.ldi = d->ldi; k.ldo = d->ldo; k.co = d->co; k.co_fill = d->co_fill; k.out_f32 = d->out_f32;
     k.strips = d->wi / 32; k.band_rows = 32; k.bands = d->hi / 32;
-    // UPS_THIN_SW=16: 16-column strips, two blocks per CU (measured equal to the 32-column form at one block per CU: 0.43 ms both;
-    // the 64-byte pieces at a 512-byte pixel pitch, not occupancy or prefetch depth, are what the launch is short of)
-    if (ups_env_off_now("UPS_THIN_SW")) {
-        k.strips = d->wi / 16;
-        return d->dtype == UPS_F16 ? launch_thinout<f16, 16>(k, s) : launch_thinout<bf16, 16>(k, s);
-    }
+    // (16-column strips at two blocks per CU measured equal, 0.43 ms both: the 64-byte pieces at a 512-byte pixel pitch, not occupancy
+    // or prefetch depth, are what the launch is short of -- docs/design/negative_results.md)
     return d->dtype == UPS_F16 ? launch_thinout<f16, 32>(k, s) : launch_thinout<bf16, 32>(k, s);
 }
 

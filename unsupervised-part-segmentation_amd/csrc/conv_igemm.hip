@@ -407,7 +407,6 @@ int launch(const ups_conv_desc& dd, hipStream_t s) {
     // split-K for latency-bound problems: few tiles, long K loop, workspace supplied.  Wider tiles + more blocks.
     d.ws = nullptr; d.splits = 1; d.stages_per_split = 0; d.ldw = 0;
     {
-        const bool sk_on = !UPS_ENV_OFF_CACHED("UPS_NO_SPLITK");
         const int chunks = d.ntaps * kchunks;
         const int bn_sk = ctot > 32 ? 64 : 32;
         const int blocks_sk = mtiles * ups_cdiv(ctot, bn_sk);
@@ -415,7 +414,7 @@ int launch(const ups_conv_desc& dd, hipStream_t s) {
         // twice: split up to ~1024 blocks (measured: 4x4 / 8x8 layers of the encoders, dv and the VGG trunk)
         const bool few = blocks_sk < 192 && chunks >= 16;
         const bool longk = (blocks_sk <= 320 && chunks >= 64) || (blocks_sk <= 512 && chunks >= 128);
-        if (sk_on && dd.workspace && (few || longk)) {
+        if (dd.workspace && (few || longk)) {
             const int cps_sk = bn_sk == 64 ? 2 : 4;
             const int stages = ups_cdiv(chunks, cps_sk);
             int splits = ups_cdiv(few ? 512 : 1024, blocks_sk);

@@ -403,9 +403,8 @@ extern "C" int ups_conv_wgrad(const ups_wgrad_desc* d, void* stream) {
         nslabs = slabs3;
     } else {
         // a single split writes exactly the elements the reduction would (rows < ci_log of every tap, the bias): straight into the
-        // gradient, no slab and no second launch (the critics' 30 dense layers; UPS_WGRAD_DIRECT=0: off)
-        const bool direct = UPS_ENV_ON_CACHED("UPS_WGRAD_DIRECT");
-        const bool one = direct && d->splitk == 1;
+        // gradient, no slab and no second launch (the critics' 30 dense layers)
+        const bool one = d->splitk == 1;
         if (one) { k.ws = d->grad; k.bias_direct = d->grad_bias; }
         if (d->dtype == UPS_F32) launch_m<float>(k, (int)M, d->splitk, s);
         else launch_m<bf16>(k, (int)M, d->splitk, s);

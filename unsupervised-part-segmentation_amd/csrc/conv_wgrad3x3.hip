@@ -654,7 +654,6 @@ int ups_wgrad3x3_run(const ups_wgrad_desc* d, hipStream_t s) {
     k.in_f16 = d->in_f16;
     k.taps_std = 1;
     for (int t = 0; t < 9; ++t) if (d->tap_dy[t] != t / 3 - 1 || d->tap_dx[t] != t % 3 - 1) k.taps_std = 0;
-    if (!ups_env_on_now("UPS_WGRAD_SLIDE")) k.taps_std = 0;      // A/B switch
     k.tap_off = 0; k.tap_wi = 0;
     for (int t = 0; t < 9; ++t) {
         k.tap_off |= (unsigned long long)(((d->tap_dy[t] + 1) << 2) | (d->tap_dx[t] + 1)) << (4 * t);

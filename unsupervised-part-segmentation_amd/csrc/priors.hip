@@ -1485,9 +1485,9 @@ static bool prior_tiles_ok(const ups_prior_desc* d, int view, std::initializer_l
     for (const void* m : maps) { if (!m) return false; all |= (uintptr_t)m; }
     return d->view == view && (d->w == 128 || d->w == 256) && ((long long)d->h * d->w) % 256 == 0 && (all & 15) == 0;
 }
-// pixel-per-lane form (round 5): P = 10 (UPS_PRIOR_PX=0: off)
+// pixel-per-lane form (round 5): P = 10
 static bool px_eligible(const ups_prior_desc* d, int view, std::initializer_list<const void*> maps) {
-    return UPS_ENV_ON_CACHED("UPS_PRIOR_PX") && d->P == 10 && prior_tiles_ok(d, view, maps);
+    return d->P == 10 && prior_tiles_ok(d, view, maps);
 }
 // chunk-per-lane, direct-from-global form (round 6): the part counts the rings cannot hold (UPS_PRIOR_DIRECT=0: off)
 static bool cpl_eligible(const ups_prior_desc* d, int view, std::initializer_list<const void*> maps) {

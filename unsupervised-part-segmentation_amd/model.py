@@ -523,8 +523,8 @@ class Trainer(object):
                               post_storage=model.nets.post_storage,
                               # (measured, round 5: the trunk on fp8 copies -- 20 more launches per step on e4m3 operands -- runs the
                               # step 1.4 % SLOWER: the pools' and the convolutions' copy emission costs more than blocks 2-4 gain at
-                              # 64 images; off by default, `vgg_fp8: True` / UPS_VGG_FP8=1 for measurements)
-                              fp8=bool(config.get("vgg_fp8", SW.flag("UPS_VGG_FP8"))))
+                              # 64 images; off by default, `vgg_fp8: True` for measurements)
+                              fp8=bool(config.get("vgg_fp8", False)))
         # `vgg_weights`: npz / torch file with the Keras VGG19 ImageNet kernels in HWIO (edflow downloads them at run time;
         # they are not obtainable offline).  Without it the perceptual loss runs on seeded He-normal stand-ins: fine for
         # timing and parity, NOT for training a model that should match the reference's part quality -- say so loudly.

@@ -168,7 +168,6 @@ class SignBits(object):
     PRODUCER of such a tensor (a convolution's epilogue, the x2 bilinear kernel) now also writes [n,h,w,c/8] sign bytes, the handle
     carries them (nets.Act.bits) and the consuming convolution's backward passes them to ups_conv_igemm next to `dact`.
     The caller that will keep the bits asks for them with ``Handoff.want_bits`` and finds them in ``Handoff.bits`` after the call."""
-    ENABLED = SW.flag("UPS_SIGN_BITS")
     stats = None        # a dict when a probe wants to know which input gradients ran without bits (tools/probes/sign_bits_coverage.py)
 
 
@@ -344,9 +343,8 @@ class Fp8State(object):
         self.fmax = None            # [MAX_LAYERS] fp32: largest normal of the slot's format
         self.count = 0
         self.GRAD = True            # input gradients of the fp8 layers on e5m2 operands (False: bf16 kernels)
-        # weight gradients of the wide 3x3 layers on e4m3 x e5m2 operands (conv_wgrad3x3_f8.hip) wherever the gradient arrives with
-        # its producer's e5m2 copy; UPS_F8_WGRAD=0: bf16 weight gradients (A/B runs)
-        self.WGRAD = SW.flag("UPS_F8_WGRAD")
+        # (weight gradients of the wide 3x3 layers: on e4m3 x e5m2 operands, conv_wgrad3x3_f8.hip, wherever the gradient arrives with
+        # its producer's e5m2 copy -- eligible_wgrad)
         # COPY_ONLY: a layer takes the fp8 kernels only when its operand arrives quantised (a copy written by the producing
         # bilinear / convolution kernel); layers whose operand would have to be converted inside the kernel (24 staging
         # registers, one block per CU: slower than bf16) stay on the bf16 kernels.  None: follows PRODUCER.
@@ -473,7 +471,7 @@ class Fp8State(object):
 
     def eligible_wgrad(self, layer, g, x, mask):
         """Weight gradient on the block-scaled fp8 MFMA (mirrors eligible8 of conv_wgrad3x3_f8.hip): K = pixels."""
-        return (self.enabled and self.WGRAD and mask is None and g.dtype == torch.bfloat16 and x.dtype == torch.bfloat16
+        return (self.enabled and mask is None and g.dtype == torch.bfloat16 and x.dtype == torch.bfloat16
                 and layer.k == 3 and layer.stride == 1 and x.shape[1] % 16 == 0 and x.shape[2] % 16 == 0
                 and round8(layer.ci_log) % 64 == 0 and layer.co % 128 == 0 and g.shape[-1] % 16 == 0)
 
@@ -590,7 +588,7 @@ class ConvLayer(_Layer):
     def d2s_channels(self, x):
         """C of the depth-to-space input gradient (ups_conv_desc.d2s) when this layer / tensor can take it, else 0."""
         c = self.ci_log
-        ok = (D2S_DGRAD and self.k == 3 and self.stride == 2 and x.dtype == torch.bfloat16 and c >= 8 and (c & (c - 1)) == 0
+        ok = (self.k == 3 and self.stride == 2 and x.dtype == torch.bfloat16 and c >= 8 and (c & (c - 1)) == 0
               and x.shape[-1] == c and x.shape[1] % 32 == 0 and x.shape[2] % 32 == 0)
         return c if ok else 0
 
@@ -675,7 +673,6 @@ def _fill_taps(desc, dy, dx, tw, ntaps):
 
 
 SPLITK_WS_BYTES = 48 << 20
-D2S_DGRAD = not SW.flag("UPS_NO_D2S")      # one-launch input gradient of the stride-2 layers (A/B switch)
 
 
 def _attach_ws(d, device):
@@ -801,7 +798,7 @@ def conv_forward(x, layer, res=None, out_f32=False, ldo=None, co_fill=None, mask
                 if t8 is not None:
                     side.f8_out = Fp8.handle(eo, t8, want_act)
     bits = None
-    if side.want_bits and SignBits.ENABLED and not out_f32 and out.dtype == torch.bfloat16 and ldo % 8 == 0:
+    if side.want_bits and not out_f32 and out.dtype == torch.bfloat16 and ldo % 8 == 0:
         bits = torch.empty((n, ho, wo, ldo // 8), dtype=torch.uint8, device=x.device)
         d.sign_out = bits.data_ptr()
     assert round8(layer.ci_log) <= ldi, (layer.name, layer.ci_log, ldi)
@@ -1257,7 +1254,7 @@ class BilinearFn(torch.autograd.Function):
         f8_site = site is not None and Fp8.enabled and Fp8.PRODUCER and x.dtype == torch.bfloat16 and c % 64 == 0 and (2 * h) % 16 == 0
         ctx.site, ctx.shape = (site if f8_site else None), (n, h, w, c)
         if out_act:
-            if side is not None and side.want_bits and SignBits.ENABLED and x.dtype == torch.bfloat16 and c % 8 == 0:
+            if side is not None and side.want_bits and x.dtype == torch.bfloat16 and c % 8 == 0:
                 side.bits = torch.empty((n, 2 * h, 2 * w, c // 8), dtype=torch.uint8, device=x.device)
                 L.call("ups_bilinear2x_fwd_bits", L.ptr(x), L.ptr(y), L.dt(x) if fmt is None else fmt, n, h, w, c, out_act, slope,
                        L.ptr(side.bits), L.stream())

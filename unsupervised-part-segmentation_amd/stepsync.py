@@ -9,11 +9,8 @@ import torch
 
 from . import dist as D, ops, switches as SW
 
-LATE_JOIN = SW.flag("UPS_LATE_JOIN")      # A/B switch: single rank joins the weight-gradient stream only before Adam
 JOIN_TIMING = SW.flag("UPS_JOIN_TIMING")
-# A/B switch, data parallel: bucket all-reduces enqueued from the weight-gradient stream's position, not after a join with it (round 4)
-DP_SIDE_LAUNCH = SW.flag("UPS_DP_SIDE_LAUNCH")
-EARLY_ADAM = SW.flag("UPS_EARLY_ADAM")    # A/B switch: ... and queues each key's Adam behind its weight gradients
+EARLY_ADAM = SW.flag("UPS_EARLY_ADAM")    # test switch: a single rank queues each key's Adam behind its weight gradients
 
 
 class GradSync(object):
@@ -53,8 +50,8 @@ class GradSync(object):
     def _reduce_from(self, current=True):
         """The context a bucket's all-reduce is enqueued in: the weight-gradient stream's position (torch's process group orders its
         stream behind the stream current at the call), so that the LAUNCHING stream need not wait for the segment's weight gradients
-        (DESIGN section 7).  DP_SIDE_LAUNCH off: it joins that stream instead and idles for as long as the queue lags."""
-        if ops.Streams.enabled and DP_SIDE_LAUNCH:
+        (DESIGN section 7).  Without side streams it joins that stream instead."""
+        if ops.Streams.enabled:
             return torch.cuda.stream(ops.Streams.wgrad_behind(self.tr.device, current=current))
         ops.Streams.join(self.tr.device, names=("wgrad",))
         return contextlib.nullcontext()
@@ -92,7 +89,7 @@ class GradSync(object):
             if tr.world_size > 1 or D.FORCE_COLLECTIVES:
                 tr.graph.boundary("grads", list(keys))
             return
-        if tr.world_size == 1 and not D.FORCE_COLLECTIVES and LATE_JOIN:
+        if tr.world_size == 1 and not D.FORCE_COLLECTIVES:
             # a single rank has nothing to reduce: the launching stream need not wait for the weight-gradient stream here (it would idle
             # whenever that stream lags); both meet before the end of the step (finish).  The tensors the side stream reads stay
             # referenced until then (ops.Streams.keep).  The keys' Adam updates are queued right BEHIND their weight gradients on that
