@@ -725,6 +725,26 @@ int ups_adam_dev(float* p, const float* g, float* m, float* v, int64_t count, co
 int ups_tps_warp(const float* img, const float* T, const float* coord, float* out, int32_t n, int32_t h, int32_t w,
                  int32_t c, int32_t K, void* stream);
 
+/* ---------------------------------------------------------------- thin-plate-spline parameters and solve (csrc/tps.hip)
+ * Added without a new UPS_ABI_VERSION, as the ups_augment_* entries: no struct changed, and a binding that expects these symbols fails
+ * to load an older library by name.
+ * ups_tps_solve: T [n][2][K+3] fp32 of coord / vector [n][K][2] fp32 (x, y): the system ups_tps_warp's T solves, f(c_i) = c_i + v_i with
+ *   the affine side conditions, built in fp64 from the fp32 inputs (phi(d2) = d2 log(d2 + 1e-6)), solved in fp64 by Gaussian elimination
+ *   with partial pivoting (largest |a| at or below the diagonal, ties to the lowest row), rounded to fp32 once.  One wave per sample, one
+ *   launch, no host check: a sample whose pivot is exactly 0 (coincident control points) or whose solution is not finite gets the
+ *   identity transform T[0] = (0,1,0,0...), T[1] = (0,0,1,0...) and adds 1 to the DEVICE counter *n_singular (int32, the caller's; it is
+ *   never reset here).  Two launches give the same bits.
+ * ups_tps_params: coord, vector and T of n samples from uniforms [n][4K+7] fp32 in [0,1) (layout of tps.tps_parameters: 2K control-point
+ *   jitters, 2K TPS vectors, offset, offset_2, the two scales, the rotation) and base_points [K][2] DOUBLE, device: ranges, scale about
+ *   `offset`, rotation about `offset_2`, cos / sin all in fp64; coord is rounded to fp32 once, vector = fp32(target - double(coord)), and
+ *   the solve of ups_tps_solve runs on those two rounded outputs in the same launch.
+ * UPS_E_UNSUPPORTED: K < 3 (no unique affine part) or K > 32.  UPS_E_ARG, nothing launched: a NULL pointer, n < 1.
+ * Semantics re-derived from the published algorithm: UNVERIFIED (parity unpinned), as ups_tps_warp. */
+int ups_tps_solve(const float* coord, const float* vector, float* T, int32_t* n_singular, int32_t n, int32_t K, void* stream);
+int ups_tps_params(const float* uniforms, const double* base_points, int32_t K, double scal, double tps_scal, double rot_scal,
+                   double off_scal, double scal_var, double augm_scal, float* coord, float* vector, float* T, int32_t* n_singular,
+                   int32_t n, void* stream);
+
 /* ---------------------------------------------------------------- Gaussian renderers (N:1639-1702, N:1976-2021)
  * tf_hm: P_xy [B][K][2], stddev [B][K][2] on the integer pixel grid (x,y order) -> heat [B,h,w,K] */
 int ups_gauss_hm(const float* pts, const float* stddev, float* out, int32_t B, int32_t h, int32_t w, int32_t K, void* stream);

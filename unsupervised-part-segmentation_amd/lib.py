@@ -184,6 +184,8 @@ _SIGS = {
     "ups_adam": ([_P, _P, _P, _P, _L, _F, _F, _F, _F, _F, _P], C.c_int),
     "ups_adam_dev": ([_P, _P, _P, _P, _L, _P, _F, _F, _F, _F, _P], C.c_int),
     "ups_tps_warp": ([_P, _P, _P, _P, _I, _I, _I, _I, _I, _P], C.c_int),
+    "ups_tps_solve": ([_P, _P, _P, _P, _I, _I, _P], C.c_int),
+    "ups_tps_params": ([_P, _P, _I] + [C.c_double] * 6 + [_P, _P, _P, _P, _I, _P], C.c_int),
     "ups_gauss_hm": ([_P, _P, _P, _I, _I, _I, _I, _P], C.c_int),
     "ups_gauss_hm3": ([_P, _P, _P, _I, _I, _I, _I, _P], C.c_int),
     "ups_convert": ([_P, _I, _P, _I, _L, _P], C.c_int),

@@ -551,6 +551,12 @@ class Trainer(object):
         self._gen = torch.Generator(device=d)
         self._gen.manual_seed(D.shard_seed(config.get("noise_seed", 4321), kwargs.get("rank", 0)))      # TPS uniforms, crop window
         self._noise = ops.NoiseStream(D.shard_seed(config.get("noise_seed", 4321), kwargs.get("rank", 0)))  # the sampling noise
+        # `use_tps`: samples whose TPS system was singular and got the identity transform (ups_tps_solve), counted on the device and read
+        # on the steps that log scalars (`_check_tps_singular`: one warning per run)
+        self._tps_singular = torch.zeros(1, dtype=torch.int32, device=d) if model.use_tps else None
+        self._tps_warned = False
+        if model.use_tps:
+            TPS.base_points(d)          # (made before any capture: a captured step only launches)
         self._lazy_logs, self._done_thunk, self._last_ckpt = None, None, None
         self.switches_report = SW.report()       # the environment switches that differ from their defaults (switches.py), logged once
         if self.logger:
@@ -858,7 +864,7 @@ class Trainer(object):
                           .format(type(exc).__name__, exc, done))
 
     def _train_step(self, batch, noise=None):
-        if self._graph_enabled and not self.model.use_tps:
+        if self._graph_enabled:
             # one device scalar carries Adam's bias-corrected step size: usable only while every trained key is at the same
             # Adam step (not after restoring a checkpoint whose keys were trained for different numbers of steps)
             ts = set(self.model.bank.groups[k]["t"] for k in self.loss_keys())
@@ -886,6 +892,11 @@ class Trainer(object):
         g = self.graph
         for k, buf in g.inputs.items():
             buf.copy_(batch[k], non_blocking=True)
+        if g.tps_u is not None:     # the TPS uniforms: drawn where the eager step draws them, BEFORE the window corner (one `_gen` stream)
+            if noise is None or "tps_u" not in noise:
+                g.tps_u.uniform_(0, 1, generator=self._gen)
+            else:
+                g.tps_u.copy_(noise["tps_u"], non_blocking=True)
         for k, buf in g.noise.items():
             if k == "crop_yx" and (noise is None or "crop_yx" not in noise):     # (explicit noise without a window corner: drawn as usual)
                 buf.random_(0, 33, generator=self._gen)
@@ -900,7 +911,8 @@ class Trainer(object):
         lr = self.learning_rate()
         g.lr.fill_(lr * math.sqrt(1.0 - self.beta2 ** t) / (1.0 - self.beta1 ** t))
         sig = self._schedule_signature() + (lr > 0,)
-        run_step = lambda: self._step_impl(g.inputs, g.noise, graph_lr=g.lr)
+        step_noise = g.noise if g.tps_u is None else dict(g.noise, tps_u=g.tps_u)
+        run_step = lambda: self._step_impl(g.inputs, step_noise, graph_lr=g.lr)
         # warm-up: kernel attributes, side streams, allocator pools; fp8: the copy hand-off settles over four steps (first maxima,
         # first copies, unread producers going quiet) and the captured graph freezes whatever it sees
         if g.eager < (5 if ops.Fp8.enabled else 2):
@@ -936,7 +948,8 @@ class Trainer(object):
         vt = v0 if df else batch["view0_target"].to(dev, torch.float32).contiguous()    # SB_model48c:669: target = view0
         if model.use_tps:           # model.py:334-337, 282-311
             tu = None if noise is None or "tps_u" not in noise else noise["tps_u"].to(dev, torch.float32)
-            aug = TPS.make_tps([v0, v1] if df else [v0, v1, vt], model.tps_parameters, uniforms=tu, generator=self._gen)
+            aug = TPS.make_tps([v0, v1] if df else [v0, v1, vt], model.tps_parameters, uniforms=tu, generator=self._gen,
+                               n_singular=self._tps_singular)
             c.raw_views = (v0, v1, vt)          # the inputs as they came (img_ops view0 / view1 / view0_target)
             v0, v1 = aug[0], aug[1]
             vt = v0 if df else aug[2]
@@ -1638,7 +1651,25 @@ class Trainer(object):
         for k, v in self.log_ops.items():
             out[k] = float(v) if torch.is_tensor(v) else float(v)
         out.update(self._val_logs)      # the val/ keys of the most recent validation (`val_freq`)
+        self._check_tps_singular()      # (the floats above have synchronised already)
         return out
+
+    def tps_singular_count(self):
+        """`use_tps`: samples so far whose TPS system was singular and that were left unwarped (synchronises)."""
+        return 0 if self._tps_singular is None else int(self._tps_singular.item())
+
+    def _check_tps_singular(self):
+        if self._tps_singular is None or self._tps_warned:
+            return
+        n = self.tps_singular_count()
+        if n:
+            self._tps_warned = True
+            msg = ("use_tps: {} sample(s) had a singular thin-plate-spline system (coincident control points) and kept the identity "
+                   "transform (reported once per run)".format(n))
+            if self.logger:
+                self.logger.warning(msg)
+            else:
+                warnings.warn(msg)
 
     # ------------------------------------------------------------------ periodic validation (`val_freq`, `val_csv`)
     def _init_validation(self):

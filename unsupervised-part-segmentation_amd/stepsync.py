@@ -7,7 +7,7 @@ from collections import deque
 
 import torch
 
-from . import dist as D, ops, switches as SW
+from . import dist as D, ops, switches as SW, tps as TPS
 
 JOIN_TIMING = SW.flag("UPS_JOIN_TIMING")
 EARLY_ADAM = SW.flag("UPS_EARLY_ADAM")    # test switch: a single rank queues each key's Adam behind its weight gradients
@@ -157,7 +157,7 @@ class GradSync(object):
 
 class StepGraph(object):
     """``trainer.graph`` once graph mode is used (``Trainer._graph_step`` decides when to warm up, capture and replay): static input /
-    noise buffers of one batch shape, the device scalar ``lr`` for Adam's step size, the count of ``eager`` warm-up steps, and the
+    noise buffers of one batch shape (``tps_u``: the TPS uniforms of a ``use_tps`` model), the device scalar ``lr`` for Adam's step size, the count of ``eager`` warm-up steps, and the
     capture -- ``graphs`` (empty until captured), the ``bounds`` between them, the schedule signature ``sig`` it baked in and
     ``img_src``, the captured step's buffers that the image logs are rendered from after a replay.
     Data parallel: the step is captured as a SEQUENCE of graphs, cut wherever the eager step talks to the other ranks (DESIGN
@@ -168,6 +168,9 @@ class StepGraph(object):
         self.tr, self.shape, dev = weakref.proxy(trainer), (B, S), trainer.device
         self.inputs = {k: torch.empty((B, S, S, 3), dtype=torch.float32, device=dev) for k in trainer.model.inputs}
         self.noise = {k: torch.empty_like(v) for k, v in trainer.draw_noise(B).items()}
+        # `use_tps`: the uniforms of the in-graph TPS of both views.  NOT one of draw_noise's keys: the eager step draws them in
+        # make_tps, before the window corner, and the generator's stream (checkpoints carry its state) stays that one
+        self.tps_u = torch.empty((2 * B, TPS.N_UNIFORMS), dtype=torch.float32, device=dev) if trainer.model.use_tps else None
         self.lr = torch.zeros(1, dtype=torch.float32, device=dev)
         self.sig, self.eager, self.graphs, self.bounds, self.img_src = None, 0, [], [], None
         self.capturing, self._pool, self._stream, self._cur = False, None, None, None       # capturing: inside capture()
