@@ -578,6 +578,29 @@ int ups_segment_render(const float* soft, int32_t n, int32_t S, int32_t P, const
                        int64_t total, const uint8_t* src, const uint8_t* colors, double alpha, uint8_t* labels, uint8_t* overlay,
                        uint8_t* confidence, int32_t* counts, void* stream);
 
+/* Edge-aware refinement of the export: joint bilateral upsampling guided by the photograph (Kopf et al. 2007).  Added by name, without
+ * a new UPS_ABI_VERSION, as the entries above.  The definitions are DESIGN.md section 8's; tests/segrefine_ref.py restates them in
+ * NumPy with equal bytes.  Two launches per pass of n images, tables and planes as for ups_segment_render (the same table checks):
+ * ups_segment_guide: guide uint8 [n, S, S, 3], the low-resolution photograph.  Tap t of an axis of extent e covers the source indices
+ *   [a, b), a = (t e) / S, b = max(a + 1, ((t + 1) e) / S) (integer division; never empty, also when e < S), and
+ *   guide[i, ty, tx, c] = (2 sum + cnt) / (2 cnt) over the cnt source pixels of the tap's rows x columns: integer arithmetic only.
+ * ups_segment_render_guided: ups_segment_render with the four bilinear taps replaced by the (2R+2)^2 window ty = y0 + j, tx = x0 + k,
+ *   j, k = -R .. R+1 (j outer, ascending; y0, fy, x0, fx as above; a tap outside [0, S-1] is SKIPPED, not repeated):
+ *     wy = 1 - |fy - j| / (R + 1), wx alike;  d1 = sum_c |src[y, x, c] - guide[ty, tx, c]| (0 .. 765);  w = (wy wx) range_w[d1];
+ *     den += w;  num_p += w soft[ty, tx, p]   (fp64 from 0.0, every operation rounded once, each num_p its own chain in tap order)
+ *     label = first p of maximal num_p;  confidence = clamp(floor((num_label / den) * 255 + 0.5), 0, 255);  overlay, counts as above.
+ *   src (packed, at the output sizes), guide (of ups_segment_guide on the same src) and range_w are REQUIRED;  0 <= R <= 3.
+ *   range_w: 766 doubles ON THE DEVICE, 8-byte aligned, built by the host: max(exp(-(d/3)^2 / (2 sigma^2)), 2^-64) for d = 0 .. 765,
+ *   sigma in uint8 levels of mean absolute channel difference.  The floor keeps den > 0; the kernel evaluates no transcendental.
+ * Integer atomics only.  Status codes as ups_segment_render's (UPS_E_UNSUPPORTED: P > 255); also UPS_E_ARG for a NULL src, guide or
+ * range_w, R outside 0 .. 3, n * S > 2^31 - 1 (the guide's grid) and a range_w that is not 8-byte aligned. */
+int ups_segment_guide(const uint8_t* src, int32_t n, int32_t S, const int32_t* table_host, const int32_t* table, int64_t total,
+                      uint8_t* guide, void* stream);
+int ups_segment_render_guided(const float* soft, int32_t n, int32_t S, int32_t P, const int32_t* table_host, const int32_t* table,
+                              int64_t total, const uint8_t* src, const uint8_t* guide, const double* range_w, int32_t R,
+                              const uint8_t* colors, double alpha, uint8_t* labels, uint8_t* overlay, uint8_t* confidence,
+                              int32_t* counts, void* stream);
+
 /* ---------------------------------------------------------------- part-appearance index (csrc/partindex.hip)
  * Nearest neighbours and k-means on a bank of per-part appearance codes (TrainModel.encode_parts): what deepfashion/code/eval/eval_02's
  * make_clusters does off-line with scikit-learn.  Restated in NumPy float64 by tests/partindex_ref.py with equal bits.

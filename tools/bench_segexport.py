@@ -4,6 +4,8 @@
              and counts, input sets (soft maps and source images) rotated over more than the Infinity Cache: microseconds per call
              (minimum of `--repeats` readings of `--iters` calls, all printed) and the share of 8 TB/s on the bytes it must move
              (3 read + 4 written per pixel, plus `soft` once).
+(a') guided  the edge-aware route in the SAME run and on the same rotated inputs: ups_segment_guide alone, and
+             ups_segment_render_guided (sigma = 16) for R = 0, 1, 2 with its ratio to the plain kernel row above.
 (b) torch    the same result with torch ops on the device, per image: interpolate(bilinear, align_corners=False) in float64, arg-max,
              colour gather, blend, bincount; the share of label and overlay bytes that differ from the kernel's is in the row.
 (c) export   runner.segment_files over `--images` synthetic PNG files of 375 x 500 (cub128p10, bf16, seeded weights, batch 64): wall
@@ -101,6 +103,33 @@ def kernel_rows(iters, repeats, sets_mib):
     emit(dict(common, row="kernel", launch="ups_segment_render", calls_per_reading=nk, us=round(min(ts), 2), us_all=[round(t, 2) for t in ts],
               GBps=round(moved / min(ts) * 1e-3, 1), fraction_of_8TBs=round(moved / (min(ts) * 1e-6) / HBM_BYTES_PER_S, 4),
               Mpixels_per_s=round(pixels / min(ts), 1)))
+    # the edge-aware route on the same rotated inputs: the guide launch alone, then the guided kernel per radius (the guide of set k
+    # is made once, outside the timed calls)
+    guides = [torch.empty((n, S, S, 3), dtype=torch.uint8, device=dev) for _ in range(nsets)]
+    range_w = torch.from_numpy(ops.segment_range_table(16.0)).to(dev)
+
+    def launch_guide(k):
+        L.call("ups_segment_guide", L.ptr(sets[k % nsets][1]), n, S, tp, L.ptr(table_dev), total, L.ptr(guides[k % nsets]), L.stream())
+    for k in range(nsets):
+        launch_guide(k)
+    torch.cuda.synchronize()
+    tg = event_us(launch_guide, nk, repeats)
+    gmoved = 3 * pixels + 3 * n * S * S
+    emit(dict(common, row="guide", launch="ups_segment_guide", outputs="guide", bytes_to_move=gmoved, calls_per_reading=nk,
+              us=round(min(tg), 2), us_all=[round(t, 2) for t in tg], GBps=round(gmoved / min(tg) * 1e-3, 1)))
+    for radius in (0, 1, 2):
+        def launch_guided(k, radius=radius):
+            soft, src = sets[k % nsets]
+            L.call("ups_segment_render_guided", L.ptr(soft), n, S, P, tp, L.ptr(table_dev), total, L.ptr(src), L.ptr(guides[k % nsets]),
+                   L.ptr(range_w), radius, L.ptr(colors), alpha, L.ptr(labels), L.ptr(overlay), None, L.ptr(counts), L.stream())
+        for k in range(nsets):
+            launch_guided(k)
+        torch.cuda.synchronize()
+        tr = event_us(launch_guided, nk, repeats)
+        emit(dict(common, row="guided", launch="ups_segment_render_guided", radius=radius, sigma=16.0, taps=(2 * radius + 2) ** 2,
+                  calls_per_reading=nk, us=round(min(tr), 2), us_all=[round(t, 2) for t in tr],
+                  ratio_to_plain_kernel=round(min(tr) / min(ts), 2), Mpixels_per_s=round(pixels / min(tr), 1)))
+    del guides
     # the torch composition on set 0, and how its bytes compare
     soft, src = sets[0]
     views = ops.segment_views(src, table)
@@ -122,7 +151,7 @@ def kernel_rows(iters, repeats, sets_mib):
     torch.cuda.empty_cache()
 
 
-def export_rows(n_images, repeats):
+def export_rows(n_images, repeats, refine=False):
     from PIL import Image
     from upsparts_amd import configs, runner
     from upsparts_amd.model import TrainModel
@@ -143,6 +172,8 @@ def export_rows(n_images, repeats):
         with open(os.path.join(tmp, "list.csv"), "w") as f:
             f.write("\n".join(rels) + "\n")
         cfg.update({"data_root": droot, "segment_csv": os.path.join(tmp, "list.csv")})
+        if refine:
+            cfg.update({"segment_refine": "bilateral"})
         runner.segment_files(model, cfg, os.path.join(tmp, "warm"), 0)
         walls = []
         for r in range(repeats):
@@ -154,7 +185,8 @@ def export_rows(n_images, repeats):
         t0 = time.perf_counter()
         runner.segment_files(model, cfg, os.path.join(tmp, "split"), 0, profile=split)
         tsplit = time.perf_counter() - t0
-    emit({"row": "export", "images": n_images, "h": H, "w": W, "B": B, "S": 128, "P": model.n_parts, "config": "cub128p10", "precision": "bf16",
+    emit({"row": "export_refine" if refine else "export", "segment_refine": "bilateral (radius 1, sigma 16)" if refine else "none",
+          "images": n_images, "h": H, "w": W, "B": B, "S": 128, "P": model.n_parts, "config": "cub128p10", "precision": "bf16",
           "outputs": "labels + overlay", "export_s": round(min(walls), 3), "export_s_all": [round(t, 3) for t in walls],
           "images_per_s": round(n_images / min(walls), 1), "phase_synchronised_s": round(tsplit, 3),
           "split_s": {k: round(v, 4) for k, v in split.items()}, "note": NOTE})
@@ -174,6 +206,7 @@ def main():
     kernel_rows(args.iters, max(args.repeats, 5), args.sets_mib)
     if not args.skip_model:
         export_rows(args.images, args.repeats)
+        export_rows(args.images, args.repeats, refine=True)
 
 
 if __name__ == "__main__":

@@ -164,6 +164,8 @@ _SIGS = {
     "ups_segment_chunk": ([], _I),
     "ups_segment_table_words": ([], _I),
     "ups_segment_render": ([_P, _I, _I, _I, C.POINTER(_I), _P, _L, _P, _P, C.c_double, _P, _P, _P, _P, _P], C.c_int),
+    "ups_segment_guide": ([_P, _I, _I, C.POINTER(_I), _P, _L, _P, _P], C.c_int),
+    "ups_segment_render_guided": ([_P, _I, _I, _I, C.POINTER(_I), _P, _L, _P, _P, _P, _I, _P, C.c_double, _P, _P, _P, _P, _P], C.c_int),
     "ups_part_knn_tile": ([], _I),
     "ups_part_kmeans_chunk": ([], _I),
     "ups_part_knn": ([_P, _P, _I, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P], C.c_int),

@@ -239,13 +239,15 @@ class TrainModel(object):
 
     @torch.no_grad()
     def export_segments(self, views, sizes, sources=None, outputs=("labels", "overlay"), alpha=0.5, colors=None, maps=None,
-                        after_launch=None):
+                        after_launch=None, refine=None):
         """Part maps of `views` [n,S,S,3] rendered at their own sizes: one ``segment_soft`` and ONE ups_segment_render launch
         (``ops.segment_render``: label = first maximal part of the bilinearly resampled soft map, decided in fp64).
         sizes [(h_i, w_i)]; sources: None or n uint8 [h_i,w_i,3] images the overlay blends with (weight 1 - alpha);
         outputs: any of labels / overlay / confidence; colors uint8 [P,3] (default: the palette of the training image logs).
         maps: the (hard, soft) of an earlier ``segment_soft(views)`` (the pass is then not run again); after_launch: called once the
         kernel is launched and before the copies are queued (a profiler's lap).
+        refine: None, or {"radius": R, "sigma": sigma}: the edge-aware route of ``ops.segment_render`` (joint bilateral upsampling
+        guided by `sources`, which are then required and uploaded also when no overlay is wanted).
         The per-part pixel counts are always taken.  The planes are copied into pinned host buffers on a side stream behind an event
         (as the image logs' canvases): nothing here waits for the device.  Returns {"table", "total", "host": {name: pinned
         tensor, "counts" included}, "views": {name: [per-image host views]}, "ready": the copies' event, "soft", "hard": the device
@@ -257,8 +259,8 @@ class TrainModel(object):
         hard, soft = self.segment_soft(views) if maps is None else maps
         if colors is None and "overlay" in outputs:
             colors = IL.mask_color_bytes(IL.mask_colors01(self.n_parts))
-        res = ops.segment_render(soft, sizes, src=sources if "overlay" in outputs else None, colors=colors, alpha=alpha,
-                                 want=outputs + ("counts",))
+        res = ops.segment_render(soft, sizes, src=sources if "overlay" in outputs or refine is not None else None, colors=colors,
+                                 alpha=alpha, want=outputs + ("counts",), refine=refine)
         if after_launch is not None:
             after_launch()
         if self._seg_stream is None:

@@ -2005,13 +2005,54 @@ def segment_pack_sources(sources, table, total):
     return host
 
 
-def segment_render(soft, sizes, src=None, colors=None, alpha=0.5, want=("labels",), out=None):
+SEGMENT_RANGE = 766             # entries of the range table of the guided kernel: L1 distances 0 .. 3 * 255
+SEGMENT_MAX_RADIUS = 3
+
+
+def segment_range_table(sigma):
+    """The range weights of the edge-aware refinement: NumPy float64 [766],
+    wr[d] = max(exp(-(d/3)^2 / (2 sigma^2)), 2^-64) for the L1 distance d = 0 .. 765 of two RGB bytes triples; sigma > 0 in uint8
+    levels of mean absolute channel difference.  The floor keeps every denominator of the kernel positive.  Host arithmetic only."""
+    import numpy as np
+    sigma = float(sigma)
+    if not sigma > 0.0 or sigma == float("inf"):
+        raise L.UpsError("segment_range_table: a finite sigma > 0 (got {!r})".format(sigma))
+    d = np.arange(SEGMENT_RANGE, dtype=np.float64) / 3.0
+    return np.maximum(np.exp(-(d * d) / (2.0 * (sigma * sigma))), 2.0 ** -64)
+
+
+def _segment_packed_src(src, total):
+    if not torch.is_tensor(src) or not src.is_cuda or src.dtype != torch.uint8 or tuple(src.shape) != (total, 3):
+        raise L.UpsError("segment_render: packed sources uint8 [{},3] on the device expected (got {})".format(
+            total, (tuple(src.shape), src.dtype) if torch.is_tensor(src) else type(src)))
+    return src.contiguous()
+
+
+def segment_guide(src_packed, table, total, S, table_dev=None):
+    """The low-resolution photographs the guided kernel compares with: uint8 [n,S,S,3] on the device, guide[i, ty, tx] = the rounded box
+    mean of the pixels of image i that tap (ty, tx) covers (ups_segment_guide; integer arithmetic, restated by tests/segrefine_ref.py).
+    src_packed: uint8 [total,3] on the device, packed by `table` (segment_table).  Asynchronous on the current stream."""
+    import numpy as np
+    table = np.ascontiguousarray(table, dtype=np.int32)
+    src_packed = _segment_packed_src(src_packed, total)
+    if table_dev is None:
+        table_dev = torch.from_numpy(table).to(src_packed.device)
+    guide = torch.empty((len(table), int(S), int(S), 3), dtype=torch.uint8, device=src_packed.device)
+    L.call("ups_segment_guide", L.ptr(src_packed), len(table), int(S), table.ctypes.data_as(C.POINTER(C.c_int32)), L.ptr(table_dev),
+           total, L.ptr(guide), L.stream())
+    return guide
+
+
+def segment_render(soft, sizes, src=None, colors=None, alpha=0.5, want=("labels",), out=None, refine=None):
     """Label maps / overlays / confidence maps / part counts of n images, image i at its own size sizes[i] = (h, w), in one launch
     (ups_segment_render; the definitions: csrc/segexport.hip, restated by tests/segexport_ref.py with equal bytes).
     soft [n,S,S,P] float32 on the device (out_parts_soft); src: None, a list of uint8 [h_i,w_i,3] images (packed here) or an already
     packed uint8 [total,3] device tensor; colors [P,3] uint8 (device tensor or array; required for the overlay); 0 <= alpha <= 1: the
     colour's weight.  want: any of SEGMENT_OUTPUTS.  out: {name: tensor} of planes to reuse (uint8 [total] / [total,3], counts int32
     [n,P] which is ADDED to); a missing plane is allocated (planes as zeros, so the alignment gaps are defined).
+    refine: None, or {"radius": R, "sigma": sigma}: the edge-aware route (needs `src`) -- one ups_segment_guide launch, then
+    ups_segment_render_guided with the range table segment_range_table(sigma) in place of ups_segment_render; the guide uint8
+    [n,S,S,3] is returned as "guide".
     Returns {"table" (NumPy), "table_dev", "total", <the wanted packed tensors>, "views": {name: [per-image views [h,w] / [h,w,3]]}}.
     Asynchronous on the current stream."""
     if not _SEGMENT_CHECKED:
@@ -2029,6 +2070,15 @@ def segment_render(soft, sizes, src=None, colors=None, alpha=0.5, want=("labels"
     n, S, _, P = soft.shape
     if len(sizes) != n:
         raise L.UpsError("segment_render: {} sizes for {} maps".format(len(sizes), n))
+    if refine is not None:
+        if not isinstance(refine, dict) or set(refine) != {"radius", "sigma"}:
+            raise L.UpsError("segment_render: refine is None or {{'radius': R, 'sigma': sigma}} (got {!r})".format(refine))
+        radius = refine["radius"]
+        if isinstance(radius, bool) or not isinstance(radius, int) or not 0 <= radius <= SEGMENT_MAX_RADIUS:
+            raise L.UpsError("segment_render: refine radius is an integer in 0 .. {} (got {!r})".format(SEGMENT_MAX_RADIUS, radius))
+        range_w = segment_range_table(refine["sigma"])
+        if src is None:
+            raise L.UpsError("segment_render: refine compares with the source images: `src` is required")
     dev = soft.device
     table, total = segment_table(sizes)
     table_dev = torch.from_numpy(table).to(dev)
@@ -2055,6 +2105,14 @@ def segment_render(soft, sizes, src=None, colors=None, alpha=0.5, want=("labels"
             raise L.UpsError("segment_render: out[{!r}] {} {} expected (got {} {})".format(k, shapes[k][1], shapes[k][0], t.dtype,
                                                                                          tuple(t.shape)))
         res[k] = t
+    if refine is not None:
+        src = _segment_packed_src(src, total)
+        res["guide"] = segment_guide(src, table, total, S, table_dev)
+        L.call("ups_segment_render_guided", L.ptr(soft), n, S, P, table.ctypes.data_as(C.POINTER(C.c_int32)), L.ptr(table_dev), total,
+               L.ptr(src), L.ptr(res["guide"]), L.ptr(torch.from_numpy(range_w).to(dev)), radius, L.ptr(colors), float(alpha),
+               L.ptr(res.get("labels")), L.ptr(res.get("overlay")), L.ptr(res.get("confidence")), L.ptr(res.get("counts")), L.stream())
+        res["views"] = {k: segment_views(res[k], table) for k in want if k != "counts"}
+        return res
     L.call("ups_segment_render", L.ptr(soft), n, S, P, table.ctypes.data_as(C.POINTER(C.c_int32)), L.ptr(table_dev), total,
            L.ptr(src.contiguous()) if src is not None else None, L.ptr(colors), float(alpha), L.ptr(res.get("labels")),
            L.ptr(res.get("overlay")), L.ptr(res.get("confidence")), L.ptr(res.get("counts")), L.stream())

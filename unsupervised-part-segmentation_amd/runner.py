@@ -368,7 +368,8 @@ SEGMENT_OUTPUTS = ("labels", "overlay", "confidence")
 
 
 def segment_options(cfg):
-    """The `segment_*` keys of a yaml, validated: {"csv", "size", "max_side", "outputs", "alpha"}.  ValueError on anything else."""
+    """The `segment_*` keys of a yaml, validated: {"csv", "size", "max_side", "outputs", "alpha"}, and with `segment_refine: bilateral`
+    also "refine": {"radius", "sigma"} (what ``export_segments`` takes).  ValueError on anything else."""
     csv_path = cfg.get("segment_csv")
     if not csv_path:
         raise ValueError("--segment: `segment_csv` (one image path per line, relative to data_root) is required")
@@ -391,7 +392,19 @@ def segment_options(cfg):
     alpha = cfg.get("segment_alpha", 0.5)
     if isinstance(alpha, bool) or not isinstance(alpha, (int, float)) or not 0.0 <= float(alpha) <= 1.0:
         raise ValueError("segment_alpha: a number in [0, 1] (got {!r})".format(alpha))
-    return {"csv": csv_path, "size": size, "max_side": int(max_side), "outputs": outputs, "alpha": float(alpha)}
+    opt = {"csv": csv_path, "size": size, "max_side": int(max_side), "outputs": outputs, "alpha": float(alpha)}
+    mode = cfg.get("segment_refine", "none")
+    if mode not in ("none", "bilateral"):
+        raise ValueError("segment_refine: none | bilateral (got {!r})".format(mode))
+    radius = cfg.get("segment_refine_radius", 1)
+    if not isinstance(radius, int) or isinstance(radius, bool) or not 0 <= radius <= 3:
+        raise ValueError("segment_refine_radius: an integer in 0 .. 3 (got {!r})".format(radius))
+    sigma = cfg.get("segment_refine_sigma", 16.0)
+    if isinstance(sigma, bool) or not isinstance(sigma, (int, float)) or not 0.0 < float(sigma) < float("inf"):
+        raise ValueError("segment_refine_sigma: a number > 0 (got {!r})".format(sigma))
+    if mode == "bilateral":
+        opt["refine"] = {"radius": int(radius), "sigma": float(sigma)}
+    return opt
 
 
 def segment_output_size(h, w, opt, S):
@@ -437,6 +450,12 @@ def segment_files(model, cfg, root, step, profile=None):
     from . import imglog as IL
     from . import ops
     opt = segment_options(cfg)
+    refine = opt.get("refine")
+    if refine is None:
+        LOG.info("--segment: segment_refine = none: labels are the arg-max of the bilinearly resampled map")
+    else:
+        LOG.info("--segment: segment_refine = bilateral (radius %d, sigma %g): labels guided by the source images", refine["radius"],
+                 refine["sigma"])
     S, B = int(cfg["spatial_size"]), int(cfg["batch_size"])
     data_root = cfg["data_root"]
     rels = _data.TransferData._read_list(opt["csv"])
@@ -470,13 +489,14 @@ def segment_files(model, cfg, root, step, profile=None):
                     LOG.warning("--segment: sources larger than segment_max_side = %d are rendered scaled down to it (first: %s, "
                                 "%d x %d -> %d x %d)", opt["max_side"], rel, img.height, img.width, h, w)
                 sizes.append((h, w))
-                if "overlay" in opt["outputs"]:
+                if "overlay" in opt["outputs"] or refine is not None:
                     sources.append(np.asarray(img if (img.height, img.width) == (h, w) else img.resize((w, h), Image.BILINEAR),
                                               dtype=np.uint8))
             t0 = lap("decode", t0)
             vt = torch.from_numpy(np.stack(views))
             if profile is None:
-                res = model.export_segments(vt, sizes, sources=sources or None, outputs=opt["outputs"], alpha=opt["alpha"], colors=palette)
+                res = model.export_segments(vt, sizes, sources=sources or None, outputs=opt["outputs"], alpha=opt["alpha"], colors=palette,
+                                            refine=refine)
             else:                           # the phases apart: the pose pass, the kernel and the copies each behind a synchronisation
                 maps = model.segment_soft(vt)
                 t0 = lap("model", t0)
@@ -487,7 +507,7 @@ def segment_files(model, cfg, root, step, profile=None):
                 t0 = lap("upload", t0)
                 laps = []
                 res = model.export_segments(vt, sizes, sources=packed, outputs=opt["outputs"], alpha=opt["alpha"],
-                                            colors=palette, maps=maps, after_launch=lambda: laps.append(lap("kernel", t0)))
+                                            colors=palette, maps=maps, after_launch=lambda: laps.append(lap("kernel", t0)), refine=refine)
                 res["ready"].synchronize()
                 lap("copies", laps[0])
             images = OrderedDict()
