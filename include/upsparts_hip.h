@@ -634,6 +634,59 @@ int ups_part_kmeans_step(const float* feat, const uint8_t* valid, int32_t N, int
                          const int32_t* prev_label, int32_t* label, double* mind, int32_t* counts, double* sums, double* inertia,
                          int32_t* changed, void* scratch, void* stream);
 
+/* ---------------------------------------------------------------- landmark regression evaluation (csrc/landmarks.hip)
+ * Part centres, a per-keypoint ridge fit from the centres to annotated keypoints, and its predictions: the evaluation the part-discovery
+ * papers report on CUB and PennAction.  The reference does not have it: the definitions here are this project's own (DESIGN.md
+ * section 8; tests/landmarks_ref.py restates all four entries in NumPy float64, and the bits are equal).  Added by name, without a new
+ * UPS_ABI_VERSION, as the entries above.  Everything is fp64 with every multiplication, addition, division and square root rounded
+ * once (no contraction), no floating-point atomics, every order of summation fixed: two calls give the same bits.
+ * ups_part_moments: mass and centre of every part of every image.
+ *   soft   [N, h, w, P] fp32  out_parts_soft;   pred [N, h, w] int64, its arg-max map, or NULL (hard and invalid are then not touched)
+ *   mass   [N, P] double = sum over the pixels of s = double(soft);   centre [N, P, 2] double = (sum s u_x / mass, sum s u_y / mass) with
+ *          u_x = double(2x + 1 - w) / double(w), u_y = double(2y + 1 - h) / double(h): pixel centres on [-1, 1], each product rounded
+ *   valid  [N, P] uint8 = mass is finite, > 0 and >= min_mass; where it is 0 the centre is (0, 0).  mass, centre, valid: written completely
+ *   hard   [N, P, 3] int32, caller-zeroed or holding earlier launches' sums: += (count, sum (2x + 1 - w), sum (2y + 1 - h)) over the
+ *          pixels with pred == p (integer atomics);  invalid [1] int32 += pixels with pred outside [0, P), which touch no sum
+ *   scratch  ups_part_moments_scratch_bytes(N, h, w, P) bytes, 8-byte aligned, caller-owned, overwritten before it is read
+ *   The float sums: one partial per block of ups_part_moments_chunk() consecutive pixels of one image (pixels past the end are zeros).
+ *   With Pp = the power of two >= P and G = chunk / Pp, group g adds its pixels g Pp .. g Pp + Pp - 1 in ascending order from 0.0,
+ *   then t[g] += t[g + s] for s = G/2, G/4 .. 1.  A second launch adds the partials in block order from 0.0 and divides.
+ *   UPS_E_UNSUPPORTED: P > 32.  UPS_E_ARG, nothing launched: a NULL soft, mass, centre, valid or scratch, pred without hard and
+ *   invalid, N, h, w or P < 1, a NaN min_mass, h w > 2^20 or h w max(h, w) > 2^31 - 1 (the integer sums of one image stay in int32),
+ *   3 P N chunks > 2^31 - 1.  ups_part_moments_scratch_bytes returns 0 for sizes the entry refuses.
+ * ups_landmark_gram: the normal equations per keypoint.  f_n = (feat[n, 0 .. D-2], 1): the kernel appends the constant itself.
+ *   feat [N, D-1] double;  target [N, K, 2] double;  vis [N, K] uint8 (a target with vis == 0 is never read: it may hold anything)
+ *   G [K, D, D] = sum_{n: vis[n, k]} f_a f_b (the full matrix; symmetric in bits), R [K, D, 2] = sum f_a target[n, k, c], cnt [K] int32 =
+ *   the visible items: all written completely.  Within a block of ups_landmark_chunk() items the sum runs over ascending n from 0.0 and
+ *   SKIPS the invisible items; the block partials go to scratch (ups_landmark_gram_scratch_bytes(N, D, K)) and a second launch adds them
+ *   in block order from 0.0.
+ * ups_landmark_solve: W [K, D, 2] double, written completely: (G_k + lambda diag(1, .., 1, 0)) W_k = R_k, the bias row not penalised
+ *   (A[a][a] = G[a][a] + lambda, a < D - 1: one rounded addition).  Cholesky by columns j = 0 .. D-1:
+ *     L[j][j] = sqrt(A[j][j] - sum_{m<j} L[j][m] L[j][m]);  L[i][j] = (A[i][j] - sum_{m<j} L[i][m] L[j][m]) / L[j][j], i > j
+ *   each a subtraction chain in ascending m that starts from A's element, each product rounded; then per coordinate c
+ *     y[i] = (R[i][c] - sum_{m<i} L[i][m] y[m]) / L[i][i]   (chain in ascending m),   i ascending
+ *     W[i][c] = (y[i] - sum_{m>i} L[m][i] W[m][c]) / L[i][i]   (chain in DESCENDING m from D-1),   i descending.
+ *   A keypoint with cnt <= 0, or with a pivot A[j][j] - sum that is not positive or not finite, gets W_k = 0 and adds 1 to the DEVICE
+ *   counter *n_singular (int32, the caller's; never reset here), as ups_tps_solve does.  One block per keypoint, one launch.
+ * ups_landmark_predict: pred [N, K, 2] = sum_a f_a W[k, a, c], over ascending a from 0.0, each product rounded (the last is 1 W).
+ *   target, vis and d2 are given together or all NULL: d2 [N, K] = dx dx + dy dy with d = pred - target where vis, -1 where not.
+ *   Both outputs are written completely.  The square root, the means and the PCK counts are the host's.
+ * D <= 65 and K <= 32, else UPS_E_UNSUPPORTED (gram, solve, predict).  UPS_E_ARG, nothing launched: a NULL required pointer (feat may
+ * be NULL at D = 1), N, D or K < 1, lambda negative or not finite, target / vis / d2 given only in part, 2 N K, N D or the scratch
+ * index past 2^31 - 1.  ups_landmark_gram_scratch_bytes returns 0 for sizes the entry refuses. */
+int32_t ups_part_moments_chunk(void);
+size_t ups_part_moments_scratch_bytes(int32_t N, int32_t h, int32_t w, int32_t P);
+int ups_part_moments(const float* soft, const int64_t* pred, int32_t N, int32_t h, int32_t w, int32_t P, double min_mass, double* mass,
+                     double* centre, uint8_t* valid, int32_t* hard, int32_t* invalid, void* scratch, void* stream);
+int32_t ups_landmark_chunk(void);
+size_t ups_landmark_gram_scratch_bytes(int32_t N, int32_t D, int32_t K);
+int ups_landmark_gram(const double* feat, const double* target, const uint8_t* vis, int32_t N, int32_t D, int32_t K, double* G, double* R,
+                      int32_t* cnt, void* scratch, void* stream);
+int ups_landmark_solve(const double* G, const double* R, const int32_t* cnt, int32_t D, int32_t K, double lambda, double* W,
+                       int32_t* n_singular, void* stream);
+int ups_landmark_predict(const double* feat, const double* W, int32_t N, int32_t D, int32_t K, const double* target, const uint8_t* vis,
+                         double* pred, double* d2, void* stream);
+
 /* ---------------------------------------------------------------- mask priors (M:652-797), fused
  * One pass over l/m per view producing the partial sums, one fused backward producing dl.
  * See csrc/priors.hip for the slot layout of `sums`. */

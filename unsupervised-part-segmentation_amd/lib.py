@@ -171,6 +171,14 @@ _SIGS = {
     "ups_part_knn": ([_P, _P, _I, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P], C.c_int),
     "ups_part_kmeans_scratch_bytes": ([_I, _I, _I, _I], _Z),
     "ups_part_kmeans_step": ([_P, _P, _I, _I, _I, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P], C.c_int),
+    "ups_part_moments_chunk": ([], _I),
+    "ups_part_moments_scratch_bytes": ([_I, _I, _I, _I], _Z),
+    "ups_part_moments": ([_P, _P, _I, _I, _I, _I, C.c_double, _P, _P, _P, _P, _P, _P, _P], C.c_int),
+    "ups_landmark_chunk": ([], _I),
+    "ups_landmark_gram_scratch_bytes": ([_I, _I, _I], _Z),
+    "ups_landmark_gram": ([_P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P], C.c_int),
+    "ups_landmark_solve": ([_P, _P, _P, _I, _I, C.c_double, _P, _P, _P], C.c_int),
+    "ups_landmark_predict": ([_P, _P, _I, _I, _I, _P, _P, _P, _P, _P], C.c_int),
     "ups_prior_sums_floats": ([_I, _I], _Z),
     "ups_prior_fwd": ([C.POINTER(PriorDesc), _P], C.c_int),
     "ups_prior_bwd": ([C.POINTER(PriorDesc), _P], C.c_int),

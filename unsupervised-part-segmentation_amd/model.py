@@ -312,6 +312,41 @@ class TrainModel(object):
         return {"feat": feat, "area": area, "out_parts_hard": hard}
 
     @torch.no_grad()
+    def part_centres(self, views, source="soft", min_part_area=0.005):
+        """views [n,S,S,3] -> {"centre" [n,P,2] float64 ((x, y) of each part's centre on [-1, 1], pixel centres at (2x + 1) / S - 1),
+        "mass" [n,P] float64, "valid" [n,P] uint8, "out_parts_hard" int64 [n,S,S]} on the device: the features of
+        ``landmarks.LandmarkRegressor``.  The same passes of 2 * batch_size images and the same padding as ``segment_soft``, one
+        ups_part_moments launch pair per pass (``ops.part_moments``; definitions: include/upsparts_hip.h).
+        source "soft": mass = the sum of out_parts_soft, centre = its mean position, valid = mass >= min_part_area * S^2.
+        source "hard": mass = the pixels of out_parts_hard equal to p, centre = sum(2x + 1 - S) / (S * count) from the kernel's integer
+        sums in float64 (one multiplication, one division), valid = count >= ceil(min_part_area * S^2) and count > 0.
+        A part that is not valid has the centre (0, 0)."""
+        if source not in ("soft", "hard"):
+            raise L.UpsError("part_centres: source is soft | hard (got {!r})".format(source))
+        B, P = int(self.config["batch_size"]), self.n_parts
+        views = torch.as_tensor(views)
+        n, S = views.shape[0], views.shape[1]
+        out = {"centre": torch.empty((n, P, 2), dtype=torch.float64, device=self.device),
+               "mass": torch.empty((n, P), dtype=torch.float64, device=self.device),
+               "valid": torch.empty((n, P), dtype=torch.uint8, device=self.device),
+               "out_parts_hard": torch.empty((n, S, S), dtype=torch.int64, device=self.device)}
+        for c0 in range(0, n, 2 * B):
+            hard, soft = self._segment(views[c0:c0 + 2 * B], True)
+            k = hard.shape[0]
+            out["out_parts_hard"][c0:c0 + k] = hard
+            r = ops.part_moments(soft, hard if source == "hard" else None, min_mass=float(min_part_area) * S * S)
+            if source == "hard":
+                cnt = r["hard"][..., 0].to(torch.float64)
+                ok = (cnt > 0) & (cnt >= float(math.ceil(float(min_part_area) * S * S)))
+                den = torch.where(ok, cnt, torch.ones_like(cnt)) * float(S)
+                centre = r["hard"][..., 1:].to(torch.float64) / den[..., None]
+                centre = torch.where(ok[..., None], centre, torch.zeros_like(centre))
+                r = {"centre": centre, "mass": cnt, "valid": ok.to(torch.uint8)}
+            for key in ("centre", "mass", "valid"):
+                out[key][c0:c0 + k] = r[key]
+        return out
+
+    @torch.no_grad()
     def decode_mixed(self, hard, feat, pose_idx, app_idx, chunk=None):
         """generated [K,S,S,3] fp32: image k has the masks hard[pose_idx[k]] and, for part p, the appearance feat[app_idx[k][p]][p].
         pose_idx [K], app_idx [K,P]: host integers.  Decoded in chunks of at most `chunk` images (default: the config's batch_size;

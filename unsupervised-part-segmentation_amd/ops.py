@@ -1961,6 +1961,102 @@ def part_kmeans_step(feat, valid, cent, prev_label=None, accumulate=True, change
     return out
 
 
+# --------------------------------------------------------------------------- landmark regression evaluation (csrc/landmarks.hip)
+PART_MOMENTS_MAX_P, LANDMARK_MAX_D, LANDMARK_MAX_K = 32, 65, 32
+
+
+def part_moments(soft, pred=None, min_mass=0.0, hard=None, invalid=None):
+    """Mass and centre of every part of every image (ups_part_moments; the definitions: include/upsparts_hip.h, restated by
+    tests/landmarks_ref.py with equal bits).  soft [N,h,w,P] float32 (out_parts_soft), P <= 32; pred [N,h,w] int64 (out_parts_hard)
+    or None.  Returns a dict: "mass" [N,P] float64, "centre" [N,P,2] float64 ((x, y) on [-1, 1]; (0, 0) where not valid), "valid"
+    [N,P] uint8 (mass finite, > 0 and >= min_mass) and, with pred, "hard" [N,P,3] int32 (+= count, sum(2x + 1 - w), sum(2y + 1 - h);
+    given or new zeros) and "invalid" [1] int32 (+= pixels with pred outside [0,P)).  No floating-point atomics: two calls give the
+    same bits.  The scratch is a fresh allocation per call (the caching allocator orders its reuse on the stream).  Asynchronous on the
+    current stream."""
+    if soft.dim() != 4 or soft.dtype != torch.float32 or soft.shape[0] == 0 or (
+            pred is not None and (pred.dtype != torch.int64 or tuple(pred.shape) != tuple(soft.shape[:3]))):
+        raise L.UpsError("part_moments: soft [N >= 1,h,w,P] float32 and pred [N,h,w] int64 or None (got {} {}{})".format(
+            tuple(soft.shape), soft.dtype, "" if pred is None else ", {} {}".format(tuple(pred.shape), pred.dtype)))
+    N, h, w, P = soft.shape
+    dev = soft.device
+    out = {"mass": torch.empty((N, P), dtype=torch.float64, device=dev), "centre": torch.empty((N, P, 2), dtype=torch.float64, device=dev),
+           "valid": torch.empty((N, P), dtype=torch.uint8, device=dev)}
+    if pred is not None:
+        out["hard"] = torch.zeros((N, P, 3), dtype=torch.int32, device=dev) if hard is None else hard
+        out["invalid"] = torch.zeros(1, dtype=torch.int32, device=dev) if invalid is None else invalid
+        if (out["hard"].dtype != torch.int32 or tuple(out["hard"].shape) != (N, P, 3) or out["invalid"].dtype != torch.int32
+                or out["invalid"].numel() != 1):
+            raise L.UpsError("part_moments: hard [{},{},3] int32 and invalid [1] int32 expected".format(N, P))
+    nbytes = L.load().ups_part_moments_scratch_bytes(N, h, w, P)
+    scratch = torch.empty(max(1, nbytes // 8), dtype=torch.float64, device=dev)
+    L.call("ups_part_moments", L.ptr(soft.contiguous()), L.ptr(None if pred is None else pred.contiguous()), N, h, w, P, float(min_mass),
+           L.ptr(out["mass"]), L.ptr(out["centre"]), L.ptr(out["valid"]), L.ptr(out.get("hard")), L.ptr(out.get("invalid")),
+           L.ptr(scratch), L.stream())
+    return out
+
+
+def _landmark_inputs(what, feat, target, vis):
+    if feat.dim() != 2 or feat.dtype != torch.float64 or feat.shape[0] == 0:
+        raise L.UpsError("{}: feat [N >= 1,D-1] float64 (got {} {})".format(what, tuple(feat.shape), feat.dtype))
+    if target is not None and (target.dim() != 3 or target.dtype != torch.float64 or target.shape[0] != feat.shape[0] or target.shape[2] != 2
+                               or target.shape[1] == 0 or vis is None or vis.dtype != torch.uint8
+                               or tuple(vis.shape) != tuple(target.shape[:2]) or target.device != feat.device or vis.device != feat.device):
+        raise L.UpsError("{}: target [{},K >= 1,2] float64 and vis [N,K] uint8 on feat's device".format(what, feat.shape[0]))
+
+
+def landmark_gram(feat, target, vis):
+    """The normal equations of the per-keypoint linear map (ups_landmark_gram).  feat [N,D-1] float64 (the kernel appends the constant
+    1), target [N,K,2] float64, vis [N,K] uint8; D <= 65, K <= 32.  Returns (G [K,D,D], R [K,D,2] float64, cnt [K] int32), sums over
+    the items where the keypoint is visible, in the fixed order the header states.  Asynchronous on the current stream."""
+    _landmark_inputs("landmark_gram", feat, target, vis)
+    N, D, K, dev = feat.shape[0], feat.shape[1] + 1, target.shape[1], feat.device
+    G = torch.empty((K, D, D), dtype=torch.float64, device=dev)
+    R = torch.empty((K, D, 2), dtype=torch.float64, device=dev)
+    cnt = torch.empty((K,), dtype=torch.int32, device=dev)
+    nbytes = L.load().ups_landmark_gram_scratch_bytes(N, D, K)
+    scratch = torch.empty(max(1, nbytes // 8), dtype=torch.float64, device=dev)
+    L.call("ups_landmark_gram", L.ptr(feat.contiguous()) if D > 1 else None, L.ptr(target.contiguous()), L.ptr(vis.contiguous()), N, D, K,
+           L.ptr(G), L.ptr(R), L.ptr(cnt), L.ptr(scratch), L.stream())
+    return G, R, cnt
+
+
+def landmark_solve(G, R, cnt, ridge, n_singular=None):
+    """W [K,D,2] float64 with (G_k + ridge diag(1, .., 1, 0)) W_k = R_k by Cholesky (ups_landmark_solve): the bias row is not penalised.
+    A keypoint with cnt = 0 or a pivot that is not positive gets W_k = 0 and adds 1 to n_singular ([1] int32 on the device: given, or
+    new zero).  Returns (W, n_singular).  Asynchronous on the current stream: nothing is read back here."""
+    if (G.dim() != 3 or G.dtype != torch.float64 or G.shape[0] == 0 or G.shape[1] != G.shape[2] or R.dtype != torch.float64
+            or tuple(R.shape) != (G.shape[0], G.shape[1], 2) or cnt.dtype != torch.int32 or tuple(cnt.shape) != (G.shape[0],)):
+        raise L.UpsError("landmark_solve: G [K,D,D], R [K,D,2] float64 and cnt [K] int32 (got {}, {}, {})".format(
+            tuple(G.shape), tuple(R.shape), tuple(cnt.shape)))
+    K, D = G.shape[0], G.shape[1]
+    if n_singular is None:
+        n_singular = torch.zeros(1, dtype=torch.int32, device=G.device)
+    if n_singular.dtype != torch.int32 or n_singular.numel() != 1:
+        raise L.UpsError("landmark_solve: n_singular [1] int32 expected")
+    W = torch.empty((K, D, 2), dtype=torch.float64, device=G.device)
+    L.call("ups_landmark_solve", L.ptr(G.contiguous()), L.ptr(R.contiguous()), L.ptr(cnt.contiguous()), D, K, float(ridge), L.ptr(W),
+           L.ptr(n_singular), L.stream())
+    return W, n_singular
+
+
+def landmark_predict(feat, W, target=None, vis=None):
+    """pred [N,K,2] = (feat, 1) W_k (ups_landmark_predict) and, with target [N,K,2] float64 and vis [N,K] uint8, d2 [N,K] float64: the
+    squared distance where the keypoint is visible, -1 where not.  Returns (pred, d2 or None).  Asynchronous on the current stream."""
+    _landmark_inputs("landmark_predict", feat, target, vis)
+    N, D = feat.shape[0], feat.shape[1] + 1
+    if W.dim() != 3 or W.dtype != torch.float64 or W.shape[0] == 0 or W.shape[1] != D or W.shape[2] != 2 or W.device != feat.device:
+        raise L.UpsError("landmark_predict: W [K >= 1,{},2] float64 on feat's device (got {} {})".format(D, tuple(W.shape), W.dtype))
+    K = W.shape[0]
+    if target is not None and target.shape[1] != K:
+        raise L.UpsError("landmark_predict: target [N,{},2] expected (got {})".format(K, tuple(target.shape)))
+    pred = torch.empty((N, K, 2), dtype=torch.float64, device=feat.device)
+    d2 = None if target is None else torch.empty((N, K), dtype=torch.float64, device=feat.device)
+    L.call("ups_landmark_predict", L.ptr(feat.contiguous()) if D > 1 else None, L.ptr(W.contiguous()), N, D, K,
+           L.ptr(None if target is None else target.contiguous()), L.ptr(None if vis is None else vis.contiguous()), L.ptr(pred), L.ptr(d2),
+           L.stream())
+    return pred, d2
+
+
 # --------------------------------------------------------------------------- segmentation export (csrc/segexport.hip)
 SEGMENT_CHUNK = 1024            # pixels per block of ups_segment_render (checked against the library on first use)
 SEGMENT_ALIGN = 16              # an image's pixel offset in the packed planes is a multiple of it

@@ -22,6 +22,10 @@ maps written as PNG files at the resolution of the source photographs (``segment
 
 ``--index <yaml> -c <ckpt>`` is the work-alike of deepfashion/code/eval/eval_02's ``make_clusters`` and more: the part-appearance codes of
 the images in ``index_csv``, their per-part nearest neighbours and k-means clusters (``index``; ``partindex.py``).
+
+``--landmarks <yaml> -c <ckpt>`` has no counterpart in the reference either: landmark regression, the score the part-discovery papers
+report on CUB and PennAction -- a linear map from the part centres to the keypoints of ``landmark_fit_csv``, its mean error and PCK on
+``landmark_test_csv`` (``landmarks``; ``landmarks.py``).
 """
 import argparse
 import importlib
@@ -125,6 +129,9 @@ def main(argv=None):
     ap.add_argument("--index", nargs="+", default=None,
                     help="index yaml(s): the part-appearance codes of the images in index_csv, their per-part nearest neighbours and "
                          "k-means clusters under <root>/index/<global_step>/")
+    ap.add_argument("--landmarks", nargs="+", default=None,
+                    help="landmark yaml(s): a per-keypoint linear map from the part centres to the keypoints of landmark_fit_csv, its "
+                         "mean error and PCK on landmark_test_csv under <root>/landmarks/<global_step>/")
     ap.add_argument("--parts", default=None, help="--transfer: comma-separated part ids taken from the column image (default: all)")
     ap.add_argument("--eval-batches", type=int, default=None, help="number of batches to evaluate (default: one epoch)")
     ap.add_argument("-c", "--checkpoint", default=None)
@@ -134,8 +141,10 @@ def main(argv=None):
     ap.add_argument("--strict-dataset", action="store_true")
     args = ap.parse_args(argv)
     if ((args.train is not None) + (args.eval is not None) + (args.transfer is not None) + (args.segment is not None)
-            + (args.index is not None) != 1):
-        ap.error("exactly one of -t / -e / --transfer / --segment / --index is required")
+            + (args.index is not None) + (args.landmarks is not None) != 1):
+        ap.error("exactly one of -t / -e / --transfer / --segment / --index / --landmarks is required")
+    if args.landmarks is not None:
+        return landmarks(args)
     if args.index is not None:
         return index(args)
     if args.segment is not None:
@@ -586,6 +595,36 @@ def index(args):
     odir = os.path.join(root, "index", str(it.global_step))
     res = partindex.index_files(model, cfg, odir)
     print("[INFO] {} images indexed into {}".format(res["index"].N, odir))
+    return dict(res, root=root, dir=odir, model=model)
+
+
+def landmarks(args):
+    """``--landmarks``: landmark regression from the part centres (``landmarks.landmark_files``; the keys and their defaults:
+    ``landmarks.LANDMARK_DEFAULTS``).  Outputs under <root>/landmarks/<global_step>/: regressor.npz, landmarks.csv, summary.yml and
+    predictions.npz.  A wrong key raises ValueError before the model is built; a missing csv or image raises FileNotFoundError, as on
+    --segment: nothing synthetic stands in.  Returns {"root", "dir", "model", "regressor", "summary", "predictions"}."""
+    from . import landmarks as LM
+    cfg = load_config(args.landmarks)
+    for kv in args.set:
+        k, v = kv.split("=", 1)
+        cfg[k] = yaml.safe_load(v)
+    cfg["test_mode"] = True
+    LM.landmark_options(cfg)        # a wrong key fails before a device is touched
+    if not cfg.get("data_root"):
+        raise ValueError("--landmarks: `data_root` is required")
+    dist_setup()
+    root = args.project or os.path.join("logs", time.strftime("%Y-%m-%dT%H-%M-%S") + "_landmarks")
+    Model, Iterator = get_obj_from_str(cfg["model"]), get_obj_from_str(cfg["iterator"])
+    model = Model(cfg)
+    it = Iterator(cfg, root, model)
+    it.initialize(args.checkpoint)
+    if args.checkpoint is None:
+        LOG.warning("--landmarks without -c: the part centres of freshly initialised weights")
+    odir = os.path.join(root, "landmarks", str(it.global_step))
+    res = LM.landmark_files(model, cfg, odir)
+    s = res["summary"]
+    print("[INFO] landmarks: {} over {} keypoints = {} (over {} visible instances = {}), {} fitted on {} images; written to {}".format(
+        s["error"], s["n_keypoints"], s["mean_error"], s["n_visible"], s["mean_error_instances"], s["n_test"], s["n_fit"], odir))
     return dict(res, root=root, dir=odir, model=model)
 
 
