@@ -821,6 +821,43 @@ int ups_tps_params(const float* uniforms, const double* base_points, int32_t K, 
                    double off_scal, double scal_var, double augm_scal, float* coord, float* vector, float* T, int32_t* n_singular,
                    int32_t n, void* stream);
 
+/* ---------------------------------------------------------------- part equivariance under TPS warps (csrc/equivariance.hip)
+ * Added without a new UPS_ABI_VERSION, as the ups_augment_* entries: no struct changed, and a binding that expects these symbols fails
+ * to load an older library by name.  The reference has no validation: the definitions here are the specification (DESIGN.md section 8;
+ * tests/equivariance_ref.py restates them in NumPy float64).
+ *
+ * ups_tps_grid: grid [n][h][w][2] fp32 = (px, py), the source PIXEL position ups_tps_warp samples for every output pixel, before its
+ *   corner clamp: the same fp32 arithmetic (phi(d2) = d2 logf(d2 + 1e-6f), px = (x_s + 1) * w * 0.5, py = (y_s + 1) * h * 0.5).
+ *   T fp32 [n][2][K+3], coord fp32 [n][K][2].  UPS_E_ARG, nothing launched: a NULL pointer, n, h or w < 1, K outside 1..32,
+ *   h * w > 2^31 - 1, n > 65535.
+ *
+ * ups_part_equivariance: do the parts of a warped image sit where the warp carried the parts of the original?
+ *   soft_a, soft_b [N, h, w, P] fp32  the soft-max maps of the originals and of the warped images (out_parts_soft)
+ *   pred_b [N, h, w] int64   the arg-max map of the warped images as segment_soft returned it: taken, not recomputed, for the reason
+ *          ups_part_confusion gives
+ *   grid   [N, h, w, 2] fp32 (px, py) per pixel of the warped image (ups_tps_grid)
+ *   Pixel (y, x) of image i is INSIDE iff px and py are finite and 0 <= px <= w - 1, 0 <= py <= h - 1.  A pixel that is not inside
+ *   touches nothing.  For an inside pixel, in fp64, every operation rounded once (no contraction):
+ *     X = (double)px, x0 = floor(X), fx = X - x0, x1 = min(x0 + 1, w - 1); Y, y0, fy, y1 likewise
+ *     top_p = (1 - fx) * a[y0][x0][p] + fx * a[y0][x1][p];   bot_p the same on row y1;   v_p = (1 - fy) * top_p + fy * bot_p
+ *     la = the first maximal p of v;   lb = pred_b
+ *   If some v_p or soft_b value of the pixel is NaN, or lb is outside [0, P): *invalid += 1 and the pixel touches nothing else.
+ *   Otherwise counts[i][la][lb] += 1 and t = 0.5 * sum_p |v_p - (double)b_p| (p ascending from 0.0): the total variation between
+ *   the two part distributions at the pixel.
+ *   counts [N, P, P] int32, caller-zeroed or holding earlier launches' counts: the kernel only adds (integer atomics)
+ *   invalid [1] int32
+ *   tv     double [N], written completely: the sum of t over image i's counted pixels, from per-block partials (one per chunk of
+ *          ups_part_equivariance_chunk() pixels) added in index order by a second launch; no floating-point atomics: two calls give
+ *          the same bits
+ *   scratch  ups_part_equivariance_scratch_bytes(N, h * w) bytes, 8-byte aligned, caller-owned, overwritten
+ * P > 32: UPS_E_UNSUPPORTED (evalutil.equivariance_host computes the same on the host).  UPS_E_ARG, nothing launched: a NULL pointer,
+ * N, h, w or P < 1, h * w > 2^31 - 1, N * chunks > 2^31 - 1 (then ups_part_equivariance_scratch_bytes returns 0). */
+int ups_tps_grid(const float* T, const float* coord, float* grid, int32_t n, int32_t h, int32_t w, int32_t K, void* stream);
+int32_t ups_part_equivariance_chunk(void);
+size_t ups_part_equivariance_scratch_bytes(int32_t N, int64_t HW);
+int ups_part_equivariance(const float* soft_a, const float* soft_b, const int64_t* pred_b, const float* grid, int32_t N, int32_t h,
+                          int32_t w, int32_t P, int32_t* counts, int32_t* invalid, double* tv, void* scratch, void* stream);
+
 /* ---------------------------------------------------------------- Gaussian renderers (N:1639-1702, N:1976-2021)
  * tf_hm: P_xy [B][K][2], stddev [B][K][2] on the integer pixel grid (x,y order) -> heat [B,h,w,K] */
 int ups_gauss_hm(const float* pts, const float* stddev, float* out, int32_t B, int32_t h, int32_t w, int32_t K, void* stream);

@@ -19,6 +19,10 @@ DATA_ON_DEVICE = {"data_on_device": False, "data_cache": None, "data_on_device_m
 DATA_AUGMENT_ON_DEVICE = {"data_augment_on_device": False}
 
 
+# the `tps_parameters` block of the shipped CUB yaml (train_cub_subset_tps.yaml); also the default warp of the `equivariance` metric
+TPS_PARAMETERS = {"scal": 0.8, "tps_scal": 0.15, "rot_scal": 0.2, "off_scal": 0.2, "scal_var": 0.1, "augm_scal": 1.0}
+
+
 def _stair(start, start_value, step_size, stair_factor, cmin, cmax):
     return {"var_type": "staircase", "options": {"start": start, "start_value": start_value,
             "step_size": step_size, "stair_factor": stair_factor, "clip_min": cmin, "clip_max": cmax}}
@@ -57,8 +61,7 @@ def cub_config(n_parts=10, batch_size=8, spatial_size=128, use_tps=False):
                "activation": "leaky_relu", "coords": True},
         "discriminator": {"activation": "leaky_relu", "coords": False},
         "use_tps": use_tps,
-        "tps_parameters": {"scal": 0.8, "tps_scal": 0.15, "rot_scal": 0.2, "off_scal": 0.2,
-                           "scal_var": 0.1, "augm_scal": 1.0},
+        "tps_parameters": dict(TPS_PARAMETERS),
     }
     return c
 

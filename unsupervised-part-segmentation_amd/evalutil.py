@@ -10,6 +10,9 @@ ups_part_confusion on the device through ``PartEvaluator``), which is all the pr
 Label-free metrics (`val_metrics` / `eval_metrics`: reconstruction, parts; no counterpart in the reference):
 ``ReconstructionEvaluator`` / ``PartUsageEvaluator`` collect the per-image sums of ups_image_metrics / ups_part_usage on the device and
 ``reconstruction_from_sums`` / ``usage_from_counts`` are the pure steps from those sums to the reported numbers.
+`equivariance`: ``EquivarianceEvaluator`` warps each view with its own thin-plate spline, runs the pose path once over originals and
+warped copies and collects ups_part_equivariance's counts; ``equivariance_from_counts`` is the pure step, ``equivariance_host`` the
+NumPy route for more than 32 parts.
 """
 import logging
 import os
@@ -449,11 +452,183 @@ class PartUsageEvaluator(object):
         return usage_from_counts(counts, sharp, self.HW, self.min_area)
 
 
-def validation_logs(rec=None, usage=None, rec_loss=None):
+# ------------------------------------------------------------------ part equivariance under thin-plate-spline warps (`equivariance`)
+def equivariance_from_counts(counts, tv, HW):
+    """counts [n,P,P] integers (counts[i,la,lb]: inside pixels of image i whose original's part, sampled where the warp took the pixel
+    from, is la and whose warped image's part is lb) and tv [n] (the per-pixel total variation summed over those pixels), both from
+    ups_part_equivariance, HW pixels per image ->
+      "valid"      sum counts / (n HW): the share of pixels whose source lies inside the image
+      "agreement"  sum_i trace(counts[i]) / sum counts
+      "iou"        [P], on the pooled table C = sum_i counts[i]: C[p,p] / (row_p + col_p - C[p,p]); -1.0 where that denominator is 0
+                   (the marker the reference's part_ious.csv uses for an absent label)
+      "miou"       the mean of iou over the parts whose denominator is positive
+      "tv"         sum tv / sum counts
+    ValueError: no image, shapes that do not match, or no counted pixel at all."""
+    counts = np.asarray(counts).astype(np.int64)
+    tv = np.asarray(tv, dtype=np.float64).reshape(-1)
+    if counts.ndim != 3 or counts.shape[0] == 0 or counts.shape[1] != counts.shape[2] or tv.shape[0] != counts.shape[0]:
+        raise ValueError("equivariance_from_counts: counts [n >= 1,P,P] and tv [n] expected (got {} and {})".format(counts.shape, tv.shape))
+    if int(HW) < 1:
+        raise ValueError("equivariance_from_counts: HW must be positive (got {})".format(HW))
+    n, total = counts.shape[0], int(counts.sum())
+    if total == 0:
+        raise ValueError("equivariance_from_counts: no pixel was counted (every source position outside the image, or invalid)")
+    C = counts.sum(axis=0)
+    diag = np.diagonal(C)
+    den = C.sum(axis=1) + C.sum(axis=0) - diag
+    iou = np.where(den > 0, diag / np.maximum(den, 1), -1.0)
+    return {"valid": float(total / (np.int64(n) * np.int64(HW))), "agreement": float(diag.sum() / total),
+            "iou": [float(v) for v in iou], "miou": float(iou[den > 0].mean()), "tv": float(tv.sum() / total)}
+
+
+def equivariance_host(soft_a, soft_b, pred_b, grid):
+    """ups_part_equivariance in NumPy float64 (the host route for P > 32; the definitions: include/upsparts_hip.h):
+    soft_a, soft_b [N,h,w,P] float32, pred_b [N,h,w] integers, grid [N,h,w,2] float32 -> (counts [N,P,P] int32, invalid, tv [N])."""
+    a, b = np.asarray(soft_a, dtype=np.float64), np.asarray(soft_b, dtype=np.float64)
+    N, h, w, P = a.shape
+    lb = np.asarray(pred_b).reshape(N, h, w).astype(np.int64)
+    g = np.asarray(grid).reshape(N, h, w, 2).astype(np.float64)
+    X, Y = g[..., 0], g[..., 1]
+    with np.errstate(invalid="ignore"):
+        inside = (X >= 0.0) & (X <= w - 1) & (Y >= 0.0) & (Y <= h - 1)           # NaN and +-inf compare false
+    X, Y = np.where(inside, X, 0.0), np.where(inside, Y, 0.0)
+    x0, y0 = np.floor(X), np.floor(Y)
+    fx, fy = (X - x0)[..., None], (Y - y0)[..., None]
+    x0, y0 = x0.astype(np.int64), y0.astype(np.int64)
+    x1, y1 = np.minimum(x0 + 1, w - 1), np.minimum(y0 + 1, h - 1)
+    i = np.arange(N).reshape(N, 1, 1)
+    with np.errstate(invalid="ignore"):
+        top = (1.0 - fx) * a[i, y0, x0] + fx * a[i, y0, x1]
+        bot = (1.0 - fx) * a[i, y1, x0] + fx * a[i, y1, x1]
+        v = (1.0 - fy) * top + fy * bot
+        acc = np.zeros((N, h, w))
+        for p in range(P):
+            acc = acc + np.abs(v[..., p] - b[..., p])
+    nan = np.isnan(v).any(axis=-1) | np.isnan(b).any(axis=-1)
+    counted = inside & ~nan & (lb >= 0) & (lb < P)
+    la = np.argmax(np.where(np.isnan(v), -np.inf, v), axis=-1)                    # the first maximal part
+    t = 0.5 * acc
+    counts, tv = np.zeros((N, P, P), dtype=np.int32), np.zeros(N)
+    for k in range(N):
+        m = counted[k]
+        counts[k] = np.bincount(la[k][m] * P + lb[k][m], minlength=P * P).reshape(P, P)
+        tv[k] = t[k][m].sum()
+    return counts, int((inside & ~counted).sum()), tv
+
+
+class EquivarianceEvaluator(object):
+    """Part equivariance under thin-plate-spline warps with the pixels left on the device.  ``update(model, views, uniforms)`` solves
+    one warp per view from its row of uniforms (``tps.tps_system``: a singular system keeps the identity transform and counts in
+    `n_singular`), warps the views (ups_tps_warp), runs ONE ``model.segment_soft`` over the originals and their warped copies together
+    -- for batch_size views one pass of the pose path -- takes the warp's own sampling positions (``ops.tps_grid``) and adds
+    ups_part_equivariance's counts and distance sums to device buffers that grow by one row per image; ``result`` makes one copy and
+    returns ``equivariance_from_counts``.  n_parts above 32 (the kernel's table) is computed by ``equivariance_host``, with one
+    logged line."""
+
+    def __init__(self, device, n_parts, tps_params, n_singular=None):
+        self.device, self.P, self.tps_params, self.n_singular = device, int(n_parts), dict(tps_params), n_singular
+        if self.P < 1:
+            raise ValueError("EquivarianceEvaluator: n_parts must be positive (got {})".format(self.P))
+        self.on_device = self.P <= 32
+        if not self.on_device:
+            LOG.info("EquivarianceEvaluator: P = %d exceeds the device table (32 x 32): counting on the host", self.P)
+        self.reset()
+
+    def reset(self):
+        import torch
+        self.HW, self._host, self._host_invalid, self._n_host = None, [], 0, 0
+        self._counts = self._tv = self._invalid = None
+        if self.on_device:
+            self._counts = _RowBuffer(self.device, self.P * self.P, torch.int32, True)
+            self._tv = _RowBuffer(self.device, 1, torch.float64, False)
+            self._invalid = torch.zeros(1, dtype=torch.int32, device=self.device)
+
+    @property
+    def n(self):
+        return self._counts.n if self.on_device else self._n_host
+
+    def maps(self, model, views, uniforms):
+        """(soft_a, soft_b, pred_b, grid) of `views` [n,S,S,3] under the warps of `uniforms` [n, tps.N_UNIFORMS]: what ``update``
+        hands to the kernel."""
+        import torch
+        from . import ops, tps
+        views = torch.as_tensor(views).to(self.device, torch.float32).contiguous()
+        n, h, w = views.shape[:3]
+        u = torch.as_tensor(uniforms).to(self.device, torch.float32)
+        if tuple(u.shape) != (n, tps.N_UNIFORMS):
+            raise ValueError("EquivarianceEvaluator: uniforms [{}, {}] expected, one row per view (got {})".format(
+                n, tps.N_UNIFORMS, tuple(u.shape)))
+        coord, _, T = tps.tps_system(u, self.tps_params, n_singular=self.n_singular)
+        warped = tps._warp(views, T, coord)
+        hard, soft = model.segment_soft(torch.cat([views, warped], 0))
+        return soft[:n], soft[n:], hard[n:], ops.tps_grid(T, coord, h, w)
+
+    def update(self, model, views, uniforms, valid=None):
+        """views [n,S,S,3] in [-1,1], uniforms [n, tps.N_UNIFORMS] in [0,1) (row i draws view i's warp); only the first `valid`
+        images count (a padded last batch)."""
+        from . import ops
+        n = len(views) if valid is None else int(valid)
+        if n == 0:
+            return
+        soft_a, soft_b, pred_b, grid = (t[:n] for t in self.maps(model, views, uniforms))
+        if soft_a.shape[-1] != self.P:
+            raise ValueError("EquivarianceEvaluator.update: maps of {} parts, {} expected".format(soft_a.shape[-1], self.P))
+        HW = int(pred_b[0].numel())
+        if self.HW is not None and HW != self.HW:
+            raise ValueError("EquivarianceEvaluator.update: maps of {} pixels after maps of {}".format(HW, self.HW))
+        self.HW = HW
+        if not self.on_device:
+            c, bad, tv = equivariance_host(soft_a.cpu().numpy(), soft_b.cpu().numpy(), pred_b.cpu().numpy(), grid.cpu().numpy())
+            self._host.append((c, tv))
+            self._host_invalid += bad
+            self._n_host += n
+            return
+        ops.part_equivariance(soft_a, soft_b, pred_b, grid, counts=self._counts.take(n).view(n, self.P, self.P), invalid=self._invalid,
+                              tv=self._tv.take(n).view(n))
+
+    def sums(self):
+        """(counts [n,P,P] int32, tv [n] float64, invalid) as NumPy: the one copy to the host (the integers ride in the float64
+        buffer: counts <= HW < 2^31 are exact there)."""
+        import torch
+        P = self.P
+        if not self.on_device:
+            if not self._host:
+                return np.zeros((0, P, P), np.int32), np.zeros(0), 0
+            return np.concatenate([c for c, _ in self._host]), np.concatenate([t for _, t in self._host]), self._host_invalid
+        n = self.n
+        both = torch.cat([self._tv.filled().reshape(-1), self._counts.filled().reshape(-1).double(), self._invalid.double()]).cpu().numpy()
+        return both[n:-1].astype(np.int32).reshape(n, P, P), both[:n].copy(), int(both[-1])
+
+    def result(self):
+        from .lib import UpsError
+        counts, tv, invalid = self.sums()
+        if invalid != 0:
+            raise UpsError("EquivarianceEvaluator: {} pixel(s) with a NaN in a part map or a part id outside [0, {}) were not counted"
+                           .format(invalid, self.P))
+        if self.n == 0:
+            raise ValueError("EquivarianceEvaluator.result: no image was evaluated")
+        return equivariance_from_counts(counts, tv, self.HW)
+
+
+def equivariance_uniforms(n, seed):
+    """The [n, tps.N_UNIFORMS] float32 uniforms of `val_metrics` / `eval_metrics`: equivariance, drawn once from a CPU generator
+    seeded by `val_seed`; row i belongs to image i."""
+    import torch
+    from . import tps
+    gen = torch.Generator(device="cpu")
+    gen.manual_seed(int(seed))
+    return torch.rand(int(n), tps.N_UNIFORMS, generator=gen, dtype=torch.float32)
+
+
+def validation_logs(rec=None, usage=None, rec_loss=None, equiv=None):
     """The `val/` keys of the label-free metrics: rec = ``reconstruction_from_sums`` (val/mse, val/l1, val/psnr, val/ssim), rec_loss the
     perceptual reconstruction term (val/rec), usage = ``usage_from_counts`` (val/part_area_<p>, val/parts_active, val/confidence,
-    val/entropy).  All of them sort before val/steps_done."""
+    val/entropy), equiv = ``equivariance_from_counts`` (val/equiv_agreement, val/equiv_miou, val/equiv_iou_<p>, val/equiv_tv,
+    val/equiv_valid).  All of them sort before val/steps_done."""
     logs = {}
+    if equiv is not None:
+        logs.update({"val/equiv_iou_{}".format(p): v for p, v in enumerate(equiv["iou"])})
+        logs.update({"val/equiv_" + k: equiv[k] for k in ("agreement", "miou", "tv", "valid")})
     if rec is not None:
         logs.update({"val/" + k: rec[k] for k in ("mse", "l1", "psnr", "ssim")})
     if rec_loss is not None:

@@ -196,6 +196,10 @@ _SIGS = {
     "ups_tps_warp": ([_P, _P, _P, _P, _I, _I, _I, _I, _I, _P], C.c_int),
     "ups_tps_solve": ([_P, _P, _P, _P, _I, _I, _P], C.c_int),
     "ups_tps_params": ([_P, _P, _I] + [C.c_double] * 6 + [_P, _P, _P, _P, _I, _P], C.c_int),
+    "ups_tps_grid": ([_P, _P, _P, _I, _I, _I, _I, _P], C.c_int),
+    "ups_part_equivariance_chunk": ([], _I),
+    "ups_part_equivariance_scratch_bytes": ([_I, _L], _Z),
+    "ups_part_equivariance": ([_P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P], C.c_int),
     "ups_gauss_hm": ([_P, _P, _P, _I, _I, _I, _I, _P], C.c_int),
     "ups_gauss_hm3": ([_P, _P, _P, _I, _I, _I, _I, _P], C.c_int),
     "ups_convert": ([_P, _I, _P, _I, _L, _P], C.c_int),

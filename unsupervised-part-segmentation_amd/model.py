@@ -483,7 +483,7 @@ def gram_weight_of(config, logger=None):
     return v if v > 0 else 0.0
 
 
-VAL_METRICS = ("iou", "reconstruction", "parts")
+VAL_METRICS = ("iou", "reconstruction", "parts", "equivariance")
 
 
 def validation_metrics(config, key="val_metrics", default=("iou",)):
@@ -500,6 +500,17 @@ def validation_metrics(config, key="val_metrics", default=("iou",)):
     if not v and key == "val_metrics":
         raise ValueError("val_metrics is empty: with val_freq set, list at least one of {}".format(" | ".join(VAL_METRICS)))
     return [m for m in VAL_METRICS if m in v]
+
+
+def equivariance_tps_parameters(config):
+    """The warp block of the `equivariance` metric: `val_equivariance_tps`, else the yaml's `tps_parameters` (with or without
+    `use_tps`), else the block the shipped CUB yaml carries (configs.TPS_PARAMETERS)."""
+    from .configs import TPS_PARAMETERS
+    p = config.get("val_equivariance_tps") or config.get("tps_parameters") or TPS_PARAMETERS
+    missing = [k for k in ("scal", "tps_scal", "rot_scal", "off_scal", "scal_var") if k not in p]
+    if missing:
+        raise ValueError("val_equivariance_tps / tps_parameters: missing key(s) {}".format(missing))
+    return dict(p)
 
 
 def check_validation_config(config):
@@ -520,6 +531,8 @@ def check_validation_config(config):
     if "reconstruction" in metrics and int(config.get("spatial_size", 256)) < 11:
         raise ValueError("val_metrics: reconstruction needs spatial_size >= 11, the 11 x 11 SSIM window (got {})".format(
             config.get("spatial_size")))
+    if "equivariance" in metrics:
+        equivariance_tps_parameters(config)
 
 
 class Trainer(object):
@@ -1724,13 +1737,24 @@ class Trainer(object):
             vs = _data.ValidationSet(cfg)
             ev = evalutil.PartEvaluator(self.model, int(cfg.get("eval_n_labels", 32)), lut=cfg.get("eval_label_lut"))
             self._val.update({"set": vs, "evaluator": ev})
-        if "reconstruction" in metrics or "parts" in metrics:       # the label-free metrics: one forward per chunk of B pairs
+        if "reconstruction" in metrics or "parts" in metrics or "equivariance" in metrics:
+            # the label-free metrics: one forward per chunk of B pairs (reconstruction, parts); equivariance takes the chunk's view0
             self._val["pairs"] = _data.ValidationPairs(cfg)
             if "reconstruction" in metrics:
                 self._val["rec"] = evalutil.ReconstructionEvaluator(self.device)
             if "parts" in metrics:
                 self._val["usage"] = evalutil.PartUsageEvaluator(self.device, self.model.n_parts,
                                                                  float(cfg.get("val_min_part_area", 0.005)))
+            if "equivariance" in metrics:
+                # one warp per validation image, drawn ONCE from a CPU generator seeded by `val_seed` (row i: image i) -- nothing is
+                # drawn from the trainer's generators.  Singular systems count where `use_tps` counts them.
+                if self._tps_singular is None:
+                    self._tps_singular = torch.zeros(1, dtype=torch.int32, device=self.device)
+                TPS.base_points(self.device)
+                self._val["equiv"] = evalutil.EquivarianceEvaluator(self.device, self.model.n_parts, equivariance_tps_parameters(cfg),
+                                                                    n_singular=self._tps_singular)
+                self._val["equiv_uniforms"] = evalutil.equivariance_uniforms(len(self._val["pairs"]),
+                                                                             cfg.get("val_seed", 1)).to(self.device)
 
     @torch.no_grad()
     def validate(self):
@@ -1780,17 +1804,24 @@ class Trainer(object):
         pairs feeds both evaluators.  reconstruction: `generated` against view0 -> val/mse, val/l1, val/psnr, val/ssim
         (ups_image_metrics) and val/rec, the step's own reconstruction term (``_perceptual_view`` + ``vgg.loss`` with `gram_weight`) on
         those tensors, averaged over the chunks.  parts: out_parts_soft / out_parts_hard -> val/part_area_<p>, val/parts_active,
-        val/confidence, val/entropy (ups_part_usage).  One copy to the host per evaluator, and one for val/rec."""
+        val/confidence, val/entropy (ups_part_usage).  equivariance: the chunk's view0 against its warped copy, one more pass of the pose
+        path per chunk and no forward of its own (``evalutil.EquivarianceEvaluator``) -> val/equiv_agreement, val/equiv_miou,
+        val/equiv_iou_<p>, val/equiv_tv, val/equiv_valid.  One copy to the host per evaluator, and one for val/rec."""
         from . import evalutil
         val, model = self._val, self.model
-        pairs, rec, usage = val["pairs"], val.get("rec"), val.get("usage")
-        for ev in (rec, usage):
+        pairs, rec, usage, equiv = val["pairs"], val.get("rec"), val.get("usage"), val.get("equiv")
+        for ev in (rec, usage, equiv):
             if ev is not None:
                 ev.reset()
+        B = pairs.batch_size
         pc = self._validation_perceptual() if rec is not None else None
         rec_terms = []
         for ci in range(pairs.chunks()):
             chunk = pairs.chunk_views(ci, self.device)
+            if equiv is not None:
+                equiv.update(model, chunk["view0"], val["equiv_uniforms"][ci * B:(ci + 1) * B])
+            if rec is None and usage is None:
+                continue
             out = model.forward(chunk, noise=None)
             if rec is not None:
                 gen = model.generated_act
@@ -1801,7 +1832,8 @@ class Trainer(object):
             if usage is not None:
                 usage.update(out["out_parts_soft"], out["out_parts_hard"])
         rec_loss = float(torch.cat(rec_terms).mean()) if rec_terms else None
-        return evalutil.validation_logs(rec.result() if rec is not None else None, usage.result() if usage is not None else None, rec_loss)
+        return evalutil.validation_logs(rec.result() if rec is not None else None, usage.result() if usage is not None else None, rec_loss,
+                                        equiv=equiv.result() if equiv is not None else None)
 
     def iterate(self, batch_iterator, num_steps=None, log_fn=print):
         """edflow's session loop with its hooks.  LoggingHook cadence as cub/train/log.txt:221-860 shows it (an IntervalHook whose

@@ -1896,6 +1896,65 @@ def part_usage(soft, pred, counts=None, invalid=None, sharp=None):
     return counts, invalid, sharp
 
 
+# --------------------------------------------------------------------------- part equivariance under TPS warps (csrc/equivariance.hip)
+PART_EQUIVARIANCE_CHUNK = 1024  # pixels per block of ups_part_equivariance (checked against the library on first use)
+_EQUIVARIANCE_CHECKED = []
+
+
+def tps_grid(T, coord, h, w):
+    """grid [n,h,w,2] float32 = (px, py): the source pixel position ``ups_tps_warp`` samples for every output pixel of an h x w image
+    under T [n,2,K+3], coord [n,K,2] float32 (``tps.tps_system``), in the warp kernel's own fp32 arithmetic (ups_tps_grid).
+    Asynchronous on the current stream."""
+    if (T.dim() != 3 or coord.dim() != 3 or T.dtype != torch.float32 or coord.dtype != torch.float32 or T.shape[0] == 0
+            or coord.shape[0] != T.shape[0] or coord.shape[2] != 2 or tuple(T.shape[1:]) != (2, coord.shape[1] + 3)):
+        raise L.UpsError("tps_grid: T [n >= 1,2,K+3] and coord [n,K,2] float32 (got {} {}, {} {})".format(
+            tuple(T.shape), T.dtype, tuple(coord.shape), coord.dtype))
+    n, K = coord.shape[0], coord.shape[1]
+    grid = torch.empty((n, int(h), int(w), 2), dtype=torch.float32, device=T.device)
+    L.call("ups_tps_grid", L.ptr(T.contiguous()), L.ptr(coord.contiguous()), L.ptr(grid), n, int(h), int(w), K, L.stream())
+    return grid
+
+
+def part_equivariance(soft_a, soft_b, pred_b, grid, counts=None, invalid=None, tv=None):
+    """counts[i,la,lb] += #{inside pixels of image i whose sampled original part is la and whose warped part is lb}; tv[i] = the sum
+    of the per-pixel total variation over those pixels (ups_part_equivariance; the definitions: include/upsparts_hip.h; the
+    statistics evalutil.equivariance_from_counts takes).  soft_a, soft_b [N,h,w,P] float32 (out_parts_soft of the originals and of
+    the warped images), pred_b [N,h,w] int64 (out_parts_hard of the warped images), grid [N,h,w,2] float32 (``tps_grid``), P <= 32
+    (more: L.UpsError from the C entry -- evalutil.EquivarianceEvaluator computes on the host then).  counts [N,P,P] int32 (default:
+    new zeros; given: added to), invalid [1] int32 (+= inside pixels with a NaN or a pred_b outside [0,P), counted nowhere else),
+    tv [N] float64 (written).  Asynchronous on the current stream.  Returns (counts, invalid, tv)."""
+    if not _EQUIVARIANCE_CHECKED:
+        got = L.load().ups_part_equivariance_chunk()
+        if got != PART_EQUIVARIANCE_CHUNK:
+            raise L.UpsError("the library's equivariance chunk {} differs from ops.PART_EQUIVARIANCE_CHUNK {}: rebuild".format(
+                got, PART_EQUIVARIANCE_CHUNK))
+        _EQUIVARIANCE_CHECKED.append(True)
+    if (soft_a.dim() != 4 or soft_a.dtype != torch.float32 or soft_b.dtype != torch.float32 or pred_b.dtype != torch.int64
+            or grid.dtype != torch.float32 or soft_a.shape[0] == 0 or soft_b.shape != soft_a.shape
+            or tuple(pred_b.shape) != tuple(soft_a.shape[:3]) or tuple(grid.shape) != tuple(soft_a.shape[:3]) + (2,)):
+        raise L.UpsError("part_equivariance: soft_a, soft_b [N >= 1,h,w,P] float32, pred_b [N,h,w] int64 and grid [N,h,w,2] float32 over "
+                         "the same pixels (got {} {}, {} {}, {} {}, {} {})".format(
+                             tuple(soft_a.shape), soft_a.dtype, tuple(soft_b.shape), soft_b.dtype, tuple(pred_b.shape), pred_b.dtype,
+                             tuple(grid.shape), grid.dtype))
+    N, h, w, P = soft_a.shape
+    dev = soft_a.device
+    if counts is None:
+        counts = torch.zeros((N, P, P), dtype=torch.int32, device=dev)
+    if invalid is None:
+        invalid = torch.zeros(1, dtype=torch.int32, device=dev)
+    if tv is None:
+        tv = torch.empty((N,), dtype=torch.float64, device=dev)
+    if (counts.dtype != torch.int32 or tuple(counts.shape) != (N, P, P) or invalid.dtype != torch.int32 or invalid.numel() != 1
+            or tv.dtype != torch.float64 or tv.numel() != N):
+        raise L.UpsError("part_equivariance: counts [{0},{1},{1}] int32, invalid [1] int32 and tv [{0}] float64 expected".format(N, P))
+    soft_a, soft_b, pred_b, grid = soft_a.contiguous(), soft_b.contiguous(), pred_b.contiguous(), grid.contiguous()
+    nbytes = L.load().ups_part_equivariance_scratch_bytes(N, h * w)
+    scratch = torch.empty(max(1, nbytes // 8), dtype=torch.float64, device=dev)
+    L.call("ups_part_equivariance", L.ptr(soft_a), L.ptr(soft_b), L.ptr(pred_b), L.ptr(grid), N, h, w, P, L.ptr(counts), L.ptr(invalid),
+           L.ptr(tv), L.ptr(scratch), L.stream())
+    return counts, invalid, tv
+
+
 # --------------------------------------------------------------------------- part-appearance index (csrc/partindex.hip)
 PART_KNN_MAX_K, PART_KMEANS_MAX_K = 32, 64
 

@@ -192,7 +192,8 @@ def evaluate(args):
     ``{"inputs", "outputs"}`` is pickled to <root>/eval/<global_step>/model_outputs.p; with ground-truth label maps in the
     batches (key ``gt_segmentation``) the part-IoU protocol of eval_01.py:229-383 is reported too (evalutil.py).
     ``eval_metrics: [reconstruction, parts]`` (default none) also writes metrics.yml: the label-free metrics of the trainer's
-    `val_metrics` (evalutil.ReconstructionEvaluator / PartUsageEvaluator) from the same forward passes, without the perceptual term."""
+    `val_metrics` (evalutil.ReconstructionEvaluator / PartUsageEvaluator) from the same forward passes, without the perceptual term;
+    ``equivariance`` adds evalutil.EquivarianceEvaluator's numbers on each batch's view0 (one more pose-path pass per batch)."""
     import pickle
     import numpy as np
     from . import evalutil
@@ -232,17 +233,34 @@ def evaluate(args):
     from .model import validation_metrics
     metrics = validation_metrics(cfg, "eval_metrics", ())
     if "iou" in metrics:
-        raise ValueError("eval_metrics: the part IoU is what -e writes whenever the batches carry label maps; list reconstruction | parts")
+        raise ValueError("eval_metrics: the part IoU is what -e writes whenever the batches carry label maps; list reconstruction | parts "
+                         "| equivariance")
     if "reconstruction" in metrics and int(cfg["spatial_size"]) < 11:
         raise ValueError("eval_metrics: reconstruction needs spatial_size >= 11, the 11 x 11 SSIM window")
     rec_ev = evalutil.ReconstructionEvaluator(model.device) if "reconstruction" in metrics else None
     use_ev = (evalutil.PartUsageEvaluator(model.device, model.n_parts, float(cfg.get("val_min_part_area", 0.005)))
               if "parts" in metrics else None)
+    # equivariance: every batch's view0 against its warped copy (one more pass of the pose path per batch); the uniforms of the running
+    # image index come from a CPU generator seeded by `val_seed`, drawn batch by batch in that order
+    eq_ev, eq_gen = None, None
+    if "equivariance" in metrics:
+        from .model import equivariance_tps_parameters
+        from . import tps as _tps
+        eq_ev = evalutil.EquivarianceEvaluator(model.device, model.n_parts, equivariance_tps_parameters(cfg))
+        eq_gen = torch.Generator(device="cpu")
+        eq_gen.manual_seed(int(cfg.get("val_seed", 1)))
     for bi, batch in enumerate(batches_it):
         if args.eval_batches is not None and bi >= args.eval_batches:
             break
         valid = batch.pop("valid", None)           # ragged last batch: padded to the static batch size, only `valid` rows count
         o = model.forward(batch)
+        if eq_ev is not None:
+            v0 = torch.as_tensor(batch["view0"])
+            k = len(v0) if valid is None else int(valid)
+            u = torch.rand(k, _tps.N_UNIFORMS, generator=eq_gen, dtype=torch.float32)      # rows [images so far, + k)
+            if k < len(v0):                        # the padding is warped like the last valid image and dropped
+                u = torch.cat([u, u[-1:].expand(len(v0) - k, -1)], 0)
+            eq_ev.update(model, v0, u, valid=valid)
         if rec_ev is not None:
             rec_ev.update(model.generated_act, torch.as_tensor(batch["view0"]).to(model.device, torch.float32), valid=valid)
         if use_ev is not None:
@@ -259,7 +277,8 @@ def evaluate(args):
     with open(os.path.join(odir, "model_outputs.p"), "wb") as f:
         pickle.dump(data, f)
     if metrics:
-        vals = evalutil.validation_logs(rec_ev.result() if rec_ev is not None else None, use_ev.result() if use_ev is not None else None)
+        vals = evalutil.validation_logs(rec_ev.result() if rec_ev is not None else None, use_ev.result() if use_ev is not None else None,
+                                        equiv=eq_ev.result() if eq_ev is not None else None)
         with open(os.path.join(odir, "metrics.yml"), "w") as f:       # the `val/` names of Trainer.validate without the prefix
             yaml.safe_dump({k[len("val/"):]: (int(v) if isinstance(v, int) else float(v)) for k, v in vals.items()}, f)
     if gts:
