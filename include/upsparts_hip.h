@@ -412,6 +412,13 @@ int ups_unpool_bwd(const float* hard, const float* feat, const void* g, float* g
                    int32_t dtype, int32_t B, int64_t hw, int32_t P, int32_t F, int32_t ldo, void* stream);
 /* `g_feat` must hold B*P*F floats of result followed by scratch; total = ups_unpool_bwd_floats(B,P,F). */
 size_t ups_unpool_bwd_floats(int32_t B, int32_t P, int32_t F);
+/* The route ups_unpool_bwd takes for these arguments (host code only; ups_unpool_bwd itself launches from it): out[0] form (0: the
+ * generic kernel, 1: the matrix-core kernel -- bf16, F = 64, P in 10 / 16 / 20 / 25 with ldo = round8(64 + P), hw % 128 == 0,
+ * aligned16 and UPS_UNPOOL_MFMA not 0, read at every call), out[1] blocks per image, out[2] tiles per block, out[3] pixels per
+ * tile, out[4] pixels per block, out[5] bytes of dynamic LDS.  aligned16: hard, g and g_hard are all 16-byte aligned.
+ * B, hw, P >= 1, 8 <= F <= 64, F % 8 == 0, P <= 64, ldo % 8 == 0, ldo >= F + P (and g itself 16-byte aligned in ups_unpool_bwd):
+ * UPS_E_ARG otherwise. */
+int ups_unpool_bwd_plan(int32_t dtype, int32_t B, int64_t hw, int32_t P, int32_t F, int32_t ldo, int32_t aligned16, int64_t* out);
 
 /* ---------------------------------------------------------------- training image logs (M:968-1053), csrc/canvas.hip
  * uint8 canvases of the reference's img_ops.  Every entry writes a caller-owned canvas [rows*H, cols*W, C] (C = 3 RGB, 1 gray;

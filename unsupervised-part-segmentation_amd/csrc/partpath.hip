@@ -1266,35 +1266,37 @@ extern "C" int ups_unpool_mix_fwd(const float* hard, const float* feat, const in
 // the (P, row pitch) pairs unpool_bwd_mfma_kernel is instantiated for: round8(64 + P) channels; 0: no instance
 constexpr int unpool_mfma_ld(int P) { return (P == 10 || P == 16) ? 80 : (P == 20 ? 88 : (P == 25 ? 96 : 0)); }
 
-// g_feat: caller provides B*P*F floats followed by B*UNPOOL_SLABS*P*F floats of workspace.
-extern "C" int ups_unpool_bwd(const float* hard, const float* feat, const void* g, float* g_hard, float* g_feat, int32_t dtype,
-                              int32_t B, int64_t hw, int32_t P, int32_t F, int32_t ldo, void* stream) {
-    UPS_CHECK_ARG(hard && feat && g && g_hard && g_feat && F <= 64 && F % 8 == 0 && P <= 64 && ldo >= F + P && ldo % 8 == 0);
-    hipStream_t s = (hipStream_t)stream;
-    float* partial = g_feat + (long long)B * P * F;
+// The route ups_unpool_bwd takes for a call, decided here and nowhere else (the launch below reads its numbers from this function):
+// out = {form (0: unpool_bwd_kernel, 1: unpool_bwd_mfma_kernel), blocks per image, tiles per block, pixels per tile, pixels per
+// block, bytes of dynamic LDS}.  `aligned16`: hard, g and g_hard are all 16-byte aligned.  UPS_UNPOOL_MFMA is read at every call.
+extern "C" int ups_unpool_bwd_plan(int32_t dtype, int32_t B, int64_t hw, int32_t P, int32_t F, int32_t ldo, int32_t aligned16,
+                                   int64_t* out) {
+    UPS_CHECK_ARG(out);
+    UPS_CHECK_ARG(B >= 1);
+    UPS_CHECK_ARG(hw >= 1);
+    UPS_CHECK_ARG(P >= 1);
+    UPS_CHECK_ARG(F >= 8);
+    UPS_CHECK_ARG(F <= 64 && F % 8 == 0);
+    UPS_CHECK_ARG(P <= 64);
+    UPS_CHECK_ARG(ldo >= F + P);
+    UPS_CHECK_ARG(ldo % 8 == 0);
     const size_t esz = dtype == UPS_F32 ? 4 : 2;
     {   // matrix-core form (round 5; round 6: P = 16 / 20 / 25 too): bf16 gradient, 64 features + P parts in round8(64 + P)-channel rows,
         // whole 128-pixel tiles
         const bool mf_on = ups_env_on_now("UPS_UNPOOL_MFMA");          // (read at every call: the unit test compares both forms)
-        const bool al16 = ((((uintptr_t)hard) | ((uintptr_t)g) | ((uintptr_t)g_hard)) & 15) == 0;
         const bool shape = unpool_mfma_ld(P) != 0 && ldo == unpool_mfma_ld(P);
-        if (mf_on && dtype == UPS_BF16 && shape && F == UB_F && hw % UB_TP == 0 && al16) {
+        if (mf_on && dtype == UPS_BF16 && shape && F == UB_F && hw % UB_TP == 0 && aligned16) {
             const int tiles_img = (int)(hw / UB_TP);
             // blocks per image: two per CU over the batch, a power of two dividing the tiles and the slab records
             int bpi = 1;
             while (2 * bpi <= UNPOOL_SLABS && (long long)B * bpi < 512 && tiles_img % (2 * bpi) == 0) bpi *= 2;
-            // (one record per block, `bpi` records per image: the reduction walks 8 records instead of UNPOOL_SLABS = 32)
-            const int rc = ups_pick<10, 16, 20, 25>(P, [&](auto PC) {
-                constexpr int PV = PC(), LDV = unpool_mfma_ld(PV);      // (`shape` above: ldo is this P's)
-                return ups_launch_lds<unpool_bwd_mfma_kernel<PV, LDV>>("unpool_bwd_mfma_kernel", UB<PV, LDV>::SHMEM, dim3(B, bpi), dim3(256),
-                                                                       UB<PV, LDV>::SHMEM, s, hard, feat, (const bf16*)g, g_hard, partial,
-                                                                       (long long)hw, tiles_img / bpi, 1, bpi);
+            size_t lds = 0;
+            ups_pick<10, 16, 20, 25>(P, [&](auto PC) {
+                constexpr int PV = PC();
+                lds = UB<PV, unpool_mfma_ld(PV)>::SHMEM;
+                return UPS_OK;
             });
-            if (rc != UPS_OK) return rc;
-            UPS_LAUNCH_CHECK();
-            const int total = B * P * F;
-            hipLaunchKernelGGL(unpool_feat_reduce_kernel, dim3(ups_cdiv(total, 256)), dim3(256), 0, s, partial, B, bpi, P * F, g_feat);
-            UPS_LAUNCH_CHECK();
+            out[0] = 1; out[1] = bpi; out[2] = tiles_img / bpi; out[3] = UB_TP; out[4] = (int64_t)(tiles_img / bpi) * UB_TP; out[5] = (int64_t)lds;
             return UPS_OK;
         }
     }
@@ -1308,6 +1310,39 @@ extern "C" int ups_unpool_bwd(const float* hard, const float* feat, const void* 
     const int slab_px = ups_cdiv(ups_cdiv(hw, UNPOOL_SLABS), tpx) * tpx;
     const size_t shmem = lds_bytes(tpx);
     UPS_CHECK_ARG(shmem <= 160 * 1024);
+    out[0] = 0; out[1] = UNPOOL_SLABS; out[2] = slab_px / tpx; out[3] = tpx; out[4] = slab_px; out[5] = (int64_t)shmem;
+    return UPS_OK;
+}
+
+// g_feat: caller provides B*P*F floats followed by B*UNPOOL_SLABS*P*F floats of workspace.
+extern "C" int ups_unpool_bwd(const float* hard, const float* feat, const void* g, float* g_hard, float* g_feat, int32_t dtype,
+                              int32_t B, int64_t hw, int32_t P, int32_t F, int32_t ldo, void* stream) {
+    UPS_CHECK_ARG(hard && feat && g && g_hard && g_feat);
+    UPS_CHECK_ARG((((uintptr_t)g) & 15) == 0);                 // both forms read the gradient rows as 16-byte pieces
+    const bool al16 = ((((uintptr_t)hard) | ((uintptr_t)g) | ((uintptr_t)g_hard)) & 15) == 0;
+    int64_t plan[6];
+    const int prc = ups_unpool_bwd_plan(dtype, B, hw, P, F, ldo, al16, plan);
+    if (prc != UPS_OK) return prc;
+    hipStream_t s = (hipStream_t)stream;
+    float* partial = g_feat + (long long)B * P * F;
+    if (plan[0] == 1) {
+        const int bpi = (int)plan[1], tiles_per_block = (int)plan[2];
+        // (one record per block, `bpi` records per image: the reduction walks 8 records instead of UNPOOL_SLABS = 32)
+        const int rc = ups_pick<10, 16, 20, 25>(P, [&](auto PC) {
+            constexpr int PV = PC(), LDV = unpool_mfma_ld(PV);      // (the plan's `shape`: ldo is this P's)
+            return ups_launch_lds<unpool_bwd_mfma_kernel<PV, LDV>>("unpool_bwd_mfma_kernel", UB<PV, LDV>::SHMEM, dim3(B, bpi), dim3(256),
+                                                                   UB<PV, LDV>::SHMEM, s, hard, feat, (const bf16*)g, g_hard, partial,
+                                                                   (long long)hw, tiles_per_block, 1, bpi);
+        });
+        if (rc != UPS_OK) return rc;
+        UPS_LAUNCH_CHECK();
+        const int total = B * P * F;
+        hipLaunchKernelGGL(unpool_feat_reduce_kernel, dim3(ups_cdiv(total, 256)), dim3(256), 0, s, partial, B, bpi, P * F, g_feat);
+        UPS_LAUNCH_CHECK();
+        return UPS_OK;
+    }
+    const int tpx = (int)plan[3], slab_px = (int)plan[4];
+    const size_t shmem = (size_t)plan[5];
     const dim3 grid(B, UNPOOL_SLABS);
     const int rc = dtype == UPS_F32 ? ups_launch_lds<unpool_bwd_kernel<float>>("unpool_bwd_kernel", BIG_LDS, grid, dim3(256), shmem, s, hard, feat, (const float*)g,
                                                                                g_hard, partial, (long long)hw, P, F, ldo, slab_px, tpx)

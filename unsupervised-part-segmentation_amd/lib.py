@@ -145,6 +145,7 @@ _SIGS = {
     "ups_unpool_mix_fwd": ([_P, _P, _P, _P, _P, _I, _I, _I, _I, _L, _I, _I, _I, _P], C.c_int),
     "ups_unpool_bwd": ([_P, _P, _P, _P, _P, _I, _I, _L, _I, _I, _I, _P], C.c_int),
     "ups_unpool_bwd_floats": ([_I, _I, _I], _Z),
+    "ups_unpool_bwd_plan": ([_I, _I, _L, _I, _I, _I, _I, C.POINTER(_L)], C.c_int),
     "ups_canvas_grid_side": ([_I], C.c_int),
     "ups_canvas_images": ([_P, _I, _I, _I, _I, _I, _I, _I, _P, _P], C.c_int),
     "ups_canvas_mask_rgb": ([_P, _P, _I, _P, _I, _I, _I, _I, _I, _I, _P, _P], C.c_int),
