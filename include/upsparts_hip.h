@@ -799,6 +799,64 @@ int ups_adam(float* p, const float* g, float* m, float* v, int64_t count, float 
 int ups_adam_dev(float* p, const float* g, float* m, float* v, int64_t count, const float* lr_t_dev, float beta1, float beta2,
                  float eps, float grad_scale, void* stream);
 
+/* ---------------------------------------------------------------- guarded optimizer step (csrc/stepguard.hip)
+ * What an optimizer key's gradient is like THIS step, decided and recorded on the device so that Adam can act on it without the host
+ * (and a captured HIP graph replays the decision afresh).  Added without a new UPS_ABI_VERSION, as the ups_augment_* entries were: no
+ * existing struct changed, and a binding that expects these symbols refuses an older library by name.
+ *
+ * ups_step_guard: 64 bytes, caller-owned DEVICE memory, 8-byte aligned, zeroed once by the caller; one per optimizer key.  The first five
+ * fields are rewritten by every ups_grad_guard, the other three accumulate over its calls.
+ *
+ * ups_grad_guard(g, count, grad_scale, clip_norm, skip_nonfinite, scratch, rec, max_blocks, stream): two launches.
+ *   (a) one fp64 partial and one int32 count per chunk of C = ups_grad_guard_chunk() elements of the flat fp32 bucket g (chunk c covers
+ *       elements [c C, min(count, (c + 1) C)); element e of the chunk belongs to slot e % 1024).  A slot adds (double)x * (double)x of its
+ *       elements in ascending e, from 0.0; the 1024 slots are folded f[i] = (s[i] + s[i+256]) + (s[i+512] + s[i+768]), i < 256, and the
+ *       256 values reduced by the tree `for d = 128, 64, .., 1: f[i] += f[i + d] (i < d)`; the partial is f[0].  The count is the number
+ *       of elements whose exponent bits are all ones (NaN, +inf, -inf).  16-byte loads wherever four consecutive elements of a row are
+ *       16-byte aligned, single elements in front of and behind them: the values above do not depend on the alignment of g (4 bytes
+ *       suffice), on the grid or on max_blocks (0: the default grid; n > 0: at most n blocks, each striding over the chunks).
+ *   (b) one block: t[i] = partial[i] + partial[i + 256] + ... (ascending, from 0.0), i < 256, the same tree over t -> sumsq; the counts
+ *       are added as integers -> nonfinite.  Then
+ *         norm  = sqrt(sumsq) * grad_scale                                  (fp64; grad_scale = 1 / world: the rank-averaged gradient)
+ *         scale = clip_norm > 0 ? (float)(clip_norm / max(norm, clip_norm)) : 1     (tf.clip_by_global_norm; a NaN norm gives NaN)
+ *         skip  = skip_nonfinite && nonfinite > 0
+ *         skip: skipped_total += 1, consecutive += 1;  else: consecutive = 0, and clipped_total += 1 when scale < 1.
+ *       With skip_nonfinite == 0 a non-finite gradient gives what the formulas give (an infinite norm: scale 0; a NaN norm: scale NaN
+ *       when clipping, else 1).  count == 0: sumsq = norm = 0, scale = 1, skip = 0.
+ *   No floating-point atomics: two calls give the same bits.  scratch: ups_grad_guard_scratch_bytes(count) bytes (never 0 for a count
+ *   the entry accepts), 8-byte aligned, caller-owned, overwritten.  UPS_E_ARG, nothing launched: a NULL rec or scratch, a NULL g with
+ *   count > 0, count < 0 or past 2^28 chunks, g not 4-byte aligned, scratch or rec not 8-byte aligned, clip_norm negative or NaN, a NaN
+ *   grad_scale, max_blocks < 0.
+ *
+ * ups_adam_guarded: ups_adam / ups_adam_dev (lr_t_dev NULL: the step size is lr_t, else *lr_t_dev) with the gradient
+ *   gg = (g[i] * grad_scale) * rec->scale; when rec->skip is set the whole grid returns without touching p, m, v.  Both fields are read
+ *   from device memory when the kernel runs.  One kernel body with ups_adam: {scale 1, skip 0} gives ups_adam's bits.
+ *
+ * ups_state_update_guarded: ups_state_update, except that when any of the six stats is non-finite new_state gets old_state's bits and
+ *   skipped[0] (total) and skipped[1] (consecutive) advance; otherwise ups_state_update's bits and skipped[1] = 0.  skipped: int64 [2],
+ *   DEVICE, zeroed once by the caller. */
+typedef struct ups_step_guard {
+    double sumsq;            /* this step: sum of squares of the bucket */
+    double norm;             /*            sqrt(sumsq) * grad_scale */
+    float scale;             /*            the clip factor Adam multiplies the gradient by */
+    int32_t skip;            /*            1: Adam leaves p, m, v alone */
+    int64_t nonfinite;       /*            elements that are NaN or +-inf */
+    int64_t skipped_total;   /* cumulative: steps skipped */
+    int64_t clipped_total;   /*             steps taken with scale < 1 */
+    int32_t consecutive;     /*             skipped steps in a row up to and including this one */
+    int32_t reserved[3];
+} ups_step_guard;
+int32_t ups_step_guard_bytes(void);
+int32_t ups_grad_guard_chunk(void);
+size_t ups_grad_guard_scratch_bytes(int64_t count);
+int ups_grad_guard(const float* g, int64_t count, double grad_scale, double clip_norm, int32_t skip_nonfinite, void* scratch,
+                   ups_step_guard* rec, int32_t max_blocks, void* stream);
+int ups_adam_guarded(float* p, const float* g, float* m, float* v, int64_t count, float lr_t, const float* lr_t_dev, float beta1,
+                     float beta2, float eps, float grad_scale, const ups_step_guard* rec, void* stream);
+int ups_state_update_guarded(const float* stats, const float* old_state, float* new_state, float decay, float gain,
+                             int32_t update_loa, float loa_lr, float loa_target, int32_t update_lor, float lor_lr,
+                             float lor_target, float lor_min, float lor_max, int64_t* skipped, void* stream);
+
 /* ---------------------------------------------------------------- thin-plate-spline augmentation (M:282-311)
  * Replaces eddata.utils.tps.ThinPlateSpline (un-vendored; "adapted from CompVis/unsupervised-disentangling", Y:188):
  * out[n][y][x][:] = bilinear sample of img[n] at (x_s, y_s) = T[n] @ [1, x, y, phi(|(x,y) - coord[n][i]|^2)...],

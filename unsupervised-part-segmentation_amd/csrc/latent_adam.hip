@@ -4,6 +4,7 @@
 #include <stdarg.h>
 
 #include "common.h"
+#include "optim.h"
 
 // ------------------------------------------------------------------ error plumbing
 static thread_local char g_err[512] = "";
@@ -99,19 +100,6 @@ __global__ __launch_bounds__(256) void latent_bwd_kernel(const float* __restrict
             gb[idx] = (j == i) ? dL * L - gk : dL * rs;
         }
         if (lane == 0) gb[i] = gsum + gk * pb[i];
-    }
-}
-
-__global__ void adam_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
-                            long long count, float lr_t, const float* __restrict__ lr_t_dev, float b1, float b2, float eps,
-                            float gscale) {
-    if (lr_t_dev) lr_t = *lr_t_dev;       // device scalar: lets a captured HIP graph be replayed with the step's learning rate
-    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < count; i += (long long)gridDim.x * blockDim.x) {
-        const float gg = g[i] * gscale;
-        const float mm = b1 * m[i] + (1.f - b1) * gg;
-        const float vv = b2 * v[i] + (1.f - b2) * gg * gg;
-        m[i] = mm; v[i] = vv;
-        p[i] = p[i] - lr_t * mm / (sqrtf(vv) + eps);
     }
 }
 
@@ -222,10 +210,8 @@ extern "C" int ups_adam(float* p, const float* g, float* m, float* v, int64_t co
                         float eps, float grad_scale, void* stream) {
     UPS_CHECK_ARG(p && g && m && v && count >= 0);
     if (count == 0) return UPS_OK;
-    long long grid = (count + 255) / 256;
-    if (grid > 8192) grid = 8192;
-    hipLaunchKernelGGL(adam_kernel, dim3((int)grid), dim3(256), 0, (hipStream_t)stream, p, g, m, v, (long long)count, lr_t,
-                       (const float*)nullptr, beta1, beta2, eps, grad_scale);
+    hipLaunchKernelGGL(adam_kernel<false>, dim3(ups_adam_grid(count)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, (long long)count, lr_t,
+                       (const float*)nullptr, beta1, beta2, eps, grad_scale, (const ups_step_guard*)nullptr);
     UPS_LAUNCH_CHECK();
     return UPS_OK;
 }
@@ -234,10 +220,8 @@ extern "C" int ups_adam_dev(float* p, const float* g, float* m, float* v, int64_
                             float beta2, float eps, float grad_scale, void* stream) {
     UPS_CHECK_ARG(p && g && m && v && lr_t_dev && count >= 0);
     if (count == 0) return UPS_OK;
-    long long grid = (count + 255) / 256;
-    if (grid > 8192) grid = 8192;
-    hipLaunchKernelGGL(adam_kernel, dim3((int)grid), dim3(256), 0, (hipStream_t)stream, p, g, m, v, (long long)count, 0.f, lr_t_dev,
-                       beta1, beta2, eps, grad_scale);
+    hipLaunchKernelGGL(adam_kernel<false>, dim3(ups_adam_grid(count)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, (long long)count, 0.f,
+                       lr_t_dev, beta1, beta2, eps, grad_scale, (const ups_step_guard*)nullptr);
     UPS_LAUNCH_CHECK();
     return UPS_OK;
 }
@@ -249,27 +233,9 @@ namespace {
 __global__ void state_update_kernel(const float* __restrict__ stats, const float* __restrict__ old, float* __restrict__ out,
                                     float decay, float gain, int up_loa, float loa_lr, float loa_target, int up_lor, float lor_lr,
                                     float lor_target, float lor_min, float lor_max) {
-    // every product and sum below is rounded on its own, as the torch expressions it replaces round them (the test holds it to them bit for
-    // bit).  __fmul_rn / __fadd_rn do NOT stop hipcc's contraction (their bodies are compiled under the header's fp-contract=fast: the build
-    // without packed fp32 forms fused decay * o + gain * val into v_fmac_f32, round 6); plain operators under this pragma are not fused.
-#pragma clang fp contract(off)
     const int i = threadIdx.x;
     if (i >= 9) return;
-    const float mim = stats[0], ind = stats[1], acc0 = stats[2], acc1 = stats[3], l0 = stats[4], l1 = stats[5];
-    const float o = old[i];
-    float v;
-    if (i < 7) {
-        const float val = i == 0 ? acc0 : i == 1 ? acc1 : i == 2 ? acc1 - acc0 : i == 3 ? l0 : i == 4 ? l1 : i == 5 ? mim : ind;
-        const float a = decay * o, b = gain * val;
-        v = a + b;
-    } else if (i == 7) {
-        const float d = loa_lr * (mim - loa_target);
-        v = up_loa ? fmaxf(o + d, 0.f) : o;
-    } else {
-        const float d = lor_lr * (ind - lor_target);
-        v = up_lor ? fminf(fmaxf(o + d, lor_min), lor_max) : o;
-    }
-    out[i] = v;
+    out[i] = ups_state_value(i, stats, old[i], decay, gain, up_loa, loa_lr, loa_target, up_lor, lor_lr, lor_target, lor_min, lor_max);
 }
 }  // namespace
 

@@ -79,6 +79,12 @@ class TowerLayer(C.Structure):
                 ("k", C.c_int32), ("n", C.c_int32)]
 
 
+class StepGuard(C.Structure):
+    """ups_step_guard: the 64-byte device record of one optimizer key (ups_grad_guard writes it, ups_adam_guarded reads it)."""
+    _fields_ = [("sumsq", C.c_double), ("norm", C.c_double), ("scale", C.c_float), ("skip", C.c_int32), ("nonfinite", C.c_int64),
+                ("skipped_total", C.c_int64), ("clipped_total", C.c_int64), ("consecutive", C.c_int32), ("reserved", C.c_int32 * 3)]
+
+
 _lib = None
 
 _I, _L, _F, _P, _Z = C.c_int32, C.c_int64, C.c_float, C.c_void_p, C.c_size_t
@@ -194,6 +200,12 @@ _SIGS = {
     "ups_latent_bwd": ([_P, _P, C.POINTER(_F), _P, _P, _F, _I, _I, _I, _P, _P], C.c_int),
     "ups_adam": ([_P, _P, _P, _P, _L, _F, _F, _F, _F, _F, _P], C.c_int),
     "ups_adam_dev": ([_P, _P, _P, _P, _L, _P, _F, _F, _F, _F, _P], C.c_int),
+    "ups_step_guard_bytes": ([], _I),
+    "ups_grad_guard_chunk": ([], _I),
+    "ups_grad_guard_scratch_bytes": ([_L], _Z),
+    "ups_grad_guard": ([_P, _L, C.c_double, C.c_double, _I, _P, _P, _I, _P], C.c_int),
+    "ups_adam_guarded": ([_P, _P, _P, _P, _L, _F, _P, _F, _F, _F, _F, _P, _P], C.c_int),
+    "ups_state_update_guarded": ([_P, _P, _P, _F, _F, _I, _F, _F, _I, _F, _F, _F, _F, _P, _P], C.c_int),
     "ups_tps_warp": ([_P, _P, _P, _P, _I, _I, _I, _I, _I, _P], C.c_int),
     "ups_tps_solve": ([_P, _P, _P, _P, _I, _I, _P], C.c_int),
     "ups_tps_params": ([_P, _P, _I] + [C.c_double] * 6 + [_P, _P, _P, _P, _I, _P], C.c_int),
@@ -235,6 +247,9 @@ def load():
     mine = [C.sizeof(ConvDesc), C.sizeof(WgradDesc), C.sizeof(PriorDesc), C.sizeof(PrepItem)]
     if list(sizes) != mine:
         raise UpsError("{}: descriptor struct sizes {} differ from this binding's {} (stale library?)".format(LIB_PATH, list(sizes), mine))
+    if lib.ups_step_guard_bytes() != C.sizeof(StepGuard):
+        raise UpsError("{}: ups_step_guard is {} bytes, this binding's StepGuard {} (stale library?)".format(
+            LIB_PATH, lib.ups_step_guard_bytes(), C.sizeof(StepGuard)))
     _lib = lib
     return lib
 

@@ -535,6 +535,22 @@ def check_validation_config(config):
         equivariance_tps_parameters(config)
 
 
+def step_guard_config(config):
+    """The keys of the guarded optimizer step, decided from the config alone -> (grad_clip_norm, skip_nonfinite,
+    nonfinite_max_consecutive); ValueError with the reason for a negative or non-finite `grad_clip_norm` and for a
+    `nonfinite_max_consecutive` below 1."""
+    clip = config.get("grad_clip_norm", 0.0)
+    if isinstance(clip, bool) or not isinstance(clip, (int, float)) or not math.isfinite(clip) or clip < 0:
+        raise ValueError("grad_clip_norm: a finite number >= 0 is expected, 0 = no clipping (got {!r})".format(clip))
+    skip = config.get("skip_nonfinite", False)
+    if not isinstance(skip, bool):
+        raise ValueError("skip_nonfinite: True or False is expected (got {!r})".format(skip))
+    maxc = config.get("nonfinite_max_consecutive", 10)
+    if isinstance(maxc, bool) or not isinstance(maxc, int) or maxc < 1:
+        raise ValueError("nonfinite_max_consecutive: an integer >= 1 is expected (got {!r})".format(maxc))
+    return float(clip), skip, maxc
+
+
 class Trainer(object):
     """Mirror of model.py:570-1068 plus the pieces edflow's TFBaseTrainer supplied (session loop,
     one Adam per loss key over the variables whose name contains the key, logging cadence)."""
@@ -556,7 +572,9 @@ class Trainer(object):
         # tools/pin_log.py sweeps them against the reference's training log.
         self.adam_eps = float(config.get("adam_eps", 1e-8))
         self.lr_warmup_steps = int(config.get("lr_warmup_steps", 0))       # linear ramp of lr over the first N global steps
-        self.grad_clip_norm = float(config.get("grad_clip_norm", 0.0))     # per optimizer key, global L2 norm (0 = off)
+        # grad_clip_norm: per optimizer key, global L2 norm (0 = off).  skip_nonfinite: a key whose gradient holds NaN / inf does not step
+        # (decided on the device, per key); nonfinite_max_consecutive: that many skipped steps in a row end the run
+        self.grad_clip_norm, self.skip_nonfinite, self.nonfinite_max_consecutive = step_guard_config(config)
         # `probe`: DIAGNOSTIC hooks (tools/pin_log.py, the conditional-pin test) -- never set by a shipped config:
         #   lr_scale: {optimizer key: factor}  that key alone steps with factor * lr
         #   rec_scale: s                        decoder_visualize's gradient sees priors + s * (reconstruction term), M:786-797
@@ -624,7 +642,14 @@ class Trainer(object):
         self._poisoned = None           # set when a step failed half-way through its optimizer updates (_after_failed_step)
         self._losses = OrderedDict((k, None) for k in self.loss_keys())
         self._graph_enabled = bool(config.get("hip_graph", SW.flag("UPS_GRAPH")))
-        # `log_images` (default off): the reference's img_ops (model.py:968-1053) as uint8 canvases on the steps that log scalars
+        # the guarded optimizer step: one ups_step_guard record per optimizer key and the state update's two counters, allocated ONCE at
+        # fixed addresses (never from a graph's pool: a captured step writes where guard_report reads).  Per process, from 0: checkpoints
+        # do not carry them.
+        self._guard_index = dict((k, i) for i, k in enumerate(self.loss_keys()))
+        self._guard_rec = ops.guard_records(len(self._guard_index), d)
+        self._guard_state = torch.zeros(2, dtype=torch.int64, device=d)
+        self._guard_used, self._nonfinite_warned = False, False
+        model.fp8.skip_nonfinite = self.skip_nonfinite        # `log_images` (default off): the reference's img_ops (model.py:968-1053) as uint8 canvases on the steps that log scalars
         self.log_images = bool(config.get("log_images", False))
         self._want_images = False       # set for the duration of a train_step(..., images=True)
         # `val_freq: K` with `val_csv`: the metrics of `val_metrics` (default: the part IoU) on a validation csv after every K-th step
@@ -1369,13 +1394,16 @@ class Trainer(object):
         new = dict(st)
         up_loa = bool(cfg.get("adversarial_regularization", True) and mi.get("loa_adaptive", True))
         up_lor = bool(c.var_reg and mi.get("lor_adaptive", True))
-        if STATE_KERNEL and stats.is_cuda and all(st[k].dtype == torch.float32 and st[k].device == stats.device for k in STATE_KEYS):
+        if (STATE_KERNEL or self.skip_nonfinite) and stats.is_cuda and all(st[k].dtype == torch.float32 and st[k].device == stats.device for k in STATE_KEYS):
             # one launch instead of ~30 scalar ones (they were the last thing a step enqueued, behind a drained GPU)
             old = torch.stack([st[k].reshape(()) for k in STATE_KEYS])
             vec = torch.empty_like(old)
-            L.call("ups_state_update", L.ptr(stats), L.ptr(old), L.ptr(vec), 0.99, 1.0 - 0.99, int(up_loa), mi.get("loa_lr", 4.0),
-                   (1.0 - c.MI_SLACK) * c.MI_TARGET, int(up_lor), mi.get("lor_lr", 0.05), c.MI_TARGET, mi.get("lor_min", 1.0),
-                   mi.get("lor_max", 7.5), L.stream())
+            args = (0.99, 1.0 - 0.99, int(up_loa), mi.get("loa_lr", 4.0), (1.0 - c.MI_SLACK) * c.MI_TARGET, int(up_lor),
+                    mi.get("lor_lr", 0.05), c.MI_TARGET, mi.get("lor_min", 1.0), mi.get("lor_max", 7.5))
+            if self.skip_nonfinite:     # guarded by its own stats: a non-finite statistic leaves every EMA and both multipliers as they were
+                ops.state_update_guarded(stats, old, vec, *args, self._guard_state)
+            else:
+                L.call("ups_state_update", L.ptr(stats), L.ptr(old), L.ptr(vec), *args, L.stream())
             for i, k in enumerate(STATE_KEYS):
                 if k not in ("loa", "lor") or (k == "loa" and up_loa) or (k == "lor" and up_lor):
                     new[k] = vec[i]
@@ -1547,25 +1575,53 @@ class Trainer(object):
         bank = self.model.bank
         lr = self.learning_rate()
         lr_scale = self.probe.get("lr_scale") or {}
-        if graph_lr is not None and (lr_scale or self.grad_clip_norm > 0):
-            raise NotImplementedError("probe.lr_scale / grad_clip_norm are eager-mode options (hip_graph: False)")
+        if graph_lr is not None and lr_scale:
+            raise NotImplementedError("probe.lr_scale is an eager-mode option (hip_graph: False)")
+        # the kernel route: ups_grad_guard directly before the key's Adam ON THE STREAM THIS RUNS ON (EARLY_ADAM: the
+        # weight-gradient stream), ups_adam_guarded reading the record.  Taken in graph mode and under `skip_nonfinite`, when there is
+        # something to guard; the eager torch route below stays as it was with both off.
+        guarded = self._guarded(graph_lr)
         for k in keys:
             grp = bank.groups[k]
             f = grp["flat"]
+            rec = None
+            if guarded:     # (data parallel: the bucket has been all-reduced, every rank decides alike; 1/world as in Adam)
+                rec = self._guard_rec[self._guard_index[k]]
+                ops.grad_guard(f["g"], rec, 1.0 / self.world_size, self.grad_clip_norm, self.skip_nonfinite)
+                self._guard_used = True
             if graph_lr is not None:
                 lr_t = graph_lr
             else:
                 t = grp["t"] + 1
                 lr_t = lr * lr_scale.get(k, 1.0) * math.sqrt(1.0 - self.beta2 ** t) / (1.0 - self.beta1 ** t)
-                if self.grad_clip_norm > 0:         # tf.clip_by_global_norm over the key's variables (device side, no sync)
+                if self.grad_clip_norm > 0 and not guarded:     # tf.clip_by_global_norm over the key's variables (device side, no sync)
                     gn = torch.linalg.vector_norm(f["g"]) / self.world_size
                     f["g"].mul_(torch.clamp(self.grad_clip_norm / gn.clamp_min(1e-30), max=1.0))
-            ops.adam_step(f["p"], f["g"], f["m"], f["v"], lr_t, self.beta1, self.beta2, self.adam_eps, 1.0 / self.world_size)
+            ops.adam_step(f["p"], f["g"], f["m"], f["v"], lr_t, self.beta1, self.beta2, self.adam_eps, 1.0 / self.world_size, guard=rec)
             # enqueued: this key's weights and counter have moved (for _after_failed_step, key by key).  AFTER the call: adam_step raises on
             # a rejected argument or a refused launch, i.e. with nothing enqueued; an asynchronous fault cannot be pinned to a key anyway
             if graph_lr is None:
                 grp["t"] = t
                 self.sync.stepped.add(k)
+
+    def _guarded(self, graph_lr):
+        """Does a step with this `graph_lr` run the guard kernels?  Under `skip_nonfinite` always; for `grad_clip_norm` alone only in
+        graph mode (eager clipping without `skip_nonfinite` stays on the torch route, bit for bit as before).  With both keys unset:
+        never -- the step's launches are then exactly the earlier ones."""
+        return self.skip_nonfinite or (graph_lr is not None and self.grad_clip_norm > 0)
+
+    def guard_report(self):
+        """The guard records as python numbers (synchronises): {optimizer key: {skipped, clipped, consecutive (cumulative, this
+        process, since construction), nonfinite, norm, scale (the most recent step)}, "state": {skipped, consecutive}}.  All zero
+        (scale 0.0) for a key whose guard has not run."""
+        torch.cuda.synchronize(self.device)
+        rec, out = self._guard_rec.cpu(), OrderedDict()
+        for k, i in self._guard_index.items():
+            r = ops.guard_read(rec[i])
+            out[k] = {n: r[n] for n in ("skipped", "clipped", "consecutive", "nonfinite", "norm", "scale")}
+        s = self._guard_state.cpu().tolist()
+        out["state"] = {"skipped": int(s[0]), "consecutive": int(s[1])}
+        return out
 
     def dp_wait_ms(self):       # (bench.py reports it)
         return self.sync.dp_wait_ms()
@@ -1702,6 +1758,12 @@ class Trainer(object):
             out[k] = float(v) if torch.is_tensor(v) else float(v)
         out.update(self._val_logs)      # the val/ keys of the most recent validation (`val_freq`)
         self._check_tps_singular()      # (the floats above have synchronised already)
+        if getattr(self, "_guard_used", False):     # the kernel route of the optimizer step has run: its records (cumulative counts, the last step's norm)
+            rep = self.guard_report()
+            for k in self._guard_index:
+                out["guard/skipped_" + k], out["guard/clipped_" + k] = rep[k]["skipped"], rep[k]["clipped"]
+                out["guard/grad_norm_" + k], out["guard/clip_scale_" + k] = rep[k]["norm"], rep[k]["scale"]
+            out["guard/state_skipped"] = rep["state"]["skipped"]
         return out
 
     def tps_singular_count(self):
@@ -1876,17 +1938,40 @@ class Trainer(object):
                 # the decision is made collective, so that every rank of a data-parallel run leaves together instead of the
                 # healthy ones waiting in the next all-reduce until the RCCL timeout
                 bad = [k for k, v in logs.items() if k.startswith("loss_") and not math.isfinite(v)]
-                flag = torch.tensor([1.0 if bad else 0.0], dtype=torch.float32, device=self.device)
-                D.sum_flag(flag, self.world_size, self.process_group)
-                if float(flag) > 0:
-                    raise FloatingPointError("non-finite {} at global step {} (on {} rank(s))".format(
-                        ", ".join(bad) if bad else "loss on another rank", s, int(float(flag))))
+                if getattr(self, "skip_nonfinite", False):      # (getattr: stub trainers of the host tests, as val_freq above)
+                    self._check_skipped(bad, s, log_fn)
+                else:
+                    flag = torch.tensor([1.0 if bad else 0.0], dtype=torch.float32, device=self.device)
+                    D.sum_flag(flag, self.world_size, self.process_group)
+                    if float(flag) > 0:
+                        raise FloatingPointError("non-finite {} at global step {} (on {} rank(s))".format(
+                            ", ".join(bad) if bad else "loss on another rank", s, int(float(flag))))
             # edflow CheckpointHook: the file is named after the global step the restored run continues FROM
             if ckpt_freq and self.global_step % ckpt_freq == 0:
                 self._flush_images()      # a checkpoint is reported only once the images of the steps before it are on disk
                 self._checkpoint()
         self._flush_images(close=True)
         self._checkpoint()                # final state at loop exit
+
+    def _check_skipped(self, bad, s, log_fn):
+        """`skip_nonfinite` on a step that logs: the device has kept the bad gradients out of the weights, so non-finite losses `bad` are
+        reported once per run instead of ending it; FloatingPointError once some optimizer key (or the state update) has been skipped
+        `nonfinite_max_consecutive` times in a row -- decided collectively, as the plain check is."""
+        if bad and not self._nonfinite_warned:
+            self._nonfinite_warned = True
+            msg = ("non-finite {} at global step {}: skip_nonfinite leaves the affected optimizer keys unstepped (reported once per "
+                   "run; guard/skipped_<key> counts them)".format(", ".join(bad), s))
+            if self.logger:
+                self.logger.warning(msg)
+            else:
+                log_fn("[WARNING] [Trainer]: " + msg)
+        rep = self.guard_report()
+        stuck = sorted(k for k, r in rep.items() if r["consecutive"] >= self.nonfinite_max_consecutive)
+        flag = torch.tensor([1.0 if stuck else 0.0], dtype=torch.float32, device=self.device)
+        D.sum_flag(flag, self.world_size, self.process_group)
+        if float(flag) > 0:
+            raise FloatingPointError("skip_nonfinite: {} skipped {} or more steps in a row by global step {} (on {} rank(s))".format(
+                ", ".join(stuck) if stuck else "an optimizer key on another rank", self.nonfinite_max_consecutive, s, int(float(flag))))
 
     def _checkpoint(self):
         """model.ckpt-<step> of THIS process's current state: written to a temporary name and renamed, so a file of that name

@@ -356,6 +356,7 @@ class Fp8State(object):
         # arguments of the calls: Handoff.f8_in into ops.conv, Handoff.f8_out out of it; no state here outlives a call.
         # UPS_F8_PRODUCER=0 switches the hand-off off (every eligible layer then converts its bf16 operand inside the kernel).
         self.PRODUCER = SW.flag("UPS_F8_PRODUCER")
+        self.skip_nonfinite = False # the trainer's `skip_nonfinite` key: update() keeps the scale of a slot whose maximum is not finite
         self.steps = 0              # update() calls so far (a tensor's copy starts one step after its first maximum was recorded)
         self.stats = {"fwd_f8": 0, "fwd_copy_in": 0, "fwd_copy_out": 0, "dgrad_f8": 0, "dgrad_copy_in": 0, "dgrad_copy_out": 0,
                       "wgrad_f8": 0}
@@ -379,7 +380,10 @@ class Fp8State(object):
             return
         n = self.count
         m = self.amax[:n].amax(dim=1)
-        self.scale[:n] = torch.where(m > 0, (self.fmax[:n] * self.MARGIN) / m.clamp_min(1e-30), self.scale[:n])
+        ok = m > 0
+        if self.skip_nonfinite:     # (`skip_nonfinite`: a slot whose recorded maximum is inf or NaN keeps its scale instead of taking 0 / NaN)
+            ok = ok & torch.isfinite(m)
+        self.scale[:n] = torch.where(ok, (self.fmax[:n] * self.MARGIN) / m.clamp_min(1e-30), self.scale[:n])
         self.amax[:n].zero_()
         self.steps += 1
 
@@ -2484,9 +2488,64 @@ class NoiseStream(object):
         return self.fill(torch.empty(*shape, dtype=torch.float32, device=device))
 
 
-def adam_step(p, g, m, v, lr_t, beta1, beta2, eps, grad_scale=1.0):
-    """lr_t: python float, or a 1-element fp32 device tensor (HIP-graph mode: the value is read on the device)."""
-    if torch.is_tensor(lr_t):
+# --------------------------------------------------------------------------- guarded optimizer step (csrc/stepguard.hip)
+GUARD_WORDS = 8         # a ups_step_guard record as int64 words (64 bytes)
+_GUARD_SCRATCH = {}     # (device, count) -> the slab of ups_grad_guard's per-chunk partials: one per bucket size, reused every step
+
+
+def guard_records(n, device):
+    """n zeroed ups_step_guard records, [n, GUARD_WORDS] int64 on `device`: row i is record i (``guard_read`` decodes one)."""
+    assert C.sizeof(L.StepGuard) == 8 * GUARD_WORDS
+    return torch.zeros((n, GUARD_WORDS), dtype=torch.int64, device=device)
+
+
+def guard_read(rec):
+    """One record (a [GUARD_WORDS] int64 row, device or host) as a dict of python numbers; a device row synchronises."""
+    raw = rec.detach().cpu().contiguous().numpy().tobytes()
+    s = L.StepGuard.from_buffer_copy(raw)
+    return {"sumsq": s.sumsq, "norm": s.norm, "scale": s.scale, "skip": s.skip, "nonfinite": s.nonfinite,
+            "skipped": s.skipped_total, "clipped": s.clipped_total, "consecutive": s.consecutive}
+
+
+def grad_guard(g, rec, grad_scale, clip_norm, skip_nonfinite, max_blocks=0):
+    """ups_grad_guard over the flat fp32 bucket `g` on the current stream: the key's record `rec` (a row of ``guard_records``) gets this
+    step's squared norm, norm of grad_scale * g, clip scale, non-finite count and skip decision, and its counters advance.  Nothing
+    comes back to the host.  The scratch slab is cached per (device, count): launches of one bucket size are ordered on one stream by
+    the trainer (each key's guard runs directly before its Adam)."""
+    if g.dtype != torch.float32 or not g.is_cuda or not g.is_contiguous():
+        raise L.UpsError("grad_guard: a contiguous float32 device bucket is expected (got {} {})".format(tuple(g.shape), g.dtype))
+    if rec.dtype != torch.int64 or rec.numel() != GUARD_WORDS or rec.device != g.device or not rec.is_contiguous():
+        raise L.UpsError("grad_guard: rec is one row of guard_records on the bucket's device")
+    n = g.numel()
+    key = (g.device, n)
+    scratch = _GUARD_SCRATCH.get(key)
+    if scratch is None:
+        nbytes = L.load().ups_grad_guard_scratch_bytes(n)
+        if nbytes == 0:
+            raise L.UpsError("grad_guard: {} elements are more than one call takes".format(n))
+        scratch = _GUARD_SCRATCH[key] = torch.empty(nbytes // 8, dtype=torch.float64, device=g.device)
+    L.call("ups_grad_guard", L.ptr(g), n, float(grad_scale), float(clip_norm), int(bool(skip_nonfinite)), L.ptr(scratch), L.ptr(rec),
+           int(max_blocks), L.stream())
+    return rec
+
+
+def state_update_guarded(stats, old, out, decay, gain, up_loa, loa_lr, loa_target, up_lor, lor_lr, lor_target, lor_min, lor_max, skipped):
+    """ups_state_update_guarded: `skipped` int64 [2] on the device = (total, consecutive)."""
+    assert skipped.dtype == torch.int64 and skipped.numel() == 2
+    L.call("ups_state_update_guarded", L.ptr(stats), L.ptr(old), L.ptr(out), float(decay), float(gain), int(up_loa), float(loa_lr),
+           float(loa_target), int(up_lor), float(lor_lr), float(lor_target), float(lor_min), float(lor_max), L.ptr(skipped), L.stream())
+    return out
+
+
+def adam_step(p, g, m, v, lr_t, beta1, beta2, eps, grad_scale=1.0, guard=None):
+    """lr_t: python float, or a 1-element fp32 device tensor (HIP-graph mode: the value is read on the device).  guard: the key's
+    ups_step_guard record (``grad_guard`` has just filled it on this stream): ups_adam_guarded multiplies the gradient by its clip
+    scale, or leaves p, m, v alone when its skip flag is set."""
+    if guard is not None:
+        dev_lr = torch.is_tensor(lr_t)
+        L.call("ups_adam_guarded", L.ptr(p), L.ptr(g), L.ptr(m), L.ptr(v), p.numel(), 0.0 if dev_lr else float(lr_t),
+               L.ptr(lr_t) if dev_lr else None, float(beta1), float(beta2), float(eps), float(grad_scale), L.ptr(guard), L.stream())
+    elif torch.is_tensor(lr_t):
         L.call("ups_adam_dev", L.ptr(p), L.ptr(g), L.ptr(m), L.ptr(v), p.numel(), L.ptr(lr_t), float(beta1), float(beta2),
                float(eps), float(grad_scale), L.stream())
     else:
