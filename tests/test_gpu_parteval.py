@@ -234,6 +234,33 @@ def test_segment_and_part_evaluator(precision, dev):
         ev2.result()
 
 
+class _SegmentStub(object):
+    """What PartEvaluator needs of a model: `segment` hands out prepared int64 maps on the device, one tensor per call."""
+    n_parts = 3
+
+    def __init__(self, dev, maps):
+        self.device, self.maps = dev, [torch.from_numpy(m).to(dev) for m in maps]
+
+    def segment(self, views):
+        return self.maps.pop(0)[:len(views)]
+
+
+def test_part_evaluator_grows_past_its_first_rows(dev):
+    """33 images, then 36 of 37: 69 rows cross the 64-row buffer while the kernel adds into row-offset views of it."""
+    _, E = _mods()
+    rng = np.random.RandomState(13)
+    P, G = 3, 4
+    pred = [rng.randint(0, P, (n, 4, 4)).astype(np.int64) for n in (33, 37)]
+    gt = [rng.randint(0, G, (n, 4, 4)).astype(np.uint8) for n in (33, 37)]
+    ev = E.PartEvaluator(_SegmentStub(dev, pred), G)
+    assert ev.on_device
+    ev.update(torch.zeros((33, 4, 4, 3)), gt[0])
+    ev.update(torch.zeros((37, 4, 4, 3)), gt[1], valid=36)
+    counts, invalid = ev.counts()
+    want = E.confusion_counts(np.concatenate([pred[0], pred[1][:36]]), np.concatenate([gt[0], gt[1][:36]]), P, G)
+    assert ev.n == 69 and invalid == 0 and counts.dtype == np.int32 and np.array_equal(counts, want)
+
+
 def test_runner_eval_on_device_writes_the_same_tables(dev, tmp_path):
     """`-e` over a csv dataset with label images, five images at batch 2 (a ragged last batch), with and without eval_on_device:
     iou.yml, part_ious.csv, mean_part_ios.csv and best_remapping.yml byte for byte; no model_outputs.p from the device route."""

@@ -143,6 +143,16 @@ def test_library_exports_the_index_entries():
     assert (ops.PART_KNN_MAX_K, ops.PART_KMEANS_MAX_K) == (32, 64)
 
 
+def test_kmeans_step_refuses_a_bad_changed_counter():
+    """`changed` is written as one int32: another dtype or size is refused by name, before any device pointer is formed."""
+    import torch
+    lib, ops, _, _ = _mods()
+    feat, valid, cent = torch.zeros((4, 2, 3)), torch.ones((4, 2), dtype=torch.uint8), torch.zeros((2, 2, 3), dtype=torch.float64)
+    for changed in (torch.zeros(1, dtype=torch.float32), torch.zeros(2, dtype=torch.int32)):
+        with pytest.raises(lib.UpsError, match="changed"):
+            ops.part_kmeans_step(feat, valid, cent, accumulate=False, changed=changed)
+
+
 def test_part_index_save_load_round_trip(tmp_path):
     _, _, PI, _ = _mods()
     rng = np.random.RandomState(5)

@@ -316,3 +316,33 @@ __device__ __forceinline__ void ups_amax_slot(float* slot, float m) {
 }
 
 static inline int ups_cdiv(long long a, long long b) { return (int)((a + b - 1) / b); }
+
+// The fixed-order fp64 sum of the evaluation metrics (valmetrics.hip, equivariance.hip): a thread adds its items in index order, the
+// block folds its threads with the fixed LDS tree below and writes ONE partial per block into caller-owned scratch, and a second
+// launch adds an image's partials in index order.  No floating-point atomics: two launches on the same inputs give the same bits.
+// (Not for part_moments_kernel, grad_stats_kernel / tree256, landmark_gram_finish_kernel or part_kmeans_reduce_kernel: their own
+// orders are part of the tests' bit-exact restatements.)
+// red[k * BLOCK + tid] holds thread tid's k-th value: fixed tree, result in red[k * BLOCK]
+template <int K, int BLOCK>
+__device__ __forceinline__ void ups_block_tree_sum(double* red, int tid) {
+    for (int s = BLOCK / 2; s > 0; s >>= 1) {
+        __syncthreads();
+        if (tid < s) {
+#pragma unroll
+            for (int k = 0; k < K; ++k) red[k * BLOCK + tid] += red[k * BLOCK + tid + s];
+        }
+    }
+    __syncthreads();
+}
+// out[i * K + k] = sum over j < per_image, in index order, of partials[(i * per_image + j) * K + k]
+template <int BLOCK>
+__global__ __launch_bounds__(BLOCK) void ups_sum_partials_kernel(const double* __restrict__ partials, int per_image, int K, int n_out,
+                                                                 double* __restrict__ out) {
+    const int t = blockIdx.x * BLOCK + threadIdx.x;
+    if (t >= n_out) return;
+    const int img = t / K, k = t - img * K;
+    const double* p = partials + (long long)img * per_image * K + k;
+    double s = 0.0;
+    for (int j = 0; j < per_image; ++j) s += p[(long long)j * K];
+    out[t] = s;
+}

@@ -24,7 +24,8 @@
 // plain LDS atomics cost, constant regions one atomic per wave.  (evalparts.hip's run-length form needs consecutive pixels per lane;
 // here a lane's pixels are kRound apart, so that phase 2's plane is contiguous.)
 // tv: a thread adds its pixels in round order, the block adds its threads with a fixed tree and writes ONE partial into the caller's
-// scratch, and a second launch adds an image's partials in index order.  No floating-point atomics: two calls give the same bits.
+// scratch, and a second launch adds an image's partials in index order (ups_block_tree_sum<1> and ups_sum_partials_kernel with K = 1,
+// common.h: additions only, nothing for the pragma below to act on).  No floating-point atomics: two calls give the same bits.
 // Bounds: a tap index is formed only for an inside pixel (0 <= x0 <= x1 <= w - 1, 0 <= y0 <= y1 <= h - 1, decided in fp64 on the
 // finite position); a bin only from 0 <= la < P and a pred_b compared as unsigned 64-bit against P.
 #include "common.h"
@@ -187,11 +188,7 @@ __global__ __launch_bounds__(kBlock) void part_equivariance_kernel(const float* 
     }
     if (nbad) atomicAdd(&bad, nbad);
     red[tid] = tsum;
-    for (int s = kBlock / 2; s > 0; s >>= 1) {   // fixed tree (its barriers also order the LDS atomics before the reads below)
-        __syncthreads();
-        if (tid < s) red[tid] += red[tid + s];
-    }
-    __syncthreads();
+    ups_block_tree_sum<1, kBlock>(red, tid);     // fixed tree (its barriers also order the LDS atomics before the reads below)
     if (tid == 0) partials[blockIdx.x] = red[0];
     int* out = counts + img * nb;
     for (int t = tid; t < nb; t += kBlock) {
@@ -199,17 +196,6 @@ __global__ __launch_bounds__(kBlock) void part_equivariance_kernel(const float* 
         if (v) atomicAdd(&out[t], v);
     }
     if (tid == 0 && bad) atomicAdd(invalid, bad);
-}
-
-// tv[i] = sum over j < chunks, in index order, of partials[i * chunks + j]
-__global__ __launch_bounds__(kBlock) void equivariance_sum_kernel(const double* __restrict__ partials, int chunks, int N,
-                                                                  double* __restrict__ tv) {
-    const int i = blockIdx.x * kBlock + threadIdx.x;
-    if (i >= N) return;
-    const double* p = partials + (long long)i * chunks;
-    double s = 0.0;
-    for (int j = 0; j < chunks; ++j) s += p[j];
-    tv[i] = s;
 }
 
 }  // namespace
@@ -251,7 +237,7 @@ extern "C" int ups_part_equivariance(const float* soft_a, const float* soft_b, c
     hipLaunchKernelGGL(part_equivariance_kernel, dim3((unsigned)blocks), dim3(kBlock), lds, s, soft_a, soft_b,
                        reinterpret_cast<const long long*>(pred_b), grid, h, w, P, (int)chunks, counts, invalid, part);
     UPS_LAUNCH_CHECK();
-    hipLaunchKernelGGL(equivariance_sum_kernel, dim3(ups_cdiv(N, kBlock)), dim3(kBlock), 0, s, part, (int)chunks, N, tv);
+    hipLaunchKernelGGL(ups_sum_partials_kernel<kBlock>, dim3(ups_cdiv(N, kBlock)), dim3(kBlock), 0, s, part, (int)chunks, 1, N, tv);
     UPS_LAUNCH_CHECK();
     return UPS_OK;
 }

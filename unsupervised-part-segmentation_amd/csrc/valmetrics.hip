@@ -4,9 +4,9 @@
 // Both report SUMS; the step to mse / psnr / ssim / part_area / ... is evalutil.reconstruction_from_sums / usage_from_counts on the host.
 // All floating-point arithmetic is fp64 on the source values (fp32 and bf16 are exact in fp64), and every floating-point sum has a
 // fixed order: a thread adds its items in index order, a block adds its threads with a fixed tree in LDS and writes ONE partial per
-// block into caller-owned scratch, and a second launch (sum_partials_kernel) adds an image's partials in index order.  No
-// floating-point atomics: two launches on the same inputs give the same bits.  The part counts are integers (LDS and global integer
-// atomics, as ups_part_confusion).
+// block into caller-owned scratch, and a second launch adds an image's partials in index order (ups_block_tree_sum and
+// ups_sum_partials_kernel, common.h).  No floating-point atomics: two launches on the same inputs give the same bits.  The part counts
+// are integers (LDS and global integer atomics, as ups_part_confusion).
 //
 // ups_image_metrics.  One 256-thread block per (image, kTile x kTile tile of the VALID region [H-10, W-10] of the 11 x 11 window).  Per
 // channel the block stages the tile with its 10-pixel halo in LDS as the SOURCE floats (42 x 42 values per operand, in two strips of
@@ -46,19 +46,6 @@ template <> __device__ __forceinline__ float src_float<bf16>(const bf16* p, long
 __device__ __forceinline__ double unit(float v) {           // clamp((v + 1) / 2, 0, 1) in fp64
     const double x = ((double)v + 1.0) * 0.5;
     return fmin(fmax(x, 0.0), 1.0);
-}
-
-// red[k * kBlock + tid] holds thread tid's k-th value: fixed tree, result in red[k * kBlock]
-template <int K>
-__device__ __forceinline__ void block_tree_sum(double* red, int tid) {
-    for (int s = kBlock / 2; s > 0; s >>= 1) {
-        __syncthreads();
-        if (tid < s) {
-#pragma unroll
-            for (int k = 0; k < K; ++k) red[k * kBlock + tid] += red[k * kBlock + tid + s];
-        }
-    }
-    __syncthreads();
 }
 
 template <typename TA, typename TB>
@@ -141,20 +128,8 @@ __global__ __launch_bounds__(kBlock) void image_metrics_kernel(const TA* __restr
     red[tid] = sse;
     red[kBlock + tid] = sae;
     red[2 * kBlock + tid] = ssim;
-    block_tree_sum<3>(red, tid);
+    ups_block_tree_sum<3, kBlock>(red, tid);
     if (tid < 3) partials[(long long)blockIdx.x * 3 + tid] = red[tid * kBlock];
-}
-
-// out[i * K + k] = sum over j < per_image, in index order, of partials[(i * per_image + j) * K + k]
-__global__ __launch_bounds__(kBlock) void sum_partials_kernel(const double* __restrict__ partials, int per_image, int K, int n_out,
-                                                              double* __restrict__ out) {
-    const int t = blockIdx.x * kBlock + threadIdx.x;
-    if (t >= n_out) return;
-    const int img = t / K, k = t - img * K;
-    const double* p = partials + (long long)img * per_image * K + k;
-    double s = 0.0;
-    for (int j = 0; j < per_image; ++j) s += p[(long long)j * K];
-    out[t] = s;
 }
 
 __global__ __launch_bounds__(kBlock) void part_usage_kernel(const float* __restrict__ soft, const long long* __restrict__ pred,
@@ -192,7 +167,7 @@ __global__ __launch_bounds__(kBlock) void part_usage_kernel(const float* __restr
     if (nbad) atomicAdd(&bad, nbad);
     red[tid] = conf;
     red[kBlock + tid] = ent;
-    block_tree_sum<2>(red, tid);         // (its barriers also order the LDS atomics above before the reads below)
+    ups_block_tree_sum<2, kBlock>(red, tid);     // (its barriers also order the LDS atomics above before the reads below)
     if (tid < 2) partials[(long long)blockIdx.x * 2 + tid] = red[tid * kBlock];
     if (tid < P) {
         const int v = bins[tid];
@@ -244,7 +219,8 @@ extern "C" int ups_image_metrics(const void* a, int32_t dtype_a, int32_t lda, co
     else UPS_IM_LAUNCH(bf16, bf16);
 #undef UPS_IM_LAUNCH
     UPS_LAUNCH_CHECK();
-    hipLaunchKernelGGL(sum_partials_kernel, dim3(ups_cdiv(3LL * N, kBlock)), dim3(kBlock), 0, s, part, (int)tiles, 3, 3 * N, out);
+    hipLaunchKernelGGL(ups_sum_partials_kernel<kBlock>, dim3(ups_cdiv(3LL * N, kBlock)), dim3(kBlock), 0, s, part, (int)tiles, 3, 3 * N,
+                       out);
     UPS_LAUNCH_CHECK();
     return UPS_OK;
 }
@@ -271,7 +247,8 @@ extern "C" int ups_part_usage(const float* soft, const int64_t* pred, int32_t N,
     hipLaunchKernelGGL(part_usage_kernel, dim3((unsigned)blocks), dim3(kBlock), 0, s, soft, reinterpret_cast<const long long*>(pred),
                        (long long)HW, P, (int)chunks, counts, invalid, part);
     UPS_LAUNCH_CHECK();
-    hipLaunchKernelGGL(sum_partials_kernel, dim3(ups_cdiv(2LL * N, kBlock)), dim3(kBlock), 0, s, part, (int)chunks, 2, 2 * N, sharp);
+    hipLaunchKernelGGL(ups_sum_partials_kernel<kBlock>, dim3(ups_cdiv(2LL * N, kBlock)), dim3(kBlock), 0, s, part, (int)chunks, 2, 2 * N,
+                       sharp);
     UPS_LAUNCH_CHECK();
     return UPS_OK;
 }

@@ -191,6 +191,85 @@ def evaluate_from_counts(counts, part_ids=None, labels=None, background_label=0)
             "pooled": dict(zip(pl, pooled.tolist()))}
 
 
+class _Accumulator(object):
+    """What the evaluators share: named per-image columns gathered on the device and copied to the host once.
+    columns: (name, width or row shape, torch.int32 / torch.float64, zero) each.  zero: fresh rows are zero -- a count column, which the
+    kernels ADD to; a float64 column is written completely and may start empty.  `invalid` is the [1] int32 counter of the pixels that
+    were counted nowhere.  on_device False is the host route: ``add_host`` keeps the NumPy arrays of the restatements in lists."""
+
+    def __init__(self, who, device, columns, on_device=True):
+        self.who, self.device, self.on_device = who, device, on_device
+        self.columns = [(name, (shape,) if isinstance(shape, int) else tuple(shape), dtype, zero) for name, shape, dtype, zero in columns]
+        self.reset()
+
+    def _new(self, rows, shape, dtype, zero):
+        import torch
+        return (torch.zeros if zero else torch.empty)((rows,) + shape, dtype=dtype, device=self.device)
+
+    def reset(self):
+        """Fresh buffers of 64 rows, a zero `invalid`, no image, no pixel count."""
+        import torch
+        self.n, self.HW, self.capacity, self._host, self._host_invalid = 0, None, 64, [], 0
+        self._buf = self.invalid = None
+        if self.on_device:
+            self._buf = [self._new(self.capacity, *c[1:]) for c in self.columns]
+            self.invalid = self._new(1, (), torch.int32, True)
+
+    def take(self, n):
+        """The next n rows of every column (contiguous row-offset views, in column order).  The buffers grow stream-ordered to
+        max(2 * rows, needed): the filled rows are kept and fresh count rows are zero."""
+        if self.n + n > self.capacity:
+            self.capacity = max(2 * self.capacity, self.n + n)
+            for k, c in enumerate(self.columns):
+                grown = self._new(self.capacity, *c[1:])
+                grown[:self.n] = self._buf[k][:self.n]
+                self._buf[k] = grown
+        views = tuple(b[self.n:self.n + n] for b in self._buf)
+        self.n += n
+        return views
+
+    def add_host(self, n, arrays, invalid):
+        """The host route: `arrays` (one per column) and the invalid count of n more images."""
+        self._host.append(arrays)
+        self._host_invalid += invalid
+        self.n += n
+
+    def same_pixels(self, what, HW):
+        if self.HW is not None and HW != self.HW:
+            raise ValueError("{}.update: {} of {} pixels after {} of {}".format(self.who, what, HW, what, self.HW))
+        self.HW = HW
+
+    def fetch(self):
+        """((one NumPy array [n, ..] per column, in its own dtype), invalid as int).  On the device route this is the ONE copy to the
+        host: a single .cpu() of every filled row and `invalid` concatenated.  Beside float64 columns the int32 values ride as
+        float64: every |int32| < 2^31 is exact there (a count is at most HW < 2^31)."""
+        import torch
+        np_of = {torch.int32: np.int32, torch.float64: np.float64}
+        if not self.on_device:
+            if not self._host:
+                return tuple(np.zeros((0,) + shape, np_of[dtype]) for _, shape, dtype, _ in self.columns), 0
+            return tuple(np.concatenate([a[k] for a in self._host]) for k in range(len(self.columns))), self._host_invalid
+        wide = torch.float64 if any(c[2] == torch.float64 for c in self.columns) else torch.int32
+        both = torch.cat([b[:self.n].reshape(-1).to(wide) for b in self._buf] + [self.invalid.to(wide)]).cpu().numpy()
+        out, at = [], 0
+        for _, shape, dtype, _ in self.columns:
+            size = self.n * int(np.prod(shape, dtype=np.int64))
+            out.append(both[at:at + size].astype(np_of[dtype], copy=False).reshape((self.n,) + shape))
+            at += size
+        return tuple(out), int(both[-1])
+
+    def finish(self, sentence):
+        """``fetch`` and the evaluators' common ending: UpsError "<who>: <invalid> <sentence>" when pixels were left out, ValueError
+        when no image was evaluated.  Returns the columns."""
+        from .lib import UpsError
+        columns, invalid = self.fetch()
+        if invalid != 0:
+            raise UpsError("{}: {} {}".format(self.who, invalid, sentence))
+        if self.n == 0:
+            raise ValueError("{}.result: no image was evaluated".format(self.who))
+        return columns
+
+
 class PartEvaluator(object):
     """The part-IoU protocol with the pixels left on the device: ``update`` runs ``model.segment`` (pose path only) and
     ups_part_confusion into a device buffer of counts that grows by one [P,G] row per image, without synchronising with the host;
@@ -209,15 +288,12 @@ class PartEvaluator(object):
         if not self.on_device:
             LOG.info("PartEvaluator: P = %d, G = %d exceed the device table (32 x 32): counting on the host", self.P, self.G)
         self._lut_dev = None if self.lut is None or not self.on_device else torch.from_numpy(self.lut).to(model.device)
-        self.reset()
+        self._acc = _Accumulator("PartEvaluator", model.device, [("counts", (self.P, self.G), torch.int32, True)], self.on_device)
+
+    n = property(lambda self: self._acc.n)
 
     def reset(self):
-        import torch
-        self.n, self._host, self._host_invalid = 0, [], 0
-        self._counts = self._invalid = None
-        if self.on_device:
-            self._counts = torch.zeros((64, self.P, self.G), dtype=torch.int32, device=self.model.device)
-            self._invalid = torch.zeros(1, dtype=torch.int32, device=self.model.device)
+        self._acc.reset()
 
     def _labels(self, gt):
         import torch
@@ -240,34 +316,18 @@ class PartEvaluator(object):
             raise ValueError("PartEvaluator.update: label maps {} do not match the part maps {}".format(tuple(gt.shape), tuple(pred.shape)))
         if not self.on_device:
             c, bad = confusion_counts(pred.cpu().numpy(), gt.cpu().numpy(), self.P, self.G, self.lut, return_invalid=True)
-            self._host.append(c)
-            self._host_invalid += bad
-            self.n += n
-            return
-        if self.n + n > self._counts.shape[0]:        # grow on the device (stream-ordered): the evaluated rows are kept
-            grown = torch.zeros((max(2 * self._counts.shape[0], self.n + n), self.P, self.G), dtype=torch.int32, device=self._counts.device)
-            grown[:self.n] = self._counts[:self.n]
-            self._counts = grown
+            return self._acc.add_host(n, (c,), bad)
         ops.part_confusion(pred, gt.to(pred.device, non_blocking=True), self.P, self.G, lut=self._lut_dev,
-                           counts=self._counts[self.n:self.n + n], invalid=self._invalid)
-        self.n += n
+                           counts=self._acc.take(n)[0], invalid=self._acc.invalid)
 
     def counts(self):
         """(counts [n,P,G] int32 NumPy, invalid): the one copy to the host."""
-        import torch
-        if not self.on_device:
-            return (np.concatenate(self._host) if self._host else np.zeros((0, self.P, self.G), np.int32)), self._host_invalid
-        both = torch.cat([self._counts[:self.n].reshape(-1), self._invalid]).cpu().numpy()
-        return both[:-1].reshape(self.n, self.P, self.G), int(both[-1])
+        (counts,), invalid = self._acc.fetch()
+        return counts, invalid
 
     def result(self):
-        from .lib import UpsError
-        counts, invalid = self.counts()
-        if invalid != 0:
-            raise UpsError("PartEvaluator: {} pixel(s) with a part id outside [0, {}) or a label outside [0, {}) were not counted "
-                           "(n_labels too small, or a label lut is missing)".format(invalid, self.P, self.G))
-        if self.n == 0:
-            raise ValueError("PartEvaluator.result: no image was evaluated")
+        counts, = self._acc.finish("pixel(s) with a part id outside [0, {}) or a label outside [0, {}) were not counted "
+                                   "(n_labels too small, or a label lut is missing)".format(self.P, self.G))
         return evaluate_from_counts(counts, background_label=self.background_label)
 
 
@@ -317,47 +377,22 @@ def part_usage_host(soft, pred, P):
     return counts, int(ok.size - ok.sum()), sharp
 
 
-class _RowBuffer(object):
-    """Per-image rows [n, width] in a device buffer that grows stream-ordered (as PartEvaluator's counts)."""
-
-    def __init__(self, device, width, dtype, zero):
-        self.device, self.width, self.dtype, self.zero = device, width, dtype, zero
-        self.n, self.buf = 0, self._new(64)
-
-    def _new(self, rows):
-        import torch
-        return (torch.zeros if self.zero else torch.empty)((rows, self.width), dtype=self.dtype, device=self.device)
-
-    def take(self, n):
-        """The next n rows (a view); the rows written so far are kept when the buffer has to grow."""
-        if self.n + n > self.buf.shape[0]:
-            grown = self._new(max(2 * self.buf.shape[0], self.n + n))
-            grown[:self.n] = self.buf[:self.n]
-            self.buf = grown
-        rows = self.buf[self.n:self.n + n]
-        self.n += n
-        return rows
-
-    def filled(self):
-        return self.buf[:self.n]
-
-
 class ReconstructionEvaluator(object):
     """mse / l1 / psnr / ssim of generated images against their targets with the pixels left on the device: ``update`` runs
     ups_image_metrics into a device buffer of (sse, sae, ssim_sum) rows, without synchronising with the host; ``result`` copies the
     rows once and returns ``reconstruction_from_sums``."""
 
     def __init__(self, device):
+        import torch
         self.device = device
-        self.reset()
+        self._acc = _Accumulator("ReconstructionEvaluator", device, [("rows", 3, torch.float64, False)])
+
+    n = property(lambda self: self._acc.n)
+    H = property(lambda self: None if self._acc.HW is None else self._acc.HW[0])
+    W = property(lambda self: None if self._acc.HW is None else self._acc.HW[1])
 
     def reset(self):
-        import torch
-        self._rows, self.H, self.W = _RowBuffer(self.device, 3, torch.float64, False), None, None
-
-    @property
-    def n(self):
-        return self._rows.n
+        self._acc.reset()
 
     def update(self, generated, target, valid=None):
         """generated, target [n,H,W,>=3] float32 / bfloat16 on the device, values in [-1, 1]; only the first `valid` images count."""
@@ -365,20 +400,16 @@ class ReconstructionEvaluator(object):
         n = generated.shape[0] if valid is None else int(valid)
         if n == 0:
             return
-        H, W = int(generated.shape[1]), int(generated.shape[2])
-        if self.H is not None and (H, W) != (self.H, self.W):
-            raise ValueError("ReconstructionEvaluator.update: images of {} x {} after images of {} x {}".format(H, W, self.H, self.W))
-        self.H, self.W = H, W
-        ops.image_metrics(generated[:n], target[:n], out=self._rows.take(n))
+        self._acc.same_pixels("images", (int(generated.shape[1]), int(generated.shape[2])))
+        ops.image_metrics(generated[:n], target[:n], out=self._acc.take(n)[0])
 
     def rows(self):
         """[n,3] float64 NumPy: the one copy to the host."""
-        return self._rows.filled().cpu().numpy()
+        return self._acc.fetch()[0][0]
 
     def result(self):
-        if self.n == 0:
-            raise ValueError("ReconstructionEvaluator.result: no image was evaluated")
-        return reconstruction_from_sums(self.rows(), self.H, self.W)
+        rows, = self._acc.finish("pixel(s) were not counted")  # (ups_image_metrics has no `invalid`: the refusal of n == 0 alone)
+        return reconstruction_from_sums(rows, self.H, self.W)
 
 
 class PartUsageEvaluator(object):
@@ -387,26 +418,21 @@ class PartUsageEvaluator(object):
     kernel's table) is computed by ``part_usage_host``, with one logged line."""
 
     def __init__(self, device, n_parts, min_area=0.005):
+        import torch
         self.device, self.P, self.min_area = device, int(n_parts), float(min_area)
         if self.P < 1:
             raise ValueError("PartUsageEvaluator: n_parts must be positive (got {})".format(self.P))
         self.on_device = self.P <= 32
         if not self.on_device:
             LOG.info("PartUsageEvaluator: P = %d exceeds the device table (32): counting on the host", self.P)
-        self.reset()
+        self._acc = _Accumulator("PartUsageEvaluator", device, [("counts", self.P, torch.int32, True), ("sharp", 2, torch.float64, False)],
+                                 self.on_device)
+
+    n = property(lambda self: self._acc.n)
+    HW = property(lambda self: self._acc.HW)
 
     def reset(self):
-        import torch
-        self.HW, self._host, self._host_invalid, self._n_host = None, [], 0, 0
-        self._counts = self._sharp = self._invalid = None
-        if self.on_device:
-            self._counts = _RowBuffer(self.device, self.P, torch.int32, True)
-            self._sharp = _RowBuffer(self.device, 2, torch.float64, False)
-            self._invalid = torch.zeros(1, dtype=torch.int32, device=self.device)
-
-    @property
-    def n(self):
-        return self._counts.n if self.on_device else self._n_host
+        self._acc.reset()
 
     def update(self, soft, pred, valid=None):
         """soft [n,..,P] float32 (out_parts_soft), pred [n,..] int64 (out_parts_hard); only the first `valid` images count."""
@@ -418,37 +444,20 @@ class PartUsageEvaluator(object):
         if soft.shape[-1] != self.P or tuple(soft.shape[:-1]) != tuple(pred.shape):
             raise ValueError("PartUsageEvaluator.update: soft {} and pred {} do not describe the same pixels of {} parts".format(
                 tuple(soft.shape), tuple(pred.shape), self.P))
-        HW = int(pred[0].numel())
-        if self.HW is not None and HW != self.HW:
-            raise ValueError("PartUsageEvaluator.update: maps of {} pixels after maps of {}".format(HW, self.HW))
-        self.HW = HW
+        self._acc.same_pixels("maps", int(pred[0].numel()))
         if not self.on_device:
             c, bad, s = part_usage_host(soft.cpu().numpy(), pred.cpu().numpy(), self.P)
-            self._host.append((c, s))
-            self._host_invalid += bad
-            self._n_host += n
-            return
-        ops.part_usage(soft, pred, counts=self._counts.take(n), invalid=self._invalid, sharp=self._sharp.take(n))
+            return self._acc.add_host(n, (c, s), bad)
+        counts, sharp = self._acc.take(n)
+        ops.part_usage(soft, pred, counts=counts, invalid=self._acc.invalid, sharp=sharp)
 
     def sums(self):
-        """(counts [n,P] int32, sharp [n,2] float64, invalid) as NumPy: the one copy to the host (the integers ride in the float64
-        buffer: counts <= HW < 2^31 are exact there)."""
-        import torch
-        if not self.on_device:
-            if not self._host:
-                return np.zeros((0, self.P), np.int32), np.zeros((0, 2)), 0
-            return np.concatenate([c for c, _ in self._host]), np.concatenate([s for _, s in self._host]), self._host_invalid
-        n = self.n
-        both = torch.cat([self._sharp.filled().reshape(-1), self._counts.filled().reshape(-1).double(), self._invalid.double()]).cpu().numpy()
-        return both[2 * n:-1].astype(np.int32).reshape(n, self.P), both[:2 * n].reshape(n, 2), int(both[-1])
+        """(counts [n,P] int32, sharp [n,2] float64, invalid) as NumPy: the one copy to the host."""
+        (counts, sharp), invalid = self._acc.fetch()
+        return counts, sharp, invalid
 
     def result(self):
-        from .lib import UpsError
-        counts, sharp, invalid = self.sums()
-        if invalid != 0:
-            raise UpsError("PartUsageEvaluator: {} pixel(s) with a part id outside [0, {}) were not counted".format(invalid, self.P))
-        if self.n == 0:
-            raise ValueError("PartUsageEvaluator.result: no image was evaluated")
+        counts, sharp = self._acc.finish("pixel(s) with a part id outside [0, {}) were not counted".format(self.P))
         return usage_from_counts(counts, sharp, self.HW, self.min_area)
 
 
@@ -526,26 +535,21 @@ class EquivarianceEvaluator(object):
     logged line."""
 
     def __init__(self, device, n_parts, tps_params, n_singular=None):
+        import torch
         self.device, self.P, self.tps_params, self.n_singular = device, int(n_parts), dict(tps_params), n_singular
         if self.P < 1:
             raise ValueError("EquivarianceEvaluator: n_parts must be positive (got {})".format(self.P))
         self.on_device = self.P <= 32
         if not self.on_device:
             LOG.info("EquivarianceEvaluator: P = %d exceeds the device table (32 x 32): counting on the host", self.P)
-        self.reset()
+        self._acc = _Accumulator("EquivarianceEvaluator", device, [("counts", (self.P, self.P), torch.int32, True), ("tv", (), torch.float64, False)],
+                                 self.on_device)
+
+    n = property(lambda self: self._acc.n)
+    HW = property(lambda self: self._acc.HW)
 
     def reset(self):
-        import torch
-        self.HW, self._host, self._host_invalid, self._n_host = None, [], 0, 0
-        self._counts = self._tv = self._invalid = None
-        if self.on_device:
-            self._counts = _RowBuffer(self.device, self.P * self.P, torch.int32, True)
-            self._tv = _RowBuffer(self.device, 1, torch.float64, False)
-            self._invalid = torch.zeros(1, dtype=torch.int32, device=self.device)
-
-    @property
-    def n(self):
-        return self._counts.n if self.on_device else self._n_host
+        self._acc.reset()
 
     def maps(self, model, views, uniforms):
         """(soft_a, soft_b, pred_b, grid) of `views` [n,S,S,3] under the warps of `uniforms` [n, tps.N_UNIFORMS]: what ``update``
@@ -573,40 +577,20 @@ class EquivarianceEvaluator(object):
         soft_a, soft_b, pred_b, grid = (t[:n] for t in self.maps(model, views, uniforms))
         if soft_a.shape[-1] != self.P:
             raise ValueError("EquivarianceEvaluator.update: maps of {} parts, {} expected".format(soft_a.shape[-1], self.P))
-        HW = int(pred_b[0].numel())
-        if self.HW is not None and HW != self.HW:
-            raise ValueError("EquivarianceEvaluator.update: maps of {} pixels after maps of {}".format(HW, self.HW))
-        self.HW = HW
+        self._acc.same_pixels("maps", int(pred_b[0].numel()))
         if not self.on_device:
             c, bad, tv = equivariance_host(soft_a.cpu().numpy(), soft_b.cpu().numpy(), pred_b.cpu().numpy(), grid.cpu().numpy())
-            self._host.append((c, tv))
-            self._host_invalid += bad
-            self._n_host += n
-            return
-        ops.part_equivariance(soft_a, soft_b, pred_b, grid, counts=self._counts.take(n).view(n, self.P, self.P), invalid=self._invalid,
-                              tv=self._tv.take(n).view(n))
+            return self._acc.add_host(n, (c, tv), bad)
+        counts, tv = self._acc.take(n)
+        ops.part_equivariance(soft_a, soft_b, pred_b, grid, counts=counts, invalid=self._acc.invalid, tv=tv)
 
     def sums(self):
-        """(counts [n,P,P] int32, tv [n] float64, invalid) as NumPy: the one copy to the host (the integers ride in the float64
-        buffer: counts <= HW < 2^31 are exact there)."""
-        import torch
-        P = self.P
-        if not self.on_device:
-            if not self._host:
-                return np.zeros((0, P, P), np.int32), np.zeros(0), 0
-            return np.concatenate([c for c, _ in self._host]), np.concatenate([t for _, t in self._host]), self._host_invalid
-        n = self.n
-        both = torch.cat([self._tv.filled().reshape(-1), self._counts.filled().reshape(-1).double(), self._invalid.double()]).cpu().numpy()
-        return both[n:-1].astype(np.int32).reshape(n, P, P), both[:n].copy(), int(both[-1])
+        """(counts [n,P,P] int32, tv [n] float64, invalid) as NumPy: the one copy to the host."""
+        (counts, tv), invalid = self._acc.fetch()
+        return counts, tv, invalid
 
     def result(self):
-        from .lib import UpsError
-        counts, tv, invalid = self.sums()
-        if invalid != 0:
-            raise UpsError("EquivarianceEvaluator: {} pixel(s) with a NaN in a part map or a part id outside [0, {}) were not counted"
-                           .format(invalid, self.P))
-        if self.n == 0:
-            raise ValueError("EquivarianceEvaluator.result: no image was evaluated")
+        counts, tv = self._acc.finish("pixel(s) with a NaN in a part map or a part id outside [0, {}) were not counted".format(self.P))
         return equivariance_from_counts(counts, tv, self.HW)
 
 

@@ -1795,6 +1795,40 @@ def unpool_mix(hard, feat, pose_idx, app_idx, act_dtype):
     return out
 
 
+# --------------------------------------------------------------------------- what the evaluation wrappers below share
+_LIBRARY_CONSTANTS = {}         # name -> the constants of the library that ``_library_constants`` found equal to Python's
+
+
+def _given_or_new(fn, name, t, shape, dtype, device, zero=False):
+    """The output `name` of wrapper `fn`: a caller's tensor -- contiguous, of `shape` and `dtype` on `device`; a row-offset view of a
+    larger buffer is fine -- or None: new zeros (an output the kernel ADDS to) or new empty (one it writes completely).  The counters
+    (`invalid`, `changed`, `n_singular`) are [1] int32.  L.UpsError before anything is launched; L.ptr would only assert."""
+    if t is None:
+        return (torch.zeros if zero else torch.empty)(shape, dtype=dtype, device=device)
+    if not torch.is_tensor(t) or t.dtype != dtype or tuple(t.shape) != tuple(shape) or t.device != device or not t.is_contiguous():
+        got = type(t) if not torch.is_tensor(t) else "{} {} on {}{}".format(list(t.shape), t.dtype, t.device,
+                                                                               "" if t.is_contiguous() else ", not contiguous")
+        raise L.UpsError("{}: {} {} {} contiguous on {} expected (got {})".format(fn, name, list(shape), dtype, device, got))
+    return t
+
+
+def _scratch(nbytes, device):
+    """The float64 scratch of a ups_*_scratch_bytes result; a fresh allocation per call (the caching allocator orders its reuse on the
+    stream).  0 bytes (sizes the library does not take): one element, and the C entry refuses the call."""
+    return torch.empty(max(1, nbytes // 8), dtype=torch.float64, device=device)
+
+
+def _library_constants(name, **want):
+    """On first use of `name`: every keyword k is a constant of this module that the library exports as ups_<k>() and must agree."""
+    if name not in _LIBRARY_CONSTANTS:
+        lib = L.load()
+        got = {k: getattr(lib, "ups_" + k)() for k in want}
+        if got != want:
+            raise L.UpsError("the library's {} constants {} differ from ops' {}: rebuild".format(
+                name, {k: v for k, v in got.items() if v != want[k]}, {k: v for k, v in want.items() if v != got[k]}))
+        _LIBRARY_CONSTANTS[name] = got
+
+
 # --------------------------------------------------------------------------- part-IoU evaluation (csrc/evalparts.hip)
 def part_confusion(pred, gt_u8, P, G, lut=None, counts=None, invalid=None):
     """counts[i,p,g] += #{pixels of image i with pred == p and lut[gt] == g} (ups_part_confusion; the statistic
@@ -1808,13 +1842,8 @@ def part_confusion(pred, gt_u8, P, G, lut=None, counts=None, invalid=None):
         raise L.UpsError("part_confusion: pred int64 and gt uint8 of one shape [N >= 1, ..], lut [256] uint8 (got {} {}, {} {}, lut {})"
                          .format(tuple(pred.shape), pred.dtype, tuple(gt_u8.shape), gt_u8.dtype,
                                  None if lut is None else (tuple(lut.shape), lut.dtype)))
-    if counts is None:
-        counts = torch.zeros((N, P, G), dtype=torch.int32, device=pred.device)
-    if invalid is None:
-        invalid = torch.zeros(1, dtype=torch.int32, device=pred.device)
-    if counts.dtype != torch.int32 or tuple(counts.shape) != (N, P, G) or invalid.dtype != torch.int32 or invalid.numel() != 1:
-        raise L.UpsError("part_confusion: counts [{},{},{}] int32 and invalid [1] int32 expected (got {} {}, {} {})".format(
-            N, P, G, tuple(counts.shape), counts.dtype, tuple(invalid.shape), invalid.dtype))
+    counts = _given_or_new("part_confusion", "counts", counts, (N, P, G), torch.int32, pred.device, zero=True)
+    invalid = _given_or_new("part_confusion", "invalid", invalid, (1,), torch.int32, pred.device, zero=True)
     pred, gt_u8 = pred.contiguous(), gt_u8.contiguous()
     L.call("ups_part_confusion", L.ptr(pred), L.ptr(gt_u8), L.ptr(lut), N, pred.numel() // N, P, G, L.ptr(counts), L.ptr(invalid),
            L.stream())
@@ -1825,7 +1854,6 @@ def part_confusion(pred, gt_u8, P, G, lut=None, counts=None, invalid=None):
 IMAGE_METRICS_TILE = 32         # valid pixels per tile edge of ups_image_metrics (checked against the library on first use)
 PART_USAGE_CHUNK = 1024         # pixels per block of ups_part_usage
 SSIM_WINDOW, SSIM_SIGMA = 11, 1.5
-_GEOMETRY_CHECKED = []
 
 
 def ssim_weights():
@@ -1838,13 +1866,7 @@ def ssim_weights():
 
 
 def _metrics_geometry():
-    if not _GEOMETRY_CHECKED:
-        lib = L.load()
-        got = (lib.ups_image_metrics_tile(), lib.ups_part_usage_chunk())
-        if got != (IMAGE_METRICS_TILE, PART_USAGE_CHUNK):
-            raise L.UpsError("the library's metric tile / chunk {} differ from ops.IMAGE_METRICS_TILE / PART_USAGE_CHUNK {}: rebuild"
-                             .format(got, (IMAGE_METRICS_TILE, PART_USAGE_CHUNK)))
-        _GEOMETRY_CHECKED.append(True)
+    _library_constants("metrics", image_metrics_tile=IMAGE_METRICS_TILE, part_usage_chunk=PART_USAGE_CHUNK)
 
 
 def image_metrics(a, b, out=None):
@@ -1853,19 +1875,15 @@ def image_metrics(a, b, out=None):
     (mapped to [0, 1] and clamped); H, W >= 11.  out [N,3] float64 (default: new; a row-offset view of a larger buffer is fine), written
     completely.  Asynchronous on the current stream; the scratch is a fresh allocation per call (the caching allocator orders its reuse
     on that stream).  Returns out."""
-    _metrics_geometry()
     if (a.dim() != 4 or b.dim() != 4 or tuple(a.shape[:3]) != tuple(b.shape[:3]) or a.shape[0] == 0 or a.shape[3] < 3 or b.shape[3] < 3
             or a.dtype not in _IMG_DTYPES or b.dtype not in _IMG_DTYPES):
         raise L.UpsError("image_metrics: a, b [N >= 1,H,W,>=3] float32 / bfloat16 of one [N,H,W] (got {} {}, {} {})".format(
             tuple(a.shape), a.dtype, tuple(b.shape), b.dtype))
     N, H, W = a.shape[:3]
-    if out is None:
-        out = torch.empty((N, 3), dtype=torch.float64, device=a.device)
-    if out.dtype != torch.float64 or tuple(out.shape) != (N, 3):
-        raise L.UpsError("image_metrics: out [{},3] float64 expected (got {} {})".format(N, tuple(out.shape), out.dtype))
+    out = _given_or_new("image_metrics", "out", out, (N, 3), torch.float64, a.device)
+    _metrics_geometry()
     a, b = a.contiguous(), b.contiguous()
-    nbytes = L.load().ups_image_metrics_scratch_bytes(N, H, W)
-    scratch = torch.empty(max(1, nbytes // 8), dtype=torch.float64, device=a.device)
+    scratch = _scratch(L.load().ups_image_metrics_scratch_bytes(N, H, W), a.device)
     w = ssim_weights()
     L.call("ups_image_metrics", L.ptr(a), L.dt(a), a.shape[3], L.ptr(b), L.dt(b), b.shape[3], N, H, W,
            w.ctypes.data_as(C.POINTER(C.c_double)), L.ptr(out), L.ptr(scratch), L.stream())
@@ -1878,31 +1896,23 @@ def part_usage(soft, pred, counts=None, invalid=None, sharp=None):
     (out_parts_hard) over the same pixels, P <= 32 (more: L.UpsError from the C entry -- evalutil.PartUsageEvaluator counts on the host
     then).  counts [N,P] int32 (default: new zeros; given: added to), invalid [1] int32 (+= pixels with pred outside [0,P), counted
     nowhere else), sharp [N,2] float64 (written).  Asynchronous on the current stream.  Returns (counts, invalid, sharp)."""
-    _metrics_geometry()
     N, P = pred.shape[0], soft.shape[-1]
     if (soft.dtype != torch.float32 or pred.dtype != torch.int64 or N == 0 or tuple(soft.shape[:-1]) != tuple(pred.shape)):
         raise L.UpsError("part_usage: soft [N >= 1,..,P] float32 and pred [N,..] int64 over the same pixels (got {} {}, {} {})".format(
             tuple(soft.shape), soft.dtype, tuple(pred.shape), pred.dtype))
-    if counts is None:
-        counts = torch.zeros((N, P), dtype=torch.int32, device=pred.device)
-    if invalid is None:
-        invalid = torch.zeros(1, dtype=torch.int32, device=pred.device)
-    if sharp is None:
-        sharp = torch.empty((N, 2), dtype=torch.float64, device=pred.device)
-    if (counts.dtype != torch.int32 or tuple(counts.shape) != (N, P) or invalid.dtype != torch.int32 or invalid.numel() != 1
-            or sharp.dtype != torch.float64 or tuple(sharp.shape) != (N, 2)):
-        raise L.UpsError("part_usage: counts [{0},{1}] int32, invalid [1] int32 and sharp [{0},2] float64 expected".format(N, P))
+    counts = _given_or_new("part_usage", "counts", counts, (N, P), torch.int32, pred.device, zero=True)
+    invalid = _given_or_new("part_usage", "invalid", invalid, (1,), torch.int32, pred.device, zero=True)
+    sharp = _given_or_new("part_usage", "sharp", sharp, (N, 2), torch.float64, pred.device)
+    _metrics_geometry()
     soft, pred = soft.contiguous(), pred.contiguous()
     HW = pred.numel() // N
-    nbytes = L.load().ups_part_usage_scratch_bytes(N, HW)
-    scratch = torch.empty(max(1, nbytes // 8), dtype=torch.float64, device=pred.device)
+    scratch = _scratch(L.load().ups_part_usage_scratch_bytes(N, HW), pred.device)
     L.call("ups_part_usage", L.ptr(soft), L.ptr(pred), N, HW, P, L.ptr(counts), L.ptr(invalid), L.ptr(sharp), L.ptr(scratch), L.stream())
     return counts, invalid, sharp
 
 
 # --------------------------------------------------------------------------- part equivariance under TPS warps (csrc/equivariance.hip)
 PART_EQUIVARIANCE_CHUNK = 1024  # pixels per block of ups_part_equivariance (checked against the library on first use)
-_EQUIVARIANCE_CHECKED = []
 
 
 def tps_grid(T, coord, h, w):
@@ -1927,12 +1937,6 @@ def part_equivariance(soft_a, soft_b, pred_b, grid, counts=None, invalid=None, t
     (more: L.UpsError from the C entry -- evalutil.EquivarianceEvaluator computes on the host then).  counts [N,P,P] int32 (default:
     new zeros; given: added to), invalid [1] int32 (+= inside pixels with a NaN or a pred_b outside [0,P), counted nowhere else),
     tv [N] float64 (written).  Asynchronous on the current stream.  Returns (counts, invalid, tv)."""
-    if not _EQUIVARIANCE_CHECKED:
-        got = L.load().ups_part_equivariance_chunk()
-        if got != PART_EQUIVARIANCE_CHUNK:
-            raise L.UpsError("the library's equivariance chunk {} differs from ops.PART_EQUIVARIANCE_CHUNK {}: rebuild".format(
-                got, PART_EQUIVARIANCE_CHUNK))
-        _EQUIVARIANCE_CHECKED.append(True)
     if (soft_a.dim() != 4 or soft_a.dtype != torch.float32 or soft_b.dtype != torch.float32 or pred_b.dtype != torch.int64
             or grid.dtype != torch.float32 or soft_a.shape[0] == 0 or soft_b.shape != soft_a.shape
             or tuple(pred_b.shape) != tuple(soft_a.shape[:3]) or tuple(grid.shape) != tuple(soft_a.shape[:3]) + (2,)):
@@ -1942,18 +1946,12 @@ def part_equivariance(soft_a, soft_b, pred_b, grid, counts=None, invalid=None, t
                              tuple(grid.shape), grid.dtype))
     N, h, w, P = soft_a.shape
     dev = soft_a.device
-    if counts is None:
-        counts = torch.zeros((N, P, P), dtype=torch.int32, device=dev)
-    if invalid is None:
-        invalid = torch.zeros(1, dtype=torch.int32, device=dev)
-    if tv is None:
-        tv = torch.empty((N,), dtype=torch.float64, device=dev)
-    if (counts.dtype != torch.int32 or tuple(counts.shape) != (N, P, P) or invalid.dtype != torch.int32 or invalid.numel() != 1
-            or tv.dtype != torch.float64 or tv.numel() != N):
-        raise L.UpsError("part_equivariance: counts [{0},{1},{1}] int32, invalid [1] int32 and tv [{0}] float64 expected".format(N, P))
+    counts = _given_or_new("part_equivariance", "counts", counts, (N, P, P), torch.int32, dev, zero=True)
+    invalid = _given_or_new("part_equivariance", "invalid", invalid, (1,), torch.int32, dev, zero=True)
+    tv = _given_or_new("part_equivariance", "tv", tv, (N,), torch.float64, dev)
+    _library_constants("equivariance", part_equivariance_chunk=PART_EQUIVARIANCE_CHUNK)
     soft_a, soft_b, pred_b, grid = soft_a.contiguous(), soft_b.contiguous(), pred_b.contiguous(), grid.contiguous()
-    nbytes = L.load().ups_part_equivariance_scratch_bytes(N, h * w)
-    scratch = torch.empty(max(1, nbytes // 8), dtype=torch.float64, device=dev)
+    scratch = _scratch(L.load().ups_part_equivariance_scratch_bytes(N, h * w), dev)
     L.call("ups_part_equivariance", L.ptr(soft_a), L.ptr(soft_b), L.ptr(pred_b), L.ptr(grid), N, h, w, P, L.ptr(counts), L.ptr(invalid),
            L.ptr(tv), L.ptr(scratch), L.stream())
     return counts, invalid, tv
@@ -2010,14 +2008,13 @@ def part_kmeans_step(feat, valid, cent, prev_label=None, accumulate=True, change
     cent = cent.contiguous()
     k, dev = cent.shape[1], feat.device
     out = {"label": torch.empty((N, P), dtype=torch.int32, device=dev), "mind": torch.empty((N, P), dtype=torch.float64, device=dev),
-           "changed": torch.zeros(1, dtype=torch.int32, device=dev) if changed is None else changed}
+           "changed": _given_or_new("part_kmeans_step", "changed", changed, (1,), torch.int32, dev, zero=True)}
     scratch = None
     if accumulate:
         out["counts"] = torch.zeros((P, k), dtype=torch.int32, device=dev)
         out["sums"] = torch.empty((P, k, A), dtype=torch.float64, device=dev)
         out["inertia"] = torch.empty((P,), dtype=torch.float64, device=dev)
-        nbytes = L.load().ups_part_kmeans_scratch_bytes(N, P, A, k)
-        scratch = torch.empty(max(1, nbytes // 8), dtype=torch.float64, device=dev)
+        scratch = _scratch(L.load().ups_part_kmeans_scratch_bytes(N, P, A, k), dev)
     L.call("ups_part_kmeans_step", L.ptr(feat), L.ptr(valid), N, P, A, L.ptr(cent), k,
            L.ptr(None if prev_label is None else prev_label.contiguous()), L.ptr(out["label"]), L.ptr(out["mind"]),
            L.ptr(out.get("counts")), L.ptr(out.get("sums")), L.ptr(out.get("inertia")), L.ptr(out["changed"]), L.ptr(scratch), L.stream())
@@ -2045,13 +2042,9 @@ def part_moments(soft, pred=None, min_mass=0.0, hard=None, invalid=None):
     out = {"mass": torch.empty((N, P), dtype=torch.float64, device=dev), "centre": torch.empty((N, P, 2), dtype=torch.float64, device=dev),
            "valid": torch.empty((N, P), dtype=torch.uint8, device=dev)}
     if pred is not None:
-        out["hard"] = torch.zeros((N, P, 3), dtype=torch.int32, device=dev) if hard is None else hard
-        out["invalid"] = torch.zeros(1, dtype=torch.int32, device=dev) if invalid is None else invalid
-        if (out["hard"].dtype != torch.int32 or tuple(out["hard"].shape) != (N, P, 3) or out["invalid"].dtype != torch.int32
-                or out["invalid"].numel() != 1):
-            raise L.UpsError("part_moments: hard [{},{},3] int32 and invalid [1] int32 expected".format(N, P))
-    nbytes = L.load().ups_part_moments_scratch_bytes(N, h, w, P)
-    scratch = torch.empty(max(1, nbytes // 8), dtype=torch.float64, device=dev)
+        out["hard"] = _given_or_new("part_moments", "hard", hard, (N, P, 3), torch.int32, dev, zero=True)
+        out["invalid"] = _given_or_new("part_moments", "invalid", invalid, (1,), torch.int32, dev, zero=True)
+    scratch = _scratch(L.load().ups_part_moments_scratch_bytes(N, h, w, P), dev)
     L.call("ups_part_moments", L.ptr(soft.contiguous()), L.ptr(None if pred is None else pred.contiguous()), N, h, w, P, float(min_mass),
            L.ptr(out["mass"]), L.ptr(out["centre"]), L.ptr(out["valid"]), L.ptr(out.get("hard")), L.ptr(out.get("invalid")),
            L.ptr(scratch), L.stream())
@@ -2076,8 +2069,7 @@ def landmark_gram(feat, target, vis):
     G = torch.empty((K, D, D), dtype=torch.float64, device=dev)
     R = torch.empty((K, D, 2), dtype=torch.float64, device=dev)
     cnt = torch.empty((K,), dtype=torch.int32, device=dev)
-    nbytes = L.load().ups_landmark_gram_scratch_bytes(N, D, K)
-    scratch = torch.empty(max(1, nbytes // 8), dtype=torch.float64, device=dev)
+    scratch = _scratch(L.load().ups_landmark_gram_scratch_bytes(N, D, K), dev)
     L.call("ups_landmark_gram", L.ptr(feat.contiguous()) if D > 1 else None, L.ptr(target.contiguous()), L.ptr(vis.contiguous()), N, D, K,
            L.ptr(G), L.ptr(R), L.ptr(cnt), L.ptr(scratch), L.stream())
     return G, R, cnt
@@ -2092,10 +2084,7 @@ def landmark_solve(G, R, cnt, ridge, n_singular=None):
         raise L.UpsError("landmark_solve: G [K,D,D], R [K,D,2] float64 and cnt [K] int32 (got {}, {}, {})".format(
             tuple(G.shape), tuple(R.shape), tuple(cnt.shape)))
     K, D = G.shape[0], G.shape[1]
-    if n_singular is None:
-        n_singular = torch.zeros(1, dtype=torch.int32, device=G.device)
-    if n_singular.dtype != torch.int32 or n_singular.numel() != 1:
-        raise L.UpsError("landmark_solve: n_singular [1] int32 expected")
+    n_singular = _given_or_new("landmark_solve", "n_singular", n_singular, (1,), torch.int32, G.device, zero=True)
     W = torch.empty((K, D, 2), dtype=torch.float64, device=G.device)
     L.call("ups_landmark_solve", L.ptr(G.contiguous()), L.ptr(R.contiguous()), L.ptr(cnt.contiguous()), D, K, float(ridge), L.ptr(W),
            L.ptr(n_singular), L.stream())
@@ -2124,7 +2113,6 @@ def landmark_predict(feat, W, target=None, vis=None):
 SEGMENT_CHUNK = 1024            # pixels per block of ups_segment_render (checked against the library on first use)
 SEGMENT_ALIGN = 16              # an image's pixel offset in the packed planes is a multiple of it
 SEGMENT_OUTPUTS = ("labels", "overlay", "confidence", "counts")
-_SEGMENT_CHECKED = []
 
 
 def segment_table(sizes):
@@ -2214,12 +2202,7 @@ def segment_render(soft, sizes, src=None, colors=None, alpha=0.5, want=("labels"
     [n,S,S,3] is returned as "guide".
     Returns {"table" (NumPy), "table_dev", "total", <the wanted packed tensors>, "views": {name: [per-image views [h,w] / [h,w,3]]}}.
     Asynchronous on the current stream."""
-    if not _SEGMENT_CHECKED:
-        lib = L.load()
-        got = (lib.ups_segment_chunk(), lib.ups_segment_table_words())
-        if got != (SEGMENT_CHUNK, 4):
-            raise L.UpsError("the library's segment chunk / table words {} differ from ops' {}: rebuild".format(got, (SEGMENT_CHUNK, 4)))
-        _SEGMENT_CHECKED.append(True)
+    _library_constants("segment", segment_chunk=SEGMENT_CHUNK, segment_table_words=4)
     want = tuple(want)
     if not want or any(k not in SEGMENT_OUTPUTS for k in want):
         raise L.UpsError("segment_render: want is a non-empty subset of {} (got {})".format(SEGMENT_OUTPUTS, want))
