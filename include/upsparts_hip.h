@@ -223,6 +223,10 @@ typedef struct {
     float ax, ay;
 } ups_prep_item;
 int64_t ups_prep_item_blocks(const ups_prep_item* item_host, int32_t dtype);
+/* Host constants of the batched launch: 256-element chunks converted per thread block (a unit of four chunks must lie inside one
+ * block), and the item count up to which the prefix is searched in LDS (beyond it: in global memory). */
+int32_t ups_prep_chunks_per_block(void);
+int32_t ups_prep_lds_items(void);
 int ups_weight_prep_batch(const ups_prep_item* items, const int64_t* block_prefix, int32_t n_items, int64_t total_blocks,
                           int32_t dtype, void* stream);
 
@@ -233,16 +237,17 @@ int ups_weight_prep_batch(const ups_prep_item* items, const int64_t* block_prefi
 int ups_coord_table(const float* V, int32_t kh, int32_t kw, int32_t ci_log, int32_t co,
                     const int32_t* tap_dy, const int32_t* tap_dx, int32_t in_sy, int32_t in_sx,
                     float ax, float ay, float* tab, void* stream);
-/* gsum[pix][c] = sum_n dout[n][pix][c] (fp32) */
+/* gsum[pix][c] = sum_n dout[n][pix][c] (fp32); dout is UPS_F32 or UPS_BF16 (gradients are never fp16: UPS_F16 is refused) */
 int ups_batch_sum(const void* dout, int32_t dtype, int32_t n, int64_t pix, int32_t co, int32_t ldo,
                   float* gsum, void* stream);
 /* gradient of the two CoordConv rows of V (and optionally the bias) from gsum [ho*wo][co];
- * `scratch` holds (kh+1)*2*wo*co floats (separable two-stage reduction: rows first, then columns) */
+ * `scratch` holds (2*kh+1)*wo*co floats (separable two-stage reduction: rows first -- two planes per tap row and one for the
+ * bias --, then columns); grad_bias [co] or NULL */
 int ups_coord_wgrad(const float* gsum, int32_t hi, int32_t wi, int32_t ho, int32_t wo, int32_t co,
                     int32_t kh, int32_t kw, const int32_t* tap_dy, const int32_t* tap_dx,
                     int32_t in_sy, int32_t in_sx, float ax, float ay,
                     int32_t ci_log, float* gradV, float* grad_bias, float* scratch, void* stream);
-/* grad_bias[c] = sum_rows dout[row][c]; workspace >= 1024*co floats */
+/* grad_bias[c] = sum_rows dout[row][c]; dout is UPS_F32 or UPS_BF16 (UPS_F16 is refused); workspace >= 1024*co floats */
 int ups_col_sum(const void* dout, int32_t dtype, int64_t rows, int32_t co, int32_t ldo,
                 float* out, float* workspace, void* stream);
 

@@ -476,6 +476,10 @@ extern "C" int64_t ups_prep_item_blocks(const ups_prep_item* item_host, int32_t 
     return (prep_elems(*item_host, dtype == UPS_F32 ? 16 : 32) + 255) / 256;
 }
 
+// the two constants of weight_prep_batch_kernel that decide which path a chunk takes (tests assert their cases' premises from these)
+extern "C" int32_t ups_prep_chunks_per_block(void) { return PREP_CPB; }
+extern "C" int32_t ups_prep_lds_items(void) { return PREP_LDS_ITEMS; }
+
 extern "C" int ups_weight_prep_batch(const ups_prep_item* items, const int64_t* block_prefix, int32_t n_items,
                                      int64_t total_blocks, int32_t dtype, void* stream) {
     UPS_CHECK_ARG(items && block_prefix && n_items >= 1 && total_blocks >= 1 && total_blocks < 0x7fffffffLL);
@@ -513,6 +517,7 @@ extern "C" int ups_coord_table(const float* V, int32_t kh, int32_t kw, int32_t c
 extern "C" int ups_batch_sum(const void* dout, int32_t dtype, int32_t n, int64_t pix, int32_t co, int32_t ldo, float* gsum,
                              void* stream) {
     UPS_CHECK_ARG(dout && gsum && n > 0 && pix > 0);
+    UPS_CHECK_ARG(dtype == UPS_F32 || dtype == UPS_BF16);       // (no fp16 instance: gradients are never fp16, and a forward tensor read as bf16 sums garbage)
     UPS_CHECK_ARG(ldo % 8 == 0 && ((uintptr_t)dout & 15) == 0);
     int grid = ups_cdiv(pix * ups_cdiv(co, dtype == UPS_F32 ? 4 : 8), 256);
     if (grid > 16384) grid = 16384;
@@ -545,6 +550,7 @@ extern "C" int ups_coord_wgrad(const float* gsum, int32_t hi, int32_t wi, int32_
 extern "C" int ups_col_sum(const void* dout, int32_t dtype, int64_t rows, int32_t co, int32_t ldo, float* out,
                            float* workspace, void* stream) {
     UPS_CHECK_ARG(dout && out && workspace && rows > 0 && co > 0);
+    UPS_CHECK_ARG(dtype == UPS_F32 || dtype == UPS_BF16);
     int tx = 32;
     while (tx < co && tx < 256) tx *= 2;
     const int ty = 256 / tx;

@@ -98,6 +98,8 @@ _SIGS = {
     "ups_weight_prep_f8": ([_P, _I, _I, _I, _I, _I, _P, _P, _P], C.c_int),
     "ups_weight_prep_d2s": ([_P, _I, _I, _I, _I, _I, _I, _P, _P], C.c_int),
     "ups_prep_item_blocks": ([C.POINTER(PrepItem), _I], C.c_int64),
+    "ups_prep_chunks_per_block": ([], _I),
+    "ups_prep_lds_items": ([], _I),
     "ups_weight_prep_batch": ([_P, _P, _I, _L, _I, _P], C.c_int),
     "ups_coord_table": ([_P, _I, _I, _I, _I, C.POINTER(_I), C.POINTER(_I), _I, _I, _F, _F, _P, _P], C.c_int),
     "ups_batch_sum": ([_P, _I, _I, _L, _I, _I, _P, _P], C.c_int),
