@@ -862,6 +862,45 @@ int ups_state_update_guarded(const float* stats, const float* old_state, float* 
                              int32_t update_loa, float loa_lr, float loa_target, int32_t update_lor, float lor_lr,
                              float lor_target, float lor_min, float lor_max, int64_t* skipped, void* stream);
 
+/* ---------------------------------------------------------------- weight EMA (csrc/ema.hip)
+ * Shadow weights: an exponential moving average of every optimizer key's flat fp32 bucket, kept on the device and updated in the step
+ * without the host.  The reference has no weight EMA: these definitions are the project's own (the decay warm-up is the `num_updates`
+ * rule of tf.train.ExponentialMovingAverage).  Added without a new UPS_ABI_VERSION, as the ups_augment_* entries were.
+ *
+ * ups_ema_item: one key.  `items` is a HOST array of at most UPS_EMA_MAX_ITEMS; the entries copy it into their kernels' arguments, so
+ * a captured graph bakes the bucket pointers in.  shadow and weights: count floats each, DEVICE, 4-byte aligned (any misalignment
+ * against 16 bytes, the two sides alike or not), not overlapping.  rec: the key's ups_step_guard, or NULL for a key that is never
+ * skipped.
+ *
+ * ups_ema_update(items, n_items, decay, warmup, n_updates, omd, max_blocks, stream): two launches for all items together.
+ *   (a) one thread per item k.  rec != NULL and rec->skip != 0 (read from device memory when the kernel runs: a graph replay decides
+ *       afresh): omd[k] = 0 and n_updates[k] stays.  Otherwise, in fp64, with n = n_updates[k]:
+ *         d = warmup ? min(decay, (1.0 + n) / (10.0 + n)) : decay;   omd[k] = (float)(1.0 - d);   n_updates[k] = n + 1.
+ *   (b) every element of every item whose skip is not set, in fp32 with one rounding per operation (no contraction):
+ *         t = s - w;  u = t * omd[k];  s = s - u.
+ *       A skipped item's shadow is not written.  A non-finite w gives what the formula gives (which NaN a NaN result is, is the
+ *       hardware's choice).  One grid over (item, chunk of 4096 elements); 16-byte accesses on the shadow wherever it is 16-byte
+ *       aligned, on the weights where they are misaligned like the shadow (else the widest their alignment permits), single elements
+ *       in front of and behind; the result does not depend on the alignment, on the grid or on max_blocks (0: the default grid; n > 0:
+ *       at most n blocks, each striding over the chunks).
+ *   n_updates: int64 [n_items], DEVICE, zeroed once by the caller.  omd: float [n_items], DEVICE scratch, overwritten.
+ * ups_ema_swap(items, n_items, max_blocks, stream): shadow and weights of every item exchange their bits in place, one launch, no
+ *   temporary buffer (rec is not read).
+ * UPS_E_ARG, nothing launched: n_items < 0 or > UPS_EMA_MAX_ITEMS, NULL items with n_items > 0, a NULL bucket with count > 0,
+ * count < 0, a bucket not 4-byte aligned (a rec not 8-byte aligned), max_blocks < 0; for ups_ema_update also a NULL n_updates or omd
+ * and a decay that is NaN or outside [0, 1).  n_items == 0: UPS_OK, nothing launched. */
+#define UPS_EMA_MAX_ITEMS 16
+typedef struct ups_ema_item {
+    float* shadow;                 /* flat fp32 bucket, DEVICE */
+    float* weights;                /* the key's ParamBank "p" bucket */
+    int64_t count;
+    const ups_step_guard* rec;     /* NULL: never skipped */
+} ups_ema_item;
+int32_t ups_ema_item_bytes(void);
+int ups_ema_update(const ups_ema_item* items, int32_t n_items, double decay, int32_t warmup, int64_t* n_updates, float* omd,
+                   int32_t max_blocks, void* stream);
+int ups_ema_swap(const ups_ema_item* items, int32_t n_items, int32_t max_blocks, void* stream);
+
 /* ---------------------------------------------------------------- thin-plate-spline augmentation (M:282-311)
  * Replaces eddata.utils.tps.ThinPlateSpline (un-vendored; "adapted from CompVis/unsupervised-disentangling", Y:188):
  * out[n][y][x][:] = bilinear sample of img[n] at (x_s, y_s) = T[n] @ [1, x, y, phi(|(x,y) - coord[n][i]|^2)...],

@@ -85,9 +85,17 @@ class StepGuard(C.Structure):
                 ("skipped_total", C.c_int64), ("clipped_total", C.c_int64), ("consecutive", C.c_int32), ("reserved", C.c_int32 * 3)]
 
 
+EMA_MAX_ITEMS = 16            # include/upsparts_hip.h UPS_EMA_MAX_ITEMS
+
+
+class EmaItem(C.Structure):
+    """ups_ema_item: one optimizer key of ups_ema_update / ups_ema_swap (shadow bucket, weight bucket, elements, guard record or NULL)."""
+    _fields_ = [("shadow", C.c_void_p), ("weights", C.c_void_p), ("count", C.c_int64), ("rec", C.c_void_p)]
+
+
 _lib = None
 
-_I, _L, _F, _P, _Z = C.c_int32, C.c_int64, C.c_float, C.c_void_p, C.c_size_t
+_I,_L, _F, _P, _Z = C.c_int32, C.c_int64, C.c_float, C.c_void_p, C.c_size_t
 _SIGS = {
     "ups_abi_version": ([], C.c_int),
     "ups_struct_sizes": ([C.POINTER(C.c_int64)], None),
@@ -208,6 +216,9 @@ _SIGS = {
     "ups_grad_guard": ([_P, _L, C.c_double, C.c_double, _I, _P, _P, _I, _P], C.c_int),
     "ups_adam_guarded": ([_P, _P, _P, _P, _L, _F, _P, _F, _F, _F, _F, _P, _P], C.c_int),
     "ups_state_update_guarded": ([_P, _P, _P, _F, _F, _I, _F, _F, _I, _F, _F, _F, _F, _P, _P], C.c_int),
+    "ups_ema_item_bytes": ([], _I),
+    "ups_ema_update": ([C.POINTER(EmaItem), _I, C.c_double, _I, _P, _P, _I, _P], C.c_int),
+    "ups_ema_swap": ([C.POINTER(EmaItem), _I, _I, _P], C.c_int),
     "ups_tps_warp": ([_P, _P, _P, _P, _I, _I, _I, _I, _I, _P], C.c_int),
     "ups_tps_solve": ([_P, _P, _P, _P, _I, _I, _P], C.c_int),
     "ups_tps_params": ([_P, _P, _I] + [C.c_double] * 6 + [_P, _P, _P, _P, _I, _P], C.c_int),
@@ -252,6 +263,9 @@ def load():
     if lib.ups_step_guard_bytes() != C.sizeof(StepGuard):
         raise UpsError("{}: ups_step_guard is {} bytes, this binding's StepGuard {} (stale library?)".format(
             LIB_PATH, lib.ups_step_guard_bytes(), C.sizeof(StepGuard)))
+    if lib.ups_ema_item_bytes() != C.sizeof(EmaItem):
+        raise UpsError("{}: ups_ema_item is {} bytes, this binding's EmaItem {} (stale library?)".format(
+            LIB_PATH, lib.ups_ema_item_bytes(), C.sizeof(EmaItem)))
     _lib = lib
     return lib
 

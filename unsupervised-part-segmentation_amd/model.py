@@ -14,6 +14,7 @@ Tape layout (cuts where the per-key semantics need different upstream gradients)
 The part path between B and C (soft-max, hard max, moments, rectangles, priors) is not taped at all:
 its forward and its fused backward are single HIP kernels.
 """
+import contextlib
 import ctypes as C
 import math
 import os
@@ -52,6 +53,7 @@ class TrainModel(object):
 
     def __init__(self, config, device=None, seed=None):
         self.config = config
+        ema_config(config)          # (an unknown or ill-formed `ema_*` key is refused before anything is built)
         if not torch.cuda.is_available():
             raise L.UpsError("TrainModel needs a HIP device: the product path has no CPU fallback")
         L.load()
@@ -551,6 +553,41 @@ def step_guard_config(config):
     return float(clip), skip, maxc
 
 
+EMA_KEYS = ("ema_decay", "ema_warmup")
+
+
+def ema_config(config):
+    """The keys of the weight EMA (DESIGN section 8.2), decided from the config alone -> (ema_decay, ema_warmup, val_use_ema, use_ema);
+    ValueError with the reason for an `ema_decay` outside [0, 1) (0 = off), for an unknown `ema_*` key and for `val_use_ema` without
+    `ema_decay`."""
+    unknown = sorted(k for k in config if isinstance(k, str) and k.startswith("ema_") and k not in EMA_KEYS)
+    if unknown:
+        raise ValueError("unknown weight-EMA key(s) {} ({})".format(unknown, " | ".join(EMA_KEYS)))
+    decay = config.get("ema_decay", 0.0)
+    if isinstance(decay, bool) or not isinstance(decay, (int, float)) or not (0.0 <= decay < 1.0):     # (NaN fails both comparisons)
+        raise ValueError("ema_decay: a number in [0, 1) is expected, 0 = no weight EMA (got {!r})".format(decay))
+    flags = []
+    for k, default in (("ema_warmup", True), ("val_use_ema", False), ("use_ema", False)):
+        v = config.get(k, default)
+        if not isinstance(v, bool):
+            raise ValueError("{}: True or False is expected (got {!r})".format(k, v))
+        flags.append(v)
+    if flags[1] and not decay > 0:
+        raise ValueError("val_use_ema: True needs ema_decay > 0 (there are no shadow weights to validate on)")
+    return (float(decay),) + tuple(flags)
+
+
+def checkpoint_shadows(ck, use_ema, where):
+    """The "ema" entry of a native checkpoint dict ({"params": {name: tensor}, "n": {key: int}}) or None; ValueError under `use_ema`
+    when the file holds none."""
+    ema = ck.get("ema")
+    if ema is not None and not ema.get("params"):
+        ema = None
+    if use_ema and ema is None:
+        raise ValueError("use_ema: True, but {} holds no shadow weights (it was written without ema_decay)".format(where))
+    return ema
+
+
 class Trainer(object):
     """Mirror of model.py:570-1068 plus the pieces edflow's TFBaseTrainer supplied (session loop,
     one Adam per loss key over the variables whose name contains the key, logging cadence)."""
@@ -651,6 +688,12 @@ class Trainer(object):
         self._guard_used, self._nonfinite_warned = False, False
         model.fp8.skip_nonfinite = self.skip_nonfinite        # `log_images` (default off): the reference's img_ops (model.py:968-1053) as uint8 canvases on the steps that log scalars
         self.log_images = bool(config.get("log_images", False))
+        # weight EMA (default off): with `ema_decay` > 0 one shadow bucket per optimizer key, updated by ONE
+        # ops.ema_update at the end of every step; allocated once at fixed addresses, as the guard records are (a captured step writes them)
+        self.ema_decay, self.ema_warmup, self.val_use_ema, self.use_ema = ema_config(config)
+        self._ema = None
+        if self.ema_decay > 0:
+            self._ema_init()
         self._want_images = False       # set for the duration of a train_step(..., images=True)
         # `val_freq: K` with `val_csv`: the metrics of `val_metrics` (default: the part IoU) on a validation csv after every K-th step
         # (``validate``)
@@ -718,6 +761,7 @@ class Trainer(object):
         if tfckpt.is_bundle(checkpoint_path):
             return self._initialize_from_tf(checkpoint_path)
         ck = torch.load(checkpoint_path, map_location="cpu")
+        ema = checkpoint_shadows(ck, self.use_ema, checkpoint_path)      # (`use_ema` with a file that holds none: refused before anything is loaded)
         keep = set(self.get_restore_variables())
         self.model.bank.load({n: t for n, t in ck["params"].items() if n in keep})
         for key, grp in self.model.bank.groups.items():
@@ -727,6 +771,7 @@ class Trainer(object):
         for k, v in ck.get("state", {}).items():
             if k in self.state:
                 self.state[k].fill_(float(v))
+        self._restore_ema(ema["params"] if ema else None, ema.get("n") if ema else None, keep, checkpoint_path)
         if "noise_offset" in ck:
             self._noise.offset = int(ck["noise_offset"])
         if "gen_state" in ck:
@@ -773,6 +818,7 @@ class Trainer(object):
         import numpy as np
         bundle = tfckpt.read_bundle(prefix)
         params, m, v, _other = tfckpt.to_trainer_state(bundle)
+        shadows = tfckpt.pop_shadows(_other)     # `<var>/ExponentialMovingAverage`: the weight EMA's shadows, not "unrestored scalars"
         keep = set(self.get_restore_variables())
         bank = self.model.bank
         loaded = {n: torch.from_numpy(np.ascontiguousarray(a)) for n, a in params.items()
@@ -791,6 +837,8 @@ class Trainer(object):
         if self.logger:
             self.logger.info("Lazily restored {} of {} variables from the TensorFlow checkpoint {}".format(
                 len(loaded), len(bank.params), prefix))
+        # (a bundle carries no update counts: tf.train.ExponentialMovingAverage takes num_updates from the global step, and so does this)
+        self._restore_ema({n: np.ascontiguousarray(a) for n, a in shadows.items()} or None, self.global_step, keep, prefix)
         self.restored_from_tf = sorted(loaded)
         # what slim.assign_from_checkpoint would ALSO have restored but cannot be matched here: the reference's unnamed
         # non-trainable scalars (Lagrangian multipliers, EMAs) and the optimizers' beta powers.  Say so instead of silently
@@ -826,14 +874,23 @@ class Trainer(object):
                 import sys
                 sys.stderr.write("[WARNING] " + msg + "\n")
 
-    def export_tf_checkpoint(self, prefix):
-        """Write the trainable variables (+ Adam slots) as a TensorFlow tensor bundle the reference's graph can restore."""
+    def export_tf_checkpoint(self, prefix, weights="current"):
+        """Write the trainable variables (+ Adam slots) as a TensorFlow tensor bundle the reference's graph can restore.  With the
+        weight EMA on, every shadow goes in as `<var>/ExponentialMovingAverage` (tf.train.ExponentialMovingAverage's name);
+        weights="ema" writes the shadows under the plain variable names as well, so that the reference's graph restores EMA weights."""
         from . import tfckpt
         import numpy as np
+        if weights not in ("current", "ema"):
+            raise ValueError("export_tf_checkpoint: weights is \"current\" or \"ema\" (got {!r})".format(weights))
+        if weights == "ema" and self._ema is None:
+            raise ValueError("export_tf_checkpoint(weights=\"ema\"): the weight EMA is off (ema_decay: 0)")
         bank = self.model.bank
         tensors = {}
+        shadows = self.ema_state() if self._ema is not None else {}
+        for n, t in shadows.items():
+            tensors[n + tfckpt.EMA_SUFFIX] = t.numpy()
         for n, p in bank.params.items():
-            tensors[n] = p.detach().cpu().numpy()
+            tensors[n] = shadows[n].numpy() if weights == "ema" and n in shadows else p.detach().cpu().numpy()
             tensors[n + "/Adam"] = bank.adam_m[n].detach().cpu().numpy()
             tensors[n + "/Adam_1"] = bank.adam_v[n].detach().cpu().numpy()
         tensors["global_step"] = np.asarray(self.global_step, dtype=np.int64)
@@ -848,7 +905,10 @@ class Trainer(object):
         if self._poisoned:
             raise RuntimeError("refusing to write a checkpoint: " + self._poisoned)
         bank = self.model.bank
-        torch.save({"params": bank.state(), "global_step": self.global_step,
+        extra = {}
+        if self._ema is not None:       # the shadows by variable name (`restore_exclude` applies to them as to params) and the keys' counts
+            extra["ema"] = {"params": self.ema_state(), "n": dict(self.ema_report())}
+        torch.save({"params": bank.state(), "global_step": self.global_step, **extra,
                     "adam": {k: {"m": g["flat"]["m"].cpu(), "v": g["flat"]["v"].cpu(), "t": g["t"]}
                              for k, g in bank.groups.items()},
                     "state": {k: float(v) for k, v in self.state.items()},
@@ -1545,6 +1605,8 @@ class Trainer(object):
         self.sync.segment_done([k for k in ("encoder_0",) if k in c.keys])
         self.sync.finish(c.keys)
         new = self._next_state(c)
+        if self._ema is not None:       # every key's Adam is enqueued and joined on this stream; behind the state update, so that
+            self._ema_step(graph_lr)    # under data parallelism it is part of the LAST graph of the captured sequence.  No collective.
         build_logs = self._log_thunk(c)
         st = c.st
         if graph_lr is not None:        # graph mode: state lives in fixed device scalars, python counters advance outside
@@ -1622,6 +1684,94 @@ class Trainer(object):
         s = self._guard_state.cpu().tolist()
         out["state"] = {"skipped": int(s[0]), "consecutive": int(s[1])}
         return out
+
+    # ------------------------------------------------------------------ weight EMA
+    def _ema_init(self):
+        """One shadow bucket per optimizer key (keys under `fix_weights` have none), a copy of the weights; per-variable views of the
+        shadows under the variables' names; the update counts and the kernel's scratch; the item arrays without and with guard records."""
+        bank, d = self.model.bank, self.device
+        keys = self.loss_keys()
+        shadow = OrderedDict((k, bank.groups[k]["flat"]["p"].detach().clone()) for k in keys)
+        views = OrderedDict()
+        for k in keys:
+            off = 0
+            for n in bank.groups[k]["names"]:
+                cnt = bank.params[n].numel()
+                views[n] = shadow[k][off:off + cnt].view(bank.params[n].shape)
+                off += cnt
+        rec = lambda k, guarded: self._guard_rec[self._guard_index[k]] if guarded else None
+        items = {g: ops.EmaItems([(shadow[k], bank.groups[k]["flat"]["p"].detach(), rec(k, g)) for k in keys]) for g in (False, True)}
+        self._ema = {"keys": keys, "shadow": shadow, "views": views, "items": items,
+                     "n": torch.zeros(len(keys), dtype=torch.int64, device=d), "omd": torch.zeros(len(keys), dtype=torch.float32, device=d)}
+
+    def _ema_step(self, graph_lr):
+        """The step's one ops.ema_update (two launches for all keys), behind every key's Adam on the launching stream.  Under the guarded
+        step the items carry the keys' records: a key that did not step keeps its shadow and its count."""
+        e = self._ema
+        ops.ema_update(e["items"][bool(self._guarded(graph_lr))], e["n"], e["omd"], self.ema_decay, self.ema_warmup)
+
+    def ema_report(self):
+        """{optimizer key: updates its shadow has taken} (synchronises).  ValueError with `ema_decay` off."""
+        if self._ema is None:
+            raise ValueError("ema_report: the weight EMA is off (ema_decay: 0)")
+        torch.cuda.synchronize(self.device)
+        return OrderedDict(zip(self._ema["keys"], (int(x) for x in self._ema["n"].cpu().tolist())))
+
+    def ema_state(self):
+        """The shadows by variable name, as host copies (the checkpoint's form)."""
+        return OrderedDict((n, t.detach().cpu().clone()) for n, t in self._ema["views"].items())
+
+    @contextlib.contextmanager
+    def ema_weights(self):
+        """Inside the scope the model's weights ARE the shadows (every ``TrainModel`` method runs on them); the weights proper wait in
+        the shadow buckets and return, bit for bit, on exit: ops.ema_swap + ops.weights_changed each way, no copy of the buckets.  No
+        training step inside the scope.  ValueError with `ema_decay` off, and under `precision: fp8`, where refreshing the converted
+        copies advances the delayed scales (the refusal `val_freq` makes)."""
+        if self._ema is None:
+            raise ValueError("ema_weights: the weight EMA is off (ema_decay: 0)")
+        if self.model.fp8.enabled:
+            raise ValueError("ema_weights cannot be combined with precision: fp8: refreshing the converted weight copies advances the "
+                             "delayed scales, so the scope would move the next training step's scales")
+        ops.Fp8.activate(self.model.fp8)
+        items = self._ema["items"][False]
+        ops.ema_swap(items)
+        ops.weights_changed(self.model.nets.prep)
+        try:
+            yield self
+        finally:
+            ops.ema_swap(items)
+            ops.weights_changed(self.model.nets.prep)
+
+    @torch.no_grad()
+    def _restore_ema(self, shadows, counts, keep, where):
+        """After a restore of the weights.  shadows: {variable name: tensor} from the file, or None; counts: {key: int}, an int for
+        every key, or None.  `use_ema`: the weights are overwritten by the file's shadows.  With the feature on the shadows start as the
+        restored weights, counts 0, and take the file's shadows and counts over them where it holds some."""
+        bank = self.model.bank
+        if shadows is not None:
+            shadows = {n: (t if torch.is_tensor(t) else torch.from_numpy(t)) for n, t in shadows.items()
+                       if n in keep and n in bank.params and tuple(t.shape) == tuple(bank.params[n].shape)}
+        if self.use_ema:
+            if not shadows:
+                raise ValueError("use_ema: True, but {} holds no shadow weights of this model".format(where))
+            bank.load(shadows)
+        if self._ema is None:
+            return
+        e = self._ema
+        for k in e["keys"]:
+            e["shadow"][k].copy_(bank.groups[k]["flat"]["p"])
+        e["n"].zero_()
+        if not shadows:
+            msg = "{} holds no shadow weights: the weight EMA starts from the restored weights, counts 0".format(where)
+            if self.logger:
+                self.logger.info(msg)
+            return
+        for n, t in shadows.items():
+            if n in e["views"]:
+                e["views"][n].copy_(t.to(torch.float32))
+        if counts is not None:
+            vals = [int(counts if isinstance(counts, int) else counts.get(k, 0)) for k in e["keys"]]
+            e["n"].copy_(torch.tensor(vals, dtype=torch.int64))
 
     def dp_wait_ms(self):       # (bench.py reports it)
         return self.sync.dp_wait_ms()
@@ -1827,6 +1977,12 @@ class Trainer(object):
         trajectory is the same with and without it.  One host synchronisation per evaluator (the copy of its counts or sums)."""
         if self._val is None:
             return OrderedDict()
+        if getattr(self, "val_use_ema", False):      # `val_use_ema`: the same metrics on the shadow weights (getattr: stub trainers of the host tests)
+            with self.ema_weights():
+                return self._validate()
+        return self._validate()
+
+    def _validate(self):
         logs = OrderedDict()
         if "evaluator" in self._val:
             vs, ev = self._val["set"], self._val["evaluator"]

@@ -2536,6 +2536,61 @@ def adam_step(p, g, m, v, lr_t, beta1, beta2, eps, grad_scale=1.0, guard=None):
                float(eps), float(grad_scale), L.stream())
 
 
+# --------------------------------------------------------------------------- weight EMA (csrc/ema.hip)
+class EmaItems(object):
+    """The host array of ups_ema_item for a fixed list of (shadow, weights, rec) triples, built and validated once: `shadow` and
+    `weights` flat contiguous float32 device tensors of equal length on one device (views at any 4-byte offset), `rec` the key's row
+    of ``guard_records`` or None (never skipped).  Holds the tensors, so the pointers it carries stay valid."""
+
+    def __init__(self, triples):
+        triples = [tuple(t) for t in triples]
+        if len(triples) > L.EMA_MAX_ITEMS:
+            raise L.UpsError("ema: {} items are more than the {} one call takes".format(len(triples), L.EMA_MAX_ITEMS))
+        self.tensors, self.device = triples, None
+        self.array = (L.EmaItem * max(1, len(triples)))()
+        for i, (s, w, rec) in enumerate(triples):
+            for name, t in (("shadow", s), ("weights", w)):
+                if t.dtype != torch.float32 or not t.is_cuda or not t.is_contiguous() or t.dim() != 1:
+                    raise L.UpsError("ema: item {}: {} must be a flat contiguous float32 device bucket (got {} {})".format(
+                        i, name, tuple(t.shape), t.dtype))
+            if s.numel() != w.numel() or s.device != w.device or (self.device is not None and s.device != self.device):
+                raise L.UpsError("ema: item {}: shadow and weights must have one length and every item one device".format(i))
+            if rec is not None and (rec.dtype != torch.int64 or rec.numel() != GUARD_WORDS or rec.device != s.device
+                                    or not rec.is_contiguous()):
+                raise L.UpsError("ema: item {}: rec is one row of guard_records on the buckets' device".format(i))
+            self.device = s.device
+            it = self.array[i]
+            it.shadow, it.weights, it.count = s.data_ptr(), w.data_ptr(), s.numel()
+            it.rec = rec.data_ptr() if rec is not None else None
+
+    def __len__(self):
+        return len(self.tensors)
+
+
+def _ema_items(items):
+    return items if isinstance(items, EmaItems) else EmaItems(items)
+
+
+def ema_update(items, n_updates, omd, decay, warmup, max_blocks=0):
+    """ups_ema_update on the current stream: every item's shadow moves towards its weights by this update's 1 - decay (two launches
+    for all items; an item whose guard record says "skipped" keeps its shadow and its count).  items: an ``EmaItems`` or its list of
+    triples; n_updates: int64 [len(items)] on the device, zeroed once by the caller; omd: float32 [len(items)] device scratch."""
+    items = _ema_items(items)
+    n = len(items)
+    if n_updates.dtype != torch.int64 or omd.dtype != torch.float32 or n_updates.numel() != n or omd.numel() != n:
+        raise L.UpsError("ema_update: n_updates is int64 [{}] and omd float32 [{}]".format(n, n))
+    for t in (n_updates, omd):
+        if not t.is_cuda or not t.is_contiguous() or (items.device is not None and t.device != items.device):
+            raise L.UpsError("ema_update: n_updates and omd are contiguous tensors on the buckets' device")
+    L.call("ups_ema_update", items.array, n, float(decay), int(bool(warmup)), L.ptr(n_updates), L.ptr(omd), int(max_blocks), L.stream())
+
+
+def ema_swap(items, max_blocks=0):
+    """ups_ema_swap on the current stream: shadow and weights of every item exchange their bits in place (one launch)."""
+    items = _ema_items(items)
+    L.call("ups_ema_swap", items.array, len(items), int(max_blocks), L.stream())
+
+
 def gauss_hm(pts, stddev, h, w):
     B, K, _ = pts.shape
     out = torch.empty((B, h, w, K), dtype=torch.float32, device=pts.device)

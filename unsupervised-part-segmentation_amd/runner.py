@@ -134,7 +134,9 @@ def main(argv=None):
                          "mean error and PCK on landmark_test_csv under <root>/landmarks/<global_step>/")
     ap.add_argument("--parts", default=None, help="--transfer: comma-separated part ids taken from the column image (default: all)")
     ap.add_argument("--eval-batches", type=int, default=None, help="number of batches to evaluate (default: one epoch)")
-    ap.add_argument("-c", "--checkpoint", default=None)
+    ap.add_argument("-c", "--checkpoint", default=None,
+                    help="checkpoint to restore; with `use_ema: true` in the yaml (or --set use_ema=true) its weight-EMA shadows become "
+                         "the weights of -e / --transfer / --segment / --index / --landmarks")
     ap.add_argument("-p", "--project", default=None, help="log root (default logs/<timestamp>)")
     ap.add_argument("--num_steps", type=int, default=None)
     ap.add_argument("--set", nargs="*", default=[], help="key=value overrides (yaml-parsed)")

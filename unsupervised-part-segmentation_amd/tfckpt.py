@@ -305,3 +305,12 @@ def to_trainer_state(bundle):
         else:
             other[name] = arr
     return params, m, v, other
+
+
+EMA_SUFFIX = "/ExponentialMovingAverage"      # tf.train.ExponentialMovingAverage names a variable's shadow `<var>/ExponentialMovingAverage`
+
+
+def pop_shadows(other):
+    """Take the weight-EMA shadows (``<var>/ExponentialMovingAverage``) out of ``to_trainer_state``'s `other` -> {variable name: array}."""
+    names = [n for n in other if n.endswith(EMA_SUFFIX)]
+    return {n[:-len(EMA_SUFFIX)]: other.pop(n) for n in names}
