@@ -613,6 +613,56 @@ int ups_segment_render_guided(const float* soft, int32_t n, int32_t S, int32_t P
                               const uint8_t* colors, double alpha, uint8_t* labels, uint8_t* overlay, uint8_t* confidence,
                               int32_t* counts, void* stream);
 
+/* ---------------------------------------------------------------- part coherence (csrc/components.hip)
+ * Connected components of integer label maps, their sizes, per-part statistics and one round of speck clean-up.  Added by name,
+ * without a new UPS_ABI_VERSION, as the entries above.  Everything is integer arithmetic; these definitions are the specification
+ * (DESIGN.md section 8 "Part coherence"; tests/components_ref.py restates them twice in NumPy and the device results are equal).
+ *
+ * Images and tables.  A launch covers n <= 65535 images, image i of its own size (h_i, w_i), 1 <= h w <= 2^20, packed into planes of
+ *   `total` elements by the table of ups_segment_render (table_host / table, 4 words per image, the same checks).
+ * Labels.  `labels` is uint8 [total] (label_bytes = 1) or int64 [total] (label_bytes = 8).  A pixel is VALID if 0 <= label < P,
+ *   1 <= P <= 255.  An invalid pixel belongs to no component and is never a neighbour.
+ * Adjacency.  conn = 4: pixels that share an edge; conn = 8: an edge or a corner.  Always inside one image: x = w - 1 is not adjacent
+ *   to x = 0 of the next row, and no pixel of image i is adjacent to one of image i + 1.
+ * Components.  Two valid pixels of equal label are in one component if a chain of adjacent pixels of that label joins them.
+ *   comp int32 [total]: the smallest in-image index y w + x of the pixel's component; -1 at an invalid pixel; the alignment gaps are
+ *   not written.  A function of the map alone: two launches give the same bytes.
+ *   err int32 [1]: |= 1 when a label-chasing loop reached its bound (h w steps of a find, 2 h w retries of a union): a bug, never
+ *   expected.  The caller reads it when it next synchronises.  scratch: ups_label_components_scratch_bytes(total) = 0 bytes (comp is the
+ *   union-find's parent array); may be NULL.
+ * Sizes and statistics (ups_label_component_stats; comp is ups_label_components' of the same labels).
+ *   area int32 [total]: the pixel count of the pixel's component, 0 at an invalid pixel.
+ *   stats int32 [n, P, 4], ADDED to (caller-zeroed or accumulating): [0] += the pixels of part p, [1] += its components,
+ *   [2] = max(itself, the area of its largest component), [3] += its components with area < small (small >= 0).
+ *   invalid int32 [1] += the invalid pixels.  scratch: ups_label_component_stats_scratch_bytes(total) = 4 total bytes, 4-byte aligned.
+ * Clean-up, one round (ups_label_components_clean; comp and area as above), threshold min_area >= 1.
+ *   A component is SMALL if area < min_area.  For a small component c of part p, votes[q] counts the ordered pairs (pixel k of c, one
+ *   of k's FOUR edge neighbours k' inside the image -- whatever conn was) with k' valid, the component of k' not small and
+ *   label[k'] = q.  If the largest vote is positive every pixel of c takes the first q of maximal vote; otherwise c keeps its label.
+ *   All decisions are taken from the input map.  out (the width of labels; out == labels is allowed) equals the input everywhere
+ *   else, invalid values included; the gaps are not written.  changed int32 [1] += the pixels whose label changed.
+ *   src, colors, overlay, confidence, counts: each may be NULL.  A relabelled pixel's overlay is blended anew from src with
+ *   ups_segment_render's blend (colors alone when src is NULL; colors is required with overlay), its confidence byte becomes 0, and
+ *   counts[i, old] -= 1, counts[i, new] += 1.
+ *   scratch: ups_label_components_clean_scratch_bytes(total) = 12 total bytes, independent of P: one vote counter and a running
+ *   (best vote, best q) pair per element, one pass per part.
+ * UPS_E_UNSUPPORTED: P > 255.  UPS_E_ARG, nothing launched: a NULL required pointer, label_bytes not 1 or 8, n outside 1 .. 65535,
+ * P < 1, conn not 4 or 8, small < 0, min_area < 1, h w > 2^20, a table ups_segment_render refuses, overlay without colors, alpha
+ * outside [0, 1], int64 labels or out that are not 8-byte aligned. */
+int32_t ups_components_tile(void);
+size_t ups_label_components_scratch_bytes(int64_t total);
+size_t ups_label_component_stats_scratch_bytes(int64_t total);
+size_t ups_label_components_clean_scratch_bytes(int64_t total);
+int ups_label_components(const void* labels, int32_t label_bytes, int32_t n, const int32_t* table_host, const int32_t* table,
+                         int64_t total, int32_t P, int32_t conn, int32_t* comp, int32_t* err, void* scratch, void* stream);
+int ups_label_component_stats(const void* labels, int32_t label_bytes, const int32_t* comp, int32_t n, const int32_t* table_host,
+                              const int32_t* table, int64_t total, int32_t P, int32_t small, int32_t* area, int32_t* stats,
+                              int32_t* invalid, void* scratch, void* stream);
+int ups_label_components_clean(const void* labels, int32_t label_bytes, const int32_t* comp, const int32_t* area, int32_t n,
+                               const int32_t* table_host, const int32_t* table, int64_t total, int32_t P, int32_t min_area, void* out,
+                               int32_t* changed, const uint8_t* src, const uint8_t* colors, double alpha, uint8_t* overlay,
+                               uint8_t* confidence, int32_t* counts, void* scratch, void* stream);
+
 /* ---------------------------------------------------------------- part-appearance index (csrc/partindex.hip)
  * Nearest neighbours and k-means on a bank of per-part appearance codes (TrainModel.encode_parts): what deepfashion/code/eval/eval_02's
  * make_clusters does off-line with scikit-learn.  Restated in NumPy float64 by tests/partindex_ref.py with equal bits.

@@ -21,7 +21,7 @@ build_one() {
 }
 pids=()
 for f in $UPS_SOURCES; do
-  if [ ! -f $B/$f.o ] || [ $f.hip -nt $B/$f.o ] || [ common.h -nt $B/$f.o ] || [ env.h -nt $B/$f.o ] || [ tile.h -nt $B/$f.o ] || [ optim.h -nt $B/$f.o ] || [ build.sh -nt $B/$f.o ] || [ flags.sh -nt $B/$f.o ] || [ ../../include/upsparts_hip.h -nt $B/$f.o ]; then
+  if [ ! -f $B/$f.o ] || [ $f.hip -nt $B/$f.o ] || [ common.h -nt $B/$f.o ] || [ env.h -nt $B/$f.o ] || [ tile.h -nt $B/$f.o ] || [ optim.h -nt $B/$f.o ] || [ segment_common.h -nt $B/$f.o ] || [ build.sh -nt $B/$f.o ] || [ flags.sh -nt $B/$f.o ] || [ ../../include/upsparts_hip.h -nt $B/$f.o ]; then
     build_one $f &
     pids+=($!)
   fi

@@ -28,15 +28,21 @@
 // non-zero bins to counts[image] with one global integer atomic per part: integer sums, independent of geometry and block order.
 // `counts` is ADDED to (caller-zeroed, or holding earlier launches' counts), as ups_part_confusion's.
 #include "common.h"
+#include "segment_common.h"
 
 #pragma clang fp contract(off)
 
 namespace {
 
+using ups_segment::blend;
+using ups_segment::check_table;
+using ups_segment::to_byte;
+
 constexpr int kBlock = 256;                      // threads per block
 constexpr int kPerLane = 4;                      // consecutive pixels of one lane: one dword of labels
-constexpr int kChunk = kBlock * kPerLane;        // pixels of one block: 1024 (ops.SEGMENT_CHUNK)
-constexpr int kWords = 4;                        // int32 words per table row: pixel_offset, h, w, first_block
+constexpr int kChunk = ups_segment::kChunk;      // pixels of one block: 1024 (ops.SEGMENT_CHUNK)
+constexpr int kWords = ups_segment::kWords;      // int32 words per table row: pixel_offset, h, w, first_block
+static_assert(kChunk == kBlock * kPerLane, "a block covers one chunk");
 constexpr int kMaxP = 255;                       // a label is a byte
 static_assert(kBlock == 256, "the histogram is cleared one bin per thread");
 
@@ -48,10 +54,6 @@ __device__ __forceinline__ void source_coord(int i, int n, int S, int& i0, int& 
     i0 = (int)fl;
     i1 = min(i0 + 1, S - 1);
     f = s - fl;
-}
-
-__device__ __forceinline__ unsigned to_byte(double v) {          // clamp(floor(v + 0.5), 0, 255)
-    return (unsigned)fmin(fmax(floor(v + 0.5), 0.0), 255.0);
 }
 
 __global__ __launch_bounds__(kBlock) void segment_render_kernel(const float* __restrict__ soft, const int* __restrict__ table, int n,
@@ -140,7 +142,7 @@ __global__ __launch_bounds__(kBlock) void segment_render_kernel(const float* __r
                         const int e = 3 * k + c;
                         const unsigned col = scol[arg * 3 + c];
                         unsigned o = col;
-                        if (src) o = to_byte(alpha * (double)col + oma * (double)((sw[e >> 2] >> (8 * (e & 3))) & 255u));
+                        if (src) o = blend(alpha, oma, col, (sw[e >> 2] >> (8 * (e & 3))) & 255u);
                         ow[e >> 2] |= o << (8 * (e & 3));
                     }
                 }
@@ -381,7 +383,7 @@ __global__ __launch_bounds__(kBlock) void segment_render_guided_kernel(const flo
 #pragma unroll
                     for (int c = 0; c < 3; ++c) {
                         const int e = 3 * k + c;
-                        const unsigned o = to_byte(alpha * (double)scol[arg * 3 + c] + oma * (double)px[c]);
+                        const unsigned o = blend(alpha, oma, scol[arg * 3 + c], (unsigned)px[c]);
                         ow[e >> 2] |= o << (8 * (e & 3));
                     }
                 }
@@ -430,24 +432,6 @@ __global__ __launch_bounds__(kBlock) void segment_render_guided_kernel(const flo
             if (v) atomicAdd(&counts[(long long)img * P + tid], v);
         }
     }
-}
-
-// the checks of a packing table, shared by the launchers: UPS_OK and the number of chunks (the grid of the render kernels)
-int check_table(const int32_t* table_host, int n, long long total, long long* blocks_out) {
-    long long blocks = 0, end = 0;
-    for (int i = 0; i < n; ++i) {
-        const int32_t* r = table_host + (long long)i * kWords;
-        const long long off = r[0], h = r[1], w = r[2];
-        UPS_CHECK_ARG(h >= 1 && w >= 1 && h * w <= 0x7fffffffLL);
-        UPS_CHECK_ARG(off >= 0 && (off & 15) == 0);
-        UPS_CHECK_ARG(off >= end && off + h * w <= total);                   // ascending, no overlap, inside the planes
-        UPS_CHECK_ARG(r[3] == blocks);                                       // the prefix sum of the chunk counts
-        end = off + h * w;
-        blocks += (h * w + kChunk - 1) / kChunk;
-        UPS_CHECK_ARG(blocks <= 0x7fffffffLL);
-    }
-    *blocks_out = blocks;
-    return UPS_OK;
 }
 
 }  // namespace

@@ -13,6 +13,8 @@ Label-free metrics (`val_metrics` / `eval_metrics`: reconstruction, parts; no co
 `equivariance`: ``EquivarianceEvaluator`` warps each view with its own thin-plate spline, runs the pose path once over originals and
 warped copies and collects ups_part_equivariance's counts; ``equivariance_from_counts`` is the pure step, ``equivariance_host`` the
 NumPy route for more than 32 parts.
+`coherence`: ``CoherenceEvaluator`` labels the connected components of the part maps (ups_label_components) and collects
+ups_label_component_stats' per-part table; ``coherence_from_stats`` is the pure step, ``coherence_host`` the NumPy route.
 """
 import logging
 import os
@@ -604,12 +606,151 @@ def equivariance_uniforms(n, seed):
     return torch.rand(int(n), tps.N_UNIFORMS, generator=gen, dtype=torch.float32)
 
 
-def validation_logs(rec=None, usage=None, rec_loss=None, equiv=None):
+# ------------------------------------------------------------------ part coherence: connected components of the part maps (`coherence`)
+def coherence_from_stats(stats, HW):
+    """stats [n,P,4] integers per image and part (ups_label_component_stats: pixels, components, largest component, components smaller
+    than the speck area), HW pixels per image -> a flat dict:
+      "components_<p>"     the mean component count of part p over the images where it is present; -1.0 if it is present nowhere
+      "fragmentation_<p>"  1 - sum_i largest[i,p] / sum_i pixels[i,p] on the pooled integers (0: every image's part p is one region);
+                           -1.0 if it is present nowhere
+      "fragmentation"      the same pooled over the parts too (-1.0 without a single valid pixel)
+      "specks"             the small components per image."""
+    stats = np.asarray(stats).astype(np.int64)
+    if stats.ndim != 3 or stats.shape[0] == 0 or stats.shape[2] != 4:
+        raise ValueError("coherence_from_stats: stats [n >= 1,P,4] expected (got {})".format(stats.shape))
+    px, comps, largest, small = (stats[:, :, k] for k in range(4))
+    if (px.sum(axis=1) > int(HW)).any() or (stats < 0).any():
+        raise ValueError("coherence_from_stats: more pixels in an image's parts than the image's {} (or a negative count)".format(HW))
+    res = {}
+    present = px > 0
+    for p in range(stats.shape[1]):
+        k = int(present[:, p].sum())
+        res["components_{}".format(p)] = float(comps[present[:, p], p].sum() / k) if k else -1.0
+        tot = int(px[:, p].sum())
+        res["fragmentation_{}".format(p)] = float(1.0 - largest[:, p].sum() / tot) if tot else -1.0
+    tot = int(px.sum())
+    res["fragmentation"] = float(1.0 - largest.sum() / tot) if tot else -1.0
+    res["specks"] = float(small.sum() / stats.shape[0])
+    return res
+
+
+def _components_host(lab, P, conn):
+    """comp int64 [h,w] of one map in NumPy: every valid pixel starts as its own index and takes the minimum over its equally
+    labelled neighbours, then jumps to its representative's representative, until nothing changes (at most h * w sweeps)."""
+    h, w = lab.shape
+    ok = (lab >= 0) & (lab < P)
+    big = h * w
+    comp = np.where(ok, np.arange(big, dtype=np.int64).reshape(h, w), big)
+    shifts = [(0, 1), (1, 0)] + ([(1, 1), (1, -1)] if conn == 8 else [])
+    for _ in range(big + 1):
+        new = comp.copy()
+        for dy, dx in shifts:                                # the pair (y, x) / (y + dy, x + dx), both ways
+            a = (slice(0, h - dy), slice(max(0, -dx), w - max(0, dx)))
+            b = (slice(dy, h), slice(max(0, dx), w - max(0, -dx)))
+            same = ok[a] & ok[b] & (lab[a] == lab[b])
+            lo = np.minimum(new[a], new[b])
+            new[a] = np.where(same, lo, new[a])
+            new[b] = np.where(same, np.minimum(lo, new[b]), new[b])       # (a and b overlap: keep what the line above lowered)
+        flat = new.reshape(-1)
+        idx = np.nonzero(flat < big)[0]
+        flat[idx] = flat[flat[idx]]                          # the representative's representative: the same component, no larger
+        if np.array_equal(new, comp):
+            break
+        comp = new
+    else:
+        raise RuntimeError("coherence_host: the propagation did not settle in h * w sweeps")
+    return np.where(ok, comp, -1)
+
+
+def coherence_host(pred, P, conn=8, small=0):
+    """ups_label_components + ups_label_component_stats in NumPy (the host route, where the device cannot be used):
+    pred [N,h,w] integers -> (stats [N,P,4] int32, invalid)."""
+    pred = np.asarray(pred)
+    if pred.ndim != 3 or conn not in (4, 8) or P < 1:
+        raise ValueError("coherence_host: pred [N,h,w], conn 4 or 8, P >= 1 (got {}, {}, {})".format(pred.shape, conn, P))
+    pred = pred.astype(np.int64)
+    N, h, w = pred.shape
+    stats = np.zeros((N, P, 4), dtype=np.int32)
+    invalid = 0
+    for i in range(N):
+        comp = _components_host(pred[i], P, conn).reshape(-1)
+        lab = pred[i].reshape(-1)
+        invalid += int((comp < 0).sum())
+        area = np.bincount(comp[comp >= 0], minlength=h * w)
+        roots = np.nonzero(comp == np.arange(h * w))[0]
+        for p in range(P):
+            a = area[roots[lab[roots] == p]]
+            stats[i, p] = (int(a.sum()), a.size, int(a.max()) if a.size else 0, int((a < small).sum()))
+    return stats, invalid
+
+
+class CoherenceEvaluator(object):
+    """Whether each part is one region or many, with the pixels left on the device: ``update`` runs ups_label_components and
+    ups_label_component_stats on the part maps into a device buffer that grows by one [P,4] row per image; ``result`` makes one copy
+    and returns ``coherence_from_stats``.  speck_area: components of fewer pixels count as specks.  n_parts above 255 (a label is a
+    byte in the kernels' tables) is computed by ``coherence_host``, with one logged line."""
+
+    def __init__(self, device, n_parts, conn=8, speck_area=0):
+        import torch
+        self.device, self.P, self.conn, self.speck_area = device, int(n_parts), int(conn), int(speck_area)
+        if self.P < 1 or self.conn not in (4, 8) or self.speck_area < 0:
+            raise ValueError("CoherenceEvaluator: n_parts >= 1, conn 4 or 8, speck_area >= 0 (got {}, {}, {})".format(
+                n_parts, conn, speck_area))
+        self.on_device = self.P <= 255
+        if not self.on_device:
+            LOG.info("CoherenceEvaluator: P = %d exceeds the kernels' 255: labelling on the host", self.P)
+        self._acc = _Accumulator("CoherenceEvaluator", device, [("stats", (self.P, 4), torch.int32, True)], self.on_device)
+        self._err = None
+
+    n = property(lambda self: self._acc.n)
+    HW = property(lambda self: self._acc.HW)
+
+    def reset(self):
+        self._acc.reset()
+        self._err = None
+
+    def update(self, pred, valid=None):
+        """pred [n,h,w] int64 (out_parts_hard); only the first `valid` images count."""
+        import torch
+        from . import ops
+        n = pred.shape[0] if valid is None else int(valid)
+        if n == 0:
+            return
+        pred = pred[:n]
+        if pred.dim() != 3:
+            raise ValueError("CoherenceEvaluator.update: pred [n,h,w] expected (got {})".format(tuple(pred.shape)))
+        self._acc.same_pixels("maps", int(pred[0].numel()))
+        if not self.on_device:
+            s, bad = coherence_host(pred.cpu().numpy(), self.P, self.conn, self.speck_area)
+            return self._acc.add_host(n, (s,), bad)
+        if self._err is None:
+            self._err = torch.zeros(1, dtype=torch.int32, device=pred.device)
+        pred = pred.contiguous()
+        comp, _ = ops.label_components(pred, self.P, conn=self.conn, err=self._err)
+        ops.label_component_stats(pred, comp, self.P, small=self.speck_area, stats=self._acc.take(n)[0], invalid=self._acc.invalid)
+
+    def sums(self):
+        """(stats [n,P,4] int32, invalid) as NumPy: the one copy to the host."""
+        (stats,), invalid = self._acc.fetch()
+        return stats, invalid
+
+    def result(self):
+        from . import ops
+        stats, = self._acc.finish("pixel(s) with a part id outside [0, {}) belong to no component".format(self.P))
+        if self._err is not None:
+            ops.components_check(self._err)
+        return coherence_from_stats(stats, self.HW)
+
+
+def validation_logs(rec=None, usage=None, rec_loss=None, equiv=None, coherence=None):
     """The `val/` keys of the label-free metrics: rec = ``reconstruction_from_sums`` (val/mse, val/l1, val/psnr, val/ssim), rec_loss the
     perceptual reconstruction term (val/rec), usage = ``usage_from_counts`` (val/part_area_<p>, val/parts_active, val/confidence,
     val/entropy), equiv = ``equivariance_from_counts`` (val/equiv_agreement, val/equiv_miou, val/equiv_iou_<p>, val/equiv_tv,
-    val/equiv_valid).  All of them sort before val/steps_done."""
+    val/equiv_valid), coherence = ``coherence_from_stats`` (val/fragmentation, val/fragmentation_<p>, val/components_<p>, val/specks).
+    All of them sort before val/steps_done."""
     logs = {}
+    if coherence is not None:
+        logs.update({"val/" + k: v for k, v in coherence.items()})
     if equiv is not None:
         logs.update({"val/equiv_iou_{}".format(p): v for p, v in enumerate(equiv["iou"])})
         logs.update({"val/equiv_" + k: equiv[k] for k in ("agreement", "miou", "tv", "valid")})

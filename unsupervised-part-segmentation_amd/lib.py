@@ -183,6 +183,14 @@ _SIGS = {
     "ups_segment_render": ([_P, _I, _I, _I, C.POINTER(_I), _P, _L, _P, _P, C.c_double, _P, _P, _P, _P, _P], C.c_int),
     "ups_segment_guide": ([_P, _I, _I, C.POINTER(_I), _P, _L, _P, _P], C.c_int),
     "ups_segment_render_guided": ([_P, _I, _I, _I, C.POINTER(_I), _P, _L, _P, _P, _P, _I, _P, C.c_double, _P, _P, _P, _P, _P], C.c_int),
+    "ups_components_tile": ([], _I),
+    "ups_label_components_scratch_bytes": ([_L], _Z),
+    "ups_label_component_stats_scratch_bytes": ([_L], _Z),
+    "ups_label_components_clean_scratch_bytes": ([_L], _Z),
+    "ups_label_components": ([_P, _I, _I, C.POINTER(_I), _P, _L, _I, _I, _P, _P, _P, _P], C.c_int),
+    "ups_label_component_stats": ([_P, _I, _P, _I, C.POINTER(_I), _P, _L, _I, _I, _P, _P, _P, _P, _P], C.c_int),
+    "ups_label_components_clean": ([_P, _I, _P, _P, _I, C.POINTER(_I), _P, _L, _I, _I, _P, _P, _P, _P, C.c_double, _P, _P, _P, _P, _P],
+                                   C.c_int),
     "ups_part_knn_tile": ([], _I),
     "ups_part_kmeans_chunk": ([], _I),
     "ups_part_knn": ([_P, _P, _I, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P], C.c_int),

@@ -241,7 +241,7 @@ class TrainModel(object):
 
     @torch.no_grad()
     def export_segments(self, views, sizes, sources=None, outputs=("labels", "overlay"), alpha=0.5, colors=None, maps=None,
-                        after_launch=None, refine=None):
+                        after_launch=None, refine=None, clean=None):
         """Part maps of `views` [n,S,S,3] rendered at their own sizes: one ``segment_soft`` and ONE ups_segment_render launch
         (``ops.segment_render``: label = first maximal part of the bilinearly resampled soft map, decided in fp64).
         sizes [(h_i, w_i)]; sources: None or n uint8 [h_i,w_i,3] images the overlay blends with (weight 1 - alpha);
@@ -250,6 +250,11 @@ class TrainModel(object):
         kernel is launched and before the copies are queued (a profiler's lap).
         refine: None, or {"radius": R, "sigma": sigma}: the edge-aware route of ``ops.segment_render`` (joint bilateral upsampling
         guided by `sources`, which are then required and uploaded also when no overlay is wanted).
+        clean: None, or {"min_area": A, "rounds": R, "connectivity": 4 | 8}: speck clean-up of the rendered labels before anything is
+        copied -- up to R rounds of ``ops.label_components`` -> ``label_component_stats`` -> ``label_components_clean`` on the packed
+        labels plane, in place: a component of fewer than A pixels takes the label its edge neighbours vote for; overlay, confidence
+        (0 at a relabelled pixel) and the counts follow.  One int32 is read per round (it ends the rounds when nothing changed);
+        "relabelled" in the result is the number of pixels that changed.
         The per-part pixel counts are always taken.  The planes are copied into pinned host buffers on a side stream behind an event
         (as the image logs' canvases): nothing here waits for the device.  Returns {"table", "total", "host": {name: pinned
         tensor, "counts" included}, "views": {name: [per-image host views]}, "ready": the copies' event, "soft", "hard": the device
@@ -261,8 +266,15 @@ class TrainModel(object):
         hard, soft = self.segment_soft(views) if maps is None else maps
         if colors is None and "overlay" in outputs:
             colors = IL.mask_color_bytes(IL.mask_colors01(self.n_parts))
-        res = ops.segment_render(soft, sizes, src=sources if "overlay" in outputs or refine is not None else None, colors=colors,
-                                 alpha=alpha, want=outputs + ("counts",), refine=refine)
+        src = sources if "overlay" in outputs or refine is not None else None
+        want = outputs + ("counts",)
+        if clean is not None:
+            if src is not None and not torch.is_tensor(src):    # the clean-up blends from the packed sources too: packed once, here
+                table, total = ops.segment_table(sizes)
+                src = ops.segment_pack_sources(src, table, total).to(dev, non_blocking=True)
+            want = want if "labels" in want else want + ("labels",)
+        res = ops.segment_render(soft, sizes, src=src, colors=colors, alpha=alpha, want=want, refine=refine)
+        relabelled = self._clean_segments(res, src, colors, alpha, clean) if clean is not None else 0
         if after_launch is not None:
             after_launch()
         if self._seg_stream is None:
@@ -277,7 +289,29 @@ class TrainModel(object):
                 host[k].copy_(res[k], non_blocking=True)
             ready = side.record_event()
         return {"table": res["table"], "total": res["total"], "host": host, "ready": ready, "soft": soft, "hard": hard,
-                "views": {k: ops.segment_views(host[k], res["table"]) for k in outputs}}
+                "views": {k: ops.segment_views(host[k], res["table"]) for k in outputs}, "relabelled": relabelled}
+
+    def _clean_segments(self, res, src, colors, alpha, clean):
+        """``export_segments``' clean-up rounds on the planes of a ``segment_render`` result, in place -> the pixels relabelled."""
+        if not isinstance(clean, dict) or set(clean) != {"min_area", "rounds", "connectivity"}:
+            raise L.UpsError("export_segments: clean is None or {{'min_area', 'rounds', 'connectivity'}} (got {!r})".format(clean))
+        rounds = clean["rounds"]
+        if isinstance(rounds, bool) or not isinstance(rounds, int) or not 1 <= rounds <= 4:
+            raise L.UpsError("export_segments: clean rounds is an integer in 1 .. 4 (got {!r})".format(rounds))
+        table, P = (res["table"], res["table_dev"], res["total"]), self.n_parts
+        err, total = None, 0
+        for _ in range(rounds):
+            comp, err = ops.label_components(res["labels"], P, conn=clean["connectivity"], table=table, err=err)
+            area, _, _ = ops.label_component_stats(res["labels"], comp, P, table=table)
+            _, changed = ops.label_components_clean(res["labels"], comp, area, P, clean["min_area"], table=table, out=res["labels"],
+                                                    src=src, colors=colors, alpha=alpha, overlay=res.get("overlay"),
+                                                    confidence=res.get("confidence"), counts=res["counts"])
+            moved = int(changed.item())                 # the one int32 read of the round
+            total += moved
+            if moved == 0:
+                break
+        ops.components_check(err)
+        return total
 
     @torch.no_grad()
     def encode_appearance(self, views):
@@ -486,6 +520,8 @@ def gram_weight_of(config, logger=None):
 
 
 VAL_METRICS = ("iou", "reconstruction", "parts", "equivariance")
+VAL_METRICS_MORE = ("coherence",)       # accepted beside VAL_METRICS, and ordered after them
+VAL_METRICS_ALL = VAL_METRICS + VAL_METRICS_MORE
 
 
 def validation_metrics(config, key="val_metrics", default=("iou",)):
@@ -495,13 +531,27 @@ def validation_metrics(config, key="val_metrics", default=("iou",)):
     if v is None:
         return list(default)
     if isinstance(v, str) or not isinstance(v, (list, tuple)):
-        raise ValueError("{}: a list drawn from {} is expected (got {!r})".format(key, " | ".join(VAL_METRICS), v))
-    unknown = [m for m in v if m not in VAL_METRICS]
+        raise ValueError("{}: a list drawn from {} is expected (got {!r})".format(key, " | ".join(VAL_METRICS_ALL), v))
+    unknown = [m for m in v if m not in VAL_METRICS_ALL]
     if unknown:
-        raise ValueError("{}: unknown metric(s) {} ({})".format(key, unknown, " | ".join(VAL_METRICS)))
+        raise ValueError("{}: unknown metric(s) {} ({})".format(key, unknown, " | ".join(VAL_METRICS_ALL)))
     if not v and key == "val_metrics":
-        raise ValueError("val_metrics is empty: with val_freq set, list at least one of {}".format(" | ".join(VAL_METRICS)))
-    return [m for m in VAL_METRICS if m in v]
+        raise ValueError("val_metrics is empty: with val_freq set, list at least one of {}".format(" | ".join(VAL_METRICS_ALL)))
+    return [m for m in VAL_METRICS_ALL if m in v]
+
+
+def coherence_config(config):
+    """The keys of the `coherence` metric, decided from the config alone -> (connectivity, speck area in pixels of the S x S part map):
+    `val_coherence_connectivity` (8; 4 or 8) and `val_speck_area` (0.001: a share of S^2 like `val_min_part_area`, converted with ceil;
+    a component of fewer pixels is a speck).  ValueError with the reason."""
+    conn = config.get("val_coherence_connectivity", 8)
+    if isinstance(conn, bool) or conn not in (4, 8):
+        raise ValueError("val_coherence_connectivity: 4 or 8 is expected (got {!r})".format(conn))
+    share = config.get("val_speck_area", 0.001)
+    if isinstance(share, bool) or not isinstance(share, (int, float)) or not 0.0 <= share <= 1.0:
+        raise ValueError("val_speck_area: a share of the map in [0, 1] is expected (got {!r})".format(share))
+    S = int(config.get("spatial_size", 256))
+    return int(conn), int(math.ceil(float(share) * S * S))
 
 
 def equivariance_tps_parameters(config):
@@ -535,6 +585,8 @@ def check_validation_config(config):
             config.get("spatial_size")))
     if "equivariance" in metrics:
         equivariance_tps_parameters(config)
+    if "coherence" in metrics:
+        coherence_config(config)
 
 
 def step_guard_config(config):
@@ -1949,7 +2001,7 @@ class Trainer(object):
             vs = _data.ValidationSet(cfg)
             ev = evalutil.PartEvaluator(self.model, int(cfg.get("eval_n_labels", 32)), lut=cfg.get("eval_label_lut"))
             self._val.update({"set": vs, "evaluator": ev})
-        if "reconstruction" in metrics or "parts" in metrics or "equivariance" in metrics:
+        if "reconstruction" in metrics or "parts" in metrics or "equivariance" in metrics or "coherence" in metrics:
             # the label-free metrics: one forward per chunk of B pairs (reconstruction, parts); equivariance takes the chunk's view0
             self._val["pairs"] = _data.ValidationPairs(cfg)
             if "reconstruction" in metrics:
@@ -1957,6 +2009,8 @@ class Trainer(object):
             if "parts" in metrics:
                 self._val["usage"] = evalutil.PartUsageEvaluator(self.device, self.model.n_parts,
                                                                  float(cfg.get("val_min_part_area", 0.005)))
+            if "coherence" in metrics:
+                self._val["coherence"] = evalutil.CoherenceEvaluator(self.device, self.model.n_parts, *coherence_config(cfg))
             if "equivariance" in metrics:
                 # one warp per validation image, drawn ONCE from a CPU generator seeded by `val_seed` (row i: image i) -- nothing is
                 # drawn from the trainer's generators.  Singular systems count where `use_tps` counts them.
@@ -2024,11 +2078,13 @@ class Trainer(object):
         those tensors, averaged over the chunks.  parts: out_parts_soft / out_parts_hard -> val/part_area_<p>, val/parts_active,
         val/confidence, val/entropy (ups_part_usage).  equivariance: the chunk's view0 against its warped copy, one more pass of the pose
         path per chunk and no forward of its own (``evalutil.EquivarianceEvaluator``) -> val/equiv_agreement, val/equiv_miou,
-        val/equiv_iou_<p>, val/equiv_tv, val/equiv_valid.  One copy to the host per evaluator, and one for val/rec."""
+        val/equiv_iou_<p>, val/equiv_tv, val/equiv_valid.  coherence: the connected components of out_parts_hard (``evalutil.CoherenceEvaluator``;
+        listed without reconstruction / parts it runs ``model.segment`` itself) -> val/fragmentation, val/fragmentation_<p>,
+        val/components_<p>, val/specks.  One copy to the host per evaluator, and one for val/rec."""
         from . import evalutil
         val, model = self._val, self.model
-        pairs, rec, usage, equiv = val["pairs"], val.get("rec"), val.get("usage"), val.get("equiv")
-        for ev in (rec, usage, equiv):
+        pairs, rec, usage, equiv, coher = val["pairs"], val.get("rec"), val.get("usage"), val.get("equiv"), val.get("coherence")
+        for ev in (rec, usage, equiv, coher):
             if ev is not None:
                 ev.reset()
         B = pairs.batch_size
@@ -2039,6 +2095,8 @@ class Trainer(object):
             if equiv is not None:
                 equiv.update(model, chunk["view0"], val["equiv_uniforms"][ci * B:(ci + 1) * B])
             if rec is None and usage is None:
+                if coher is not None:               # listed without reconstruction / parts: a pass of the pose path of its own
+                    coher.update(model.segment(chunk["view0"]))
                 continue
             out = model.forward(chunk, noise=None)
             if rec is not None:
@@ -2049,9 +2107,12 @@ class Trainer(object):
                                                gram_weight=self.gram_weight).detach().double().reshape(1))
             if usage is not None:
                 usage.update(out["out_parts_soft"], out["out_parts_hard"])
+            if coher is not None:
+                coher.update(out["out_parts_hard"])
         rec_loss = float(torch.cat(rec_terms).mean()) if rec_terms else None
         return evalutil.validation_logs(rec.result() if rec is not None else None, usage.result() if usage is not None else None, rec_loss,
-                                        equiv=equiv.result() if equiv is not None else None)
+                                        equiv=equiv.result() if equiv is not None else None,
+                                        coherence=coher.result() if coher is not None else None)
 
     def iterate(self, batch_iterator, num_steps=None, log_fn=print):
         """edflow's session loop with its hooks.  LoggingHook cadence as cub/train/log.txt:221-860 shows it (an IntervalHook whose

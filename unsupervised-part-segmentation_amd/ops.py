@@ -2268,6 +2268,186 @@ def segment_views(plane, table):
     return [plane[off:off + h * w].view((h, w) + tail) for off, h, w, _ in table.tolist()]
 
 
+# --------------------------------------------------------------------------- part coherence (csrc/components.hip)
+COMPONENTS_TILE = 32            # tile edge of the LDS stage of ups_label_components (checked against the library on first use)
+COMPONENTS_MAX_HW = 1 << 20     # pixels per image
+COMPONENTS_MAX_P = 255
+_COMPONENTS_TABLES = {}         # (N, h, w, device) -> the table of a regular batch, host and device: built once, no copy per call
+
+
+class _ComponentsLayout(object):
+    """Where the images of one call lie: the packed planes' table (host, device), total, n, and whether the caller's tensors are
+    a regular [N,h,w] batch (`batch`: (N, h, w); its row stride in the plane is h * w rounded up to SEGMENT_ALIGN) or packed planes."""
+
+    def __init__(self, fn, labels, sizes, table):
+        import numpy as np
+        self.fn = fn
+        if not torch.is_tensor(labels) or not labels.is_cuda or labels.dtype not in (torch.uint8, torch.int64) or labels.numel() == 0:
+            raise L.UpsError("{}: labels uint8 or int64 on the device expected (got {})".format(
+                fn, (tuple(labels.shape), labels.dtype, labels.device) if torch.is_tensor(labels) else type(labels)))
+        self.device = labels.device
+        self.label_dtype = labels.dtype
+        if sizes is None and table is None:
+            if labels.dim() != 3:
+                raise L.UpsError("{}: a regular batch is [N,h,w]; packed planes need `sizes` (got {})".format(fn, tuple(labels.shape)))
+            N, h, w = (int(v) for v in labels.shape)
+            key = (N, h, w, self.device)
+            if key not in _COMPONENTS_TABLES:
+                tab, total = segment_table([(h, w)] * N)
+                _COMPONENTS_TABLES[key] = (tab, torch.from_numpy(tab).to(self.device), total)
+            self.table, self.table_dev, self.total = _COMPONENTS_TABLES[key]
+            self.batch, self.stride = (N, h, w), -(-(h * w) // SEGMENT_ALIGN) * SEGMENT_ALIGN
+        else:
+            if table is not None:
+                self.table, self.table_dev, self.total = table
+                self.table = np.ascontiguousarray(self.table, dtype=np.int32)
+            else:
+                self.table, self.total = segment_table(sizes)
+                self.table_dev = torch.from_numpy(self.table).to(self.device)
+            self.batch = None
+        self.n = len(self.table)
+        hw = self.table[:, 1].astype(np.int64) * self.table[:, 2]
+        if int(hw.max()) > COMPONENTS_MAX_HW:
+            raise L.UpsError("{}: at most 2^20 pixels per image (got {})".format(fn, int(hw.max())))
+
+    def plane(self, name, t, dtype):
+        """The packed plane [total] of a caller's input `name`: itself when it is one (or a regular batch without padding), else a
+        packed copy of the regular batch."""
+        if not torch.is_tensor(t) or t.device != self.device or t.dtype != dtype:
+            raise L.UpsError("{}: {} {} on {} expected (got {})".format(
+                self.fn, name, dtype, self.device, (tuple(t.shape), t.dtype, t.device) if torch.is_tensor(t) else type(t)))
+        if self.batch is None:
+            if tuple(t.shape) != (self.total,):
+                raise L.UpsError("{}: {} is a packed plane [{}] (got {})".format(self.fn, name, self.total, tuple(t.shape)))
+            return t.contiguous()
+        N, h, w = self.batch
+        if tuple(t.shape) != (N, h, w):
+            raise L.UpsError("{}: {} [{},{},{}] expected (got {})".format(self.fn, name, N, h, w, tuple(t.shape)))
+        if self.stride == h * w:
+            return t.contiguous().view(-1)
+        p = torch.zeros(self.total, dtype=dtype, device=self.device)
+        p.view(N, self.stride)[:, :h * w] = t.reshape(N, h * w)
+        return p
+
+    def out_plane(self, name, t, dtype, tail=()):
+        """A packed output plane: the caller's [total] + tail tensor, or new zeros (so that the gaps are defined)."""
+        return _given_or_new(self.fn, name, t, (self.total,) + tuple(tail), dtype, self.device, zero=True)
+
+    def shaped(self, p):
+        """A packed plane in the caller's form: [N,h,w] (a strided view when h * w is no multiple of 16) for a regular batch."""
+        if self.batch is None:
+            return p
+        N, h, w = self.batch
+        return p.view(N, self.stride)[:, :h * w].reshape(N, h, w) if self.stride != h * w else p.view(N, h, w)
+
+    def args(self):
+        return self.n, self.table.ctypes.data_as(C.POINTER(C.c_int32)), L.ptr(self.table_dev), self.total
+
+
+def _components_P(fn, P):
+    if isinstance(P, bool) or not isinstance(P, int) or not 1 <= P <= COMPONENTS_MAX_P:
+        raise L.UpsError("{}: P is an integer in 1 .. {} (got {!r})".format(fn, COMPONENTS_MAX_P, P))
+    _library_constants("components", components_tile=COMPONENTS_TILE)
+
+
+def components_check(err):
+    """Raise L.UpsError if the error flag of label_components is set (a label-chasing loop of the kernels reached its bound: a bug in
+    them, never a property of the map).  Reads one int32: synchronises with the stream that ran the kernels."""
+    v = int(err.reshape(-1)[0].item())
+    if v != 0:
+        raise L.UpsError("label_components: a bounded device loop reached its bound (flag {}): the component map is not valid".format(v))
+
+
+def label_components(labels, P, conn=8, sizes=None, comp=None, err=None, table=None):
+    """comp = the connected components of integer label maps (ups_label_components; the definitions: include/upsparts_hip.h "part
+    coherence", restated by tests/components_ref.py): comp[k] int32 = the smallest in-image index y * w + x of the component of pixel
+    k, -1 where the label is outside [0, P).  labels: uint8 or int64 on the device -- a regular batch [N,h,w] (sizes=None), or a
+    packed plane [total] of images of sizes [(h_i, w_i)] laid out by segment_table(sizes) (or table=(table, table_dev, total) of a
+    segment_render result).  conn: 4 or 8.  comp: a packed int32 plane [total] to reuse, default new.  err [1] int32 (default: new
+    zero): |= 1 if a device loop reached its bound; components_check(err) raises on it.  Asynchronous on the current stream.
+    Returns (comp in the form of labels, err)."""
+    fn = "label_components"
+    _components_P(fn, P)
+    if conn not in (4, 8):
+        raise L.UpsError("{}: conn is 4 or 8 (got {!r})".format(fn, conn))
+    lay = _ComponentsLayout(fn, labels, sizes, table)
+    lab = lay.plane("labels", labels, lay.label_dtype)
+    comp = lay.out_plane("comp", comp, torch.int32)
+    err = _given_or_new(fn, "err", err, (1,), torch.int32, lay.device, zero=True)
+    scratch = _scratch(L.load().ups_label_components_scratch_bytes(lay.total), lay.device)
+    n, th, td, total = lay.args()
+    L.call("ups_label_components", L.ptr(lab), lab.element_size(), n, th, td, total, P, conn, L.ptr(comp), L.ptr(err), L.ptr(scratch),
+           L.stream())
+    return lay.shaped(comp), err
+
+
+def label_component_stats(labels, comp, P, small=0, sizes=None, area=None, stats=None, invalid=None, table=None):
+    """Component sizes and per-part statistics (ups_label_component_stats).  labels, sizes, table as for label_components; comp: its
+    result for the same labels.  area int32 (packed plane to reuse, default new): the pixel count of the pixel's component, 0 where
+    invalid.  stats [n,P,4] int32 (default: new zeros; given: ADDED to): pixels, components, largest component (a maximum), components
+    with area < small.  invalid [1] int32 += the invalid pixels.  Asynchronous on the current stream.
+    Returns (area in the form of labels, stats, invalid)."""
+    fn = "label_component_stats"
+    _components_P(fn, P)
+    if isinstance(small, bool) or not isinstance(small, int) or small < 0:
+        raise L.UpsError("{}: small is an integer >= 0 (got {!r})".format(fn, small))
+    lay = _ComponentsLayout(fn, labels, sizes, table)
+    lab = lay.plane("labels", labels, lay.label_dtype)
+    comp = lay.plane("comp", comp, torch.int32)
+    area = lay.out_plane("area", area, torch.int32)
+    stats = _given_or_new(fn, "stats", stats, (lay.n, P, 4), torch.int32, lay.device, zero=True)
+    invalid = _given_or_new(fn, "invalid", invalid, (1,), torch.int32, lay.device, zero=True)
+    scratch = _scratch(L.load().ups_label_component_stats_scratch_bytes(lay.total), lay.device)
+    n, th, td, total = lay.args()
+    L.call("ups_label_component_stats", L.ptr(lab), lab.element_size(), L.ptr(comp), n, th, td, total, P, min(small, 0x7fffffff),
+           L.ptr(area), L.ptr(stats), L.ptr(invalid), L.ptr(scratch), L.stream())
+    return lay.shaped(area), stats, invalid
+
+
+def label_components_clean(labels, comp, area, P, min_area, sizes=None, out=None, changed=None, src=None, colors=None, alpha=0.5,
+                           overlay=None, confidence=None, counts=None, table=None):
+    """One round of speck clean-up (ups_label_components_clean): every component with area < min_area takes the first label of maximal
+    vote among its pixels' four edge neighbours that lie in components that are not small; without such a neighbour it stays.
+    labels, sizes, table as for label_components; comp, area: the results of label_components / label_component_stats for the same
+    labels.  out: a packed plane of labels' dtype (default new; `labels` itself is allowed for a packed plane); changed [1] int32 += the
+    relabelled pixels.  Optional planes of a segment_render result, updated at the relabelled pixels only: overlay uint8 [total,3]
+    (blended anew from src uint8 [total,3] with `colors` [P,3] and alpha, as segment_render does), confidence uint8 [total] (= 0),
+    counts int32 [n,P] (the old part -= 1, the new += 1).  Asynchronous on the current stream.
+    Returns (out in the form of labels, changed)."""
+    fn = "label_components_clean"
+    _components_P(fn, P)
+    if isinstance(min_area, bool) or not isinstance(min_area, int) or min_area < 1:
+        raise L.UpsError("{}: min_area is an integer >= 1 (got {!r})".format(fn, min_area))
+    if not 0.0 <= float(alpha) <= 1.0:
+        raise L.UpsError("{}: 0 <= alpha <= 1 (got {!r})".format(fn, alpha))
+    lay = _ComponentsLayout(fn, labels, sizes, table)
+    lab = lay.plane("labels", labels, lay.label_dtype)
+    comp = lay.plane("comp", comp, torch.int32)
+    area = lay.plane("area", area, torch.int32)
+    out = lay.out_plane("out", out, lay.label_dtype)
+    changed = _given_or_new(fn, "changed", changed, (1,), torch.int32, lay.device, zero=True)
+    if overlay is not None and colors is None:
+        raise L.UpsError("{}: the overlay needs `colors` [P,3] uint8".format(fn))
+    if colors is not None:
+        colors = torch.as_tensor(colors).to(lay.device).contiguous()
+        if colors.dtype != torch.uint8 or tuple(colors.shape) != (P, 3):
+            raise L.UpsError("{}: colors [{},3] uint8 expected (got {} {})".format(fn, P, tuple(colors.shape), colors.dtype))
+    if src is not None:
+        src = _given_or_new(fn, "src", src, (lay.total, 3), torch.uint8, lay.device)
+    if overlay is not None:
+        overlay = _given_or_new(fn, "overlay", overlay, (lay.total, 3), torch.uint8, lay.device)
+    if confidence is not None:
+        confidence = _given_or_new(fn, "confidence", confidence, (lay.total,), torch.uint8, lay.device)
+    if counts is not None:
+        counts = _given_or_new(fn, "counts", counts, (lay.n, P), torch.int32, lay.device)
+    scratch = _scratch(L.load().ups_label_components_clean_scratch_bytes(lay.total), lay.device)
+    n, th, td, total = lay.args()
+    L.call("ups_label_components_clean", L.ptr(lab), lab.element_size(), L.ptr(comp), L.ptr(area), n, th, td, total, P,
+           min(min_area, 0x7fffffff), L.ptr(out), L.ptr(changed), L.ptr(src), L.ptr(colors), float(alpha), L.ptr(overlay),
+           L.ptr(confidence), L.ptr(counts), L.ptr(scratch), L.stream())
+    return lay.shaped(out), changed
+
+
 # --------------------------------------------------------------------------- training image logs (csrc/canvas.hip): uint8 canvases
 def canvas_grid(n, cols=None):
     """(rows, cols) of tf_batch_to_canvas for n tiles (re-derived, UNVERIFIED): cols=None -> the square grid of side ceil(sqrt(n)),

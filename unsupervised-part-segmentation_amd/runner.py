@@ -195,7 +195,8 @@ def evaluate(args):
     batches (key ``gt_segmentation``) the part-IoU protocol of eval_01.py:229-383 is reported too (evalutil.py).
     ``eval_metrics: [reconstruction, parts]`` (default none) also writes metrics.yml: the label-free metrics of the trainer's
     `val_metrics` (evalutil.ReconstructionEvaluator / PartUsageEvaluator) from the same forward passes, without the perceptual term;
-    ``equivariance`` adds evalutil.EquivarianceEvaluator's numbers on each batch's view0 (one more pose-path pass per batch)."""
+    ``equivariance`` adds evalutil.EquivarianceEvaluator's numbers on each batch's view0 (one more pose-path pass per batch);
+    ``coherence`` adds evalutil.CoherenceEvaluator's (the connected components of out_parts_hard, from the same forward passes)."""
     import pickle
     import numpy as np
     from . import evalutil
@@ -236,7 +237,7 @@ def evaluate(args):
     metrics = validation_metrics(cfg, "eval_metrics", ())
     if "iou" in metrics:
         raise ValueError("eval_metrics: the part IoU is what -e writes whenever the batches carry label maps; list reconstruction | parts "
-                         "| equivariance")
+                         "| equivariance | coherence")
     if "reconstruction" in metrics and int(cfg["spatial_size"]) < 11:
         raise ValueError("eval_metrics: reconstruction needs spatial_size >= 11, the 11 x 11 SSIM window")
     rec_ev = evalutil.ReconstructionEvaluator(model.device) if "reconstruction" in metrics else None
@@ -244,6 +245,10 @@ def evaluate(args):
               if "parts" in metrics else None)
     # equivariance: every batch's view0 against its warped copy (one more pass of the pose path per batch); the uniforms of the running
     # image index come from a CPU generator seeded by `val_seed`, drawn batch by batch in that order
+    co_ev = None
+    if "coherence" in metrics:                     # the connected components of out_parts_hard, from the same forward passes
+        from .model import coherence_config
+        co_ev = evalutil.CoherenceEvaluator(model.device, model.n_parts, *coherence_config(cfg))
     eq_ev, eq_gen = None, None
     if "equivariance" in metrics:
         from .model import equivariance_tps_parameters
@@ -267,6 +272,8 @@ def evaluate(args):
             rec_ev.update(model.generated_act, torch.as_tensor(batch["view0"]).to(model.device, torch.float32), valid=valid)
         if use_ev is not None:
             use_ev.update(o["out_parts_soft"], o["out_parts_hard"], valid=valid)
+        if co_ev is not None:
+            co_ev.update(o["out_parts_hard"], valid=valid)
         for k in keys:
             outs[k].append((o[k].detach().float().cpu().numpy() if o[k].dtype.is_floating_point else o[k].cpu().numpy())[:valid])
         for k in ins:
@@ -280,7 +287,8 @@ def evaluate(args):
         pickle.dump(data, f)
     if metrics:
         vals = evalutil.validation_logs(rec_ev.result() if rec_ev is not None else None, use_ev.result() if use_ev is not None else None,
-                                        equiv=eq_ev.result() if eq_ev is not None else None)
+                                        equiv=eq_ev.result() if eq_ev is not None else None,
+                                        **({"coherence": co_ev.result()} if co_ev is not None else {}))
         with open(os.path.join(odir, "metrics.yml"), "w") as f:       # the `val/` names of Trainer.validate without the prefix
             yaml.safe_dump({k[len("val/"):]: (int(v) if isinstance(v, int) else float(v)) for k, v in vals.items()}, f)
     if gts:
@@ -398,8 +406,9 @@ SEGMENT_OUTPUTS = ("labels", "overlay", "confidence")
 
 
 def segment_options(cfg):
-    """The `segment_*` keys of a yaml, validated: {"csv", "size", "max_side", "outputs", "alpha"}, and with `segment_refine: bilateral`
-    also "refine": {"radius", "sigma"} (what ``export_segments`` takes).  ValueError on anything else."""
+    """The `segment_*` keys of a yaml, validated: {"csv", "size", "max_side", "outputs", "alpha"}, with `segment_refine: bilateral`
+    also "refine": {"radius", "sigma"}, and with `segment_clean_min_area` > 0 also "clean": {"min_area", "rounds", "connectivity"}
+    (what ``export_segments`` takes).  ValueError on anything else."""
     csv_path = cfg.get("segment_csv")
     if not csv_path:
         raise ValueError("--segment: `segment_csv` (one image path per line, relative to data_root) is required")
@@ -434,6 +443,18 @@ def segment_options(cfg):
         raise ValueError("segment_refine_sigma: a number > 0 (got {!r})".format(sigma))
     if mode == "bilateral":
         opt["refine"] = {"radius": int(radius), "sigma": float(sigma)}
+    # speck clean-up of the rendered labels: components of fewer than `segment_clean_min_area` output pixels (0 = off, the default)
+    min_area = cfg.get("segment_clean_min_area", 0)
+    if not isinstance(min_area, int) or isinstance(min_area, bool) or min_area < 0:
+        raise ValueError("segment_clean_min_area: an integer count of output pixels >= 0, 0 = off (got {!r})".format(min_area))
+    rounds = cfg.get("segment_clean_rounds", 1)
+    if not isinstance(rounds, int) or isinstance(rounds, bool) or not 1 <= rounds <= 4:
+        raise ValueError("segment_clean_rounds: an integer in 1 .. 4 (got {!r})".format(rounds))
+    conn = cfg.get("segment_clean_connectivity", 8)
+    if isinstance(conn, bool) or conn not in (4, 8):
+        raise ValueError("segment_clean_connectivity: 4 or 8 (got {!r})".format(conn))
+    if min_area > 0:
+        opt["clean"] = {"min_area": int(min_area), "rounds": int(rounds), "connectivity": int(conn)}
     return opt
 
 
@@ -471,6 +492,8 @@ def segment_files(model, cfg, root, step, profile=None):
     rule (bilinear, / 127.5 - 1) for the model and kept at its output size as uint8 for the overlay; passes of 2 * batch_size images
     go through ``TrainModel.export_segments`` (one pose pass and one ups_segment_render launch each) and the planes, copied into
     pinned buffers behind an event, are encoded by the bounded writer thread (it blocks, never drops, and is joined before return).
+    With `segment_clean_min_area` > 0 each pass also cleans specks out of its labels before the copies (``export_segments(clean=)``)
+    and one line logs how many pixels were relabelled in all; with the key at 0 the call is the one it was.
     A missing file raises FileNotFoundError before anything is computed: there is no synthetic fall-back on this route.
     profile: a dict that receives wall-clock seconds per phase (decode, model passes, packing and upload of the sources, kernel,
     copies, encode); the phases are then SYNCHRONISED so that the device time is attributed, which a normal run does not do.
@@ -480,7 +503,8 @@ def segment_files(model, cfg, root, step, profile=None):
     from . import imglog as IL
     from . import ops
     opt = segment_options(cfg)
-    refine = opt.get("refine")
+    refine, clean = opt.get("refine"), opt.get("clean")
+    relabelled = 0
     if refine is None:
         LOG.info("--segment: segment_refine = none: labels are the arg-max of the bilinearly resampled map")
     else:
@@ -526,7 +550,7 @@ def segment_files(model, cfg, root, step, profile=None):
             vt = torch.from_numpy(np.stack(views))
             if profile is None:
                 res = model.export_segments(vt, sizes, sources=sources or None, outputs=opt["outputs"], alpha=opt["alpha"], colors=palette,
-                                            refine=refine)
+                                            refine=refine, **({"clean": clean} if clean is not None else {}))
             else:                           # the phases apart: the pose pass, the kernel and the copies each behind a synchronisation
                 maps = model.segment_soft(vt)
                 t0 = lap("model", t0)
@@ -537,9 +561,11 @@ def segment_files(model, cfg, root, step, profile=None):
                 t0 = lap("upload", t0)
                 laps = []
                 res = model.export_segments(vt, sizes, sources=packed, outputs=opt["outputs"], alpha=opt["alpha"],
-                                            colors=palette, maps=maps, after_launch=lambda: laps.append(lap("kernel", t0)), refine=refine)
+                                            colors=palette, maps=maps, after_launch=lambda: laps.append(lap("kernel", t0)), refine=refine,
+                                            **({"clean": clean} if clean is not None else {}))
                 res["ready"].synchronize()
                 lap("copies", laps[0])
+            relabelled += res.get("relabelled", 0)
             images = OrderedDict()
             for i, rel in enumerate(chunk):
                 for kind in opt["outputs"]:
@@ -554,6 +580,9 @@ def segment_files(model, cfg, root, step, profile=None):
         writer.flush()
     finally:
         writer.close()
+    if clean is not None:
+        LOG.info("--segment: clean-up (min_area %d, up to %d round(s), connectivity %d) relabelled %d pixel(s)", clean["min_area"],
+                 clean["rounds"], clean["connectivity"], relabelled)
     for chunk, sizes, counts, ready in pending:
         ready.synchronize()
         for i, rel in enumerate(chunk):
