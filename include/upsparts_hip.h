@@ -663,6 +663,42 @@ int ups_label_components_clean(const void* labels, int32_t label_bytes, const in
                                int32_t* changed, const uint8_t* src, const uint8_t* colors, double alpha, uint8_t* overlay,
                                uint8_t* confidence, int32_t* counts, void* scratch, void* stream);
 
+/* ---------------------------------------------------------------- run-length annotations (csrc/segrle.hip)
+ * COCO run-length encoding of the label planes of the segmentation export, for every image and part at once.  Added by name, without
+ * a new UPS_ABI_VERSION, as the entries above.  Integer arithmetic only; these definitions are the specification (DESIGN.md section 8
+ * "Run-length annotations"; tests/segrle_ref.py restates them twice and the device results are equal).
+ *
+ * Inputs.  Planes, images and the table are ups_segment_render's (the same checks), with the limits of the components kernels:
+ *   n <= 65535 images, 1 <= h w <= 2^20 each, labels uint8 [total], 1 <= P <= 255.  A pixel with label >= P belongs to no part.
+ *   The alignment gaps between images are never read.
+ * Mask and order.  For image i (h x w at pixel offset off_i) and part p, in COCO's column-major order:
+ *   m[k] = (labels[off_i + y w + x] == p),  k = x h + y,  0 <= k < h w.
+ * Transitions.  T = the ascending positions k with m[k] != m[k-1], taking m[-1] = 0 (never the previous image's last pixel).
+ * Counts.  [T0, T1 - T0, .., h w - T_last], and [h w] when T is empty: COCO's uncompressed counts, alternating runs that begin with
+ *   a run of zeros (0 when m[0] = 1); |T| + 1 entries whose sum is h w.
+ * Outputs.
+ *   offsets int64 [n P + 1]   the exclusive prefix sum of the lists' lengths in (image, part) order; offsets[n P] is the total
+ *   counts  int32 [offsets[n P]]  the lists, concatenated in (image, part) order
+ *   area    int32 [n, P]      the pixels of the part: WRITTEN, not added (equal to ups_segment_render's counts)
+ *   bbox    int32 [n, P, 4]   (x_min, y_min, x_max - x_min + 1, y_max - y_min + 1); (0, 0, 0, 0) for a part without a pixel
+ *   Functions of the label plane alone: two launches give the same bytes.
+ * Two calls.  ups_segment_rle_count writes offsets, area and bbox and leaves per-chunk write positions in `scratch`
+ *   (ups_segment_rle_scratch_bytes(n, total, P) bytes, 8-byte aligned; a chunk is ups_segment_rle_chunk() = 1024 positions k).  The
+ *   caller reads the one int64 offsets[n P], allocates counts, and calls ups_segment_rle_write with the SAME labels, table, offsets
+ *   and scratch: n_counts is the offsets[n P] it read, capacity the int32 elements it allocated.  No block waits for another block:
+ *   positions come from a scan over separate launches, never from the order in which atomics land (area and bbox alone use integer
+ *   atomics).  The write kernel stores nothing at or beyond `capacity`, whatever offsets holds.
+ * UPS_E_UNSUPPORTED: P > 255.  UPS_E_ARG, nothing launched: a NULL required pointer, n outside 1 .. 65535, P < 1, h w > 2^20, a table
+ * ups_segment_render refuses, offsets or scratch not 8-byte aligned, counts, area or bbox not 4-byte aligned, n_counts < 1 or
+ * capacity < n_counts. */
+int32_t ups_segment_rle_chunk(void);
+size_t ups_segment_rle_scratch_bytes(int32_t n, int64_t total, int32_t P);
+int ups_segment_rle_count(const uint8_t* labels, int32_t n, const int32_t* table_host, const int32_t* table, int64_t total, int32_t P,
+                          int64_t* offsets, int32_t* area, int32_t* bbox, void* scratch, void* stream);
+int ups_segment_rle_write(const uint8_t* labels, int32_t n, const int32_t* table_host, const int32_t* table, int64_t total, int32_t P,
+                          const int64_t* offsets, const void* scratch, int32_t* counts, int64_t capacity, int64_t n_counts,
+                          void* stream);
+
 /* ---------------------------------------------------------------- part-appearance index (csrc/partindex.hip)
  * Nearest neighbours and k-means on a bank of per-part appearance codes (TrainModel.encode_parts): what deepfashion/code/eval/eval_02's
  * make_clusters does off-line with scikit-learn.  Restated in NumPy float64 by tests/partindex_ref.py with equal bits.

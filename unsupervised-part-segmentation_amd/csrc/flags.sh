@@ -2,7 +2,7 @@
 # an A/B library differs from the shipped one by exactly what its command line says.
 HIPCC=${HIPCC:-/opt/rocm/bin/hipcc}
 UPS_FLAGS="--offload-arch=gfx950 -O3 -fPIC -std=c++17 -Wno-unused-value -Wno-inline-asm"
-UPS_SOURCES="conv_igemm conv3x3_patch conv3x3_first conv3x3_s2 deconv3x3_s2 conv3x3_rows conv_wgrad conv_wgrad3x3 conv_wgrad3x3_f8 conv_aux pointwise partpath priors latent_adam critic gram canvas dataset augment evalparts valmetrics segexport components partindex landmarks tps equivariance stepguard ema"
+UPS_SOURCES="conv_igemm conv3x3_patch conv3x3_first conv3x3_s2 deconv3x3_s2 conv3x3_rows conv_wgrad conv_wgrad3x3 conv_wgrad3x3_f8 conv_aux pointwise partpath priors latent_adam critic gram canvas dataset augment evalparts valmetrics segexport segrle components partindex landmarks tps equivariance stepguard ema"
 # per-file flags.  EVERY translation unit is compiled WITHOUT packed fp32 VALU instructions: rule 1 of conv3x3_rows.hip's header
 # (docs/design/rows_hazard.md: the one wrong result this tree has measured from correct code was a v_pk_add_f32 beside a sibling
 # wave's MFMA section), extended to the whole library as insurance because it costs nothing -- in the MFMA files hipcc's packed forms

@@ -183,6 +183,10 @@ _SIGS = {
     "ups_segment_render": ([_P, _I, _I, _I, C.POINTER(_I), _P, _L, _P, _P, C.c_double, _P, _P, _P, _P, _P], C.c_int),
     "ups_segment_guide": ([_P, _I, _I, C.POINTER(_I), _P, _L, _P, _P], C.c_int),
     "ups_segment_render_guided": ([_P, _I, _I, _I, C.POINTER(_I), _P, _L, _P, _P, _P, _I, _P, C.c_double, _P, _P, _P, _P, _P], C.c_int),
+    "ups_segment_rle_chunk": ([], _I),
+    "ups_segment_rle_scratch_bytes": ([_I, _L, _I], _Z),
+    "ups_segment_rle_count": ([_P, _I, C.POINTER(_I), _P, _L, _I, _P, _P, _P, _P, _P], C.c_int),
+    "ups_segment_rle_write": ([_P, _I, C.POINTER(_I), _P, _L, _I, _P, _P, _P, _L, _L, _P], C.c_int),
     "ups_components_tile": ([], _I),
     "ups_label_components_scratch_bytes": ([_L], _Z),
     "ups_label_component_stats_scratch_bytes": ([_L], _Z),

@@ -241,7 +241,7 @@ class TrainModel(object):
 
     @torch.no_grad()
     def export_segments(self, views, sizes, sources=None, outputs=("labels", "overlay"), alpha=0.5, colors=None, maps=None,
-                        after_launch=None, refine=None, clean=None):
+                        after_launch=None, refine=None, clean=None, rle=False):
         """Part maps of `views` [n,S,S,3] rendered at their own sizes: one ``segment_soft`` and ONE ups_segment_render launch
         (``ops.segment_render``: label = first maximal part of the bilinearly resampled soft map, decided in fp64).
         sizes [(h_i, w_i)]; sources: None or n uint8 [h_i,w_i,3] images the overlay blends with (weight 1 - alpha);
@@ -255,12 +255,15 @@ class TrainModel(object):
         labels plane, in place: a component of fewer than A pixels takes the label its edge neighbours vote for; overlay, confidence
         (0 at a relabelled pixel) and the counts follow.  One int32 is read per round (it ends the rounds when nothing changed);
         "relabelled" in the result is the number of pixels that changed.
+        rle: True also run-length encodes the FINAL labels (after refinement and clean-up) with ``ops.segment_rle`` -- one more int64
+        read -- and `host` gains "rle_offsets" int64 [n P + 1], "rle_counts" int32, "area" int32 [n,P] and "bbox" int32 [n,P,4], copied
+        on the same side stream behind the same event (``ops.rle_lists`` splits them); `outputs` may then be empty.
         The per-part pixel counts are always taken.  The planes are copied into pinned host buffers on a side stream behind an event
         (as the image logs' canvases): nothing here waits for the device.  Returns {"table", "total", "host": {name: pinned
         tensor, "counts" included}, "views": {name: [per-image host views]}, "ready": the copies' event, "soft", "hard": the device
         maps of ``segment_soft``}: read the host buffers after ``ready.synchronize()``."""
         outputs = tuple(outputs)
-        if not outputs or any(k not in ("labels", "overlay", "confidence") for k in outputs):
+        if (not outputs and not rle) or any(k not in ("labels", "overlay", "confidence") for k in outputs):
             raise L.UpsError("export_segments: outputs is a non-empty subset of labels / overlay / confidence (got {})".format(outputs))
         dev = self.device
         hard, soft = self.segment_soft(views) if maps is None else maps
@@ -272,9 +275,13 @@ class TrainModel(object):
             if src is not None and not torch.is_tensor(src):    # the clean-up blends from the packed sources too: packed once, here
                 table, total = ops.segment_table(sizes)
                 src = ops.segment_pack_sources(src, table, total).to(dev, non_blocking=True)
-            want = want if "labels" in want else want + ("labels",)
+        if (clean is not None or rle) and "labels" not in want:
+            want = want + ("labels",)
         res = ops.segment_render(soft, sizes, src=src, colors=colors, alpha=alpha, want=want, refine=refine)
         relabelled = self._clean_segments(res, src, colors, alpha, clean) if clean is not None else 0
+        if rle:
+            enc = ops.segment_rle(res["labels"], self.n_parts, table=(res["table"], res["table_dev"], res["total"]))
+            res.update(rle_offsets=enc["offsets"], rle_counts=enc["counts"], area=enc["area"], bbox=enc["bbox"])
         if after_launch is not None:
             after_launch()
         if self._seg_stream is None:
@@ -283,7 +290,7 @@ class TrainModel(object):
         side.wait_stream(main)
         host = OrderedDict()
         with torch.cuda.stream(side):
-            for k in outputs + ("counts",):
+            for k in outputs + ("counts",) + (("rle_offsets", "rle_counts", "area", "bbox") if rle else ()):
                 res[k].record_stream(side)
                 host[k] = torch.empty(res[k].shape, dtype=res[k].dtype, pin_memory=True)
                 host[k].copy_(res[k], non_blocking=True)

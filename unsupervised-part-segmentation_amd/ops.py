@@ -2448,6 +2448,52 @@ def label_components_clean(labels, comp, area, P, min_area, sizes=None, out=None
     return lay.shaped(out), changed
 
 
+# --------------------------------------------------------------------------- run-length annotations (csrc/segrle.hip)
+SEGMENT_RLE_CHUNK = 1024        # positions k of one chunk of ups_segment_rle_* (checked against the library on first use)
+
+
+def segment_rle(labels, P, sizes=None, table=None):
+    """COCO run-length encoding of every (image, part) mask of a label plane (ups_segment_rle_count, one read of the total, then
+    ups_segment_rle_write; the definitions: include/upsparts_hip.h "run-length annotations", restated by tests/segrle_ref.py).
+    labels: uint8 on the device -- the packed plane [total] of a ``segment_render`` result with table=(table, table_dev, total) (or
+    `sizes`, laid out by segment_table), or a regular batch [N,h,w].  A label >= P belongs to no part.
+    Returns {"offsets" int64 [n P + 1], "counts" int32 [offsets[n P]], "area" int32 [n,P], "bbox" int32 [n,P,4] (x, y, w, h)} on the
+    device: list (i, p) is counts[offsets[i P + p] : offsets[i P + p + 1]], uncompressed counts in column-major order.  Reads one
+    int64 between the two launches (it sizes `counts`): synchronises with the current stream."""
+    fn = "segment_rle"
+    if isinstance(P, bool) or not isinstance(P, int) or not 1 <= P <= COMPONENTS_MAX_P:
+        raise L.UpsError("{}: P is an integer in 1 .. {} (got {!r})".format(fn, COMPONENTS_MAX_P, P))
+    _library_constants("segment_rle", segment_rle_chunk=SEGMENT_RLE_CHUNK)
+    lay = _ComponentsLayout(fn, labels, sizes, table)
+    lab = lay.plane("labels", labels, torch.uint8)
+    n, th, td, total = lay.args()
+    dev = lay.device
+    offsets = torch.empty(n * P + 1, dtype=torch.int64, device=dev)
+    area = torch.empty((n, P), dtype=torch.int32, device=dev)
+    bbox = torch.empty((n, P, 4), dtype=torch.int32, device=dev)
+    scratch = _scratch(L.load().ups_segment_rle_scratch_bytes(n, total, P), dev)
+    L.call("ups_segment_rle_count", L.ptr(lab), n, th, td, total, P, L.ptr(offsets), L.ptr(area), L.ptr(bbox), L.ptr(scratch),
+           L.stream())
+    n_counts = int(offsets[n * P].item())               # the one read: it sizes the lists
+    counts = torch.empty(n_counts, dtype=torch.int32, device=dev)
+    L.call("ups_segment_rle_write", L.ptr(lab), n, th, td, total, P, L.ptr(offsets), L.ptr(scratch), L.ptr(counts), n_counts, n_counts,
+           L.stream())
+    return {"offsets": offsets, "counts": counts, "area": area, "bbox": bbox}
+
+
+def rle_lists(offsets, counts, n, P):
+    """Host copies of segment_rle's offsets and counts (tensors or arrays) -> [[counts of (i, p) as a list of int] * P] * n."""
+    import numpy as np
+    off = np.asarray(offsets.cpu() if torch.is_tensor(offsets) else offsets, dtype=np.int64).reshape(-1)
+    cnt = np.asarray(counts.cpu() if torch.is_tensor(counts) else counts).reshape(-1)
+    if off.size != n * P + 1 or off[0] != 0 or np.any(np.diff(off) < 1) or off[-1] != cnt.size:
+        raise L.UpsError("rle_lists: offsets [{}] ascending from 0 to len(counts) = {} expected (got [{}], {} .. {})".format(
+            n * P + 1, cnt.size, off.size, off[0] if off.size else None, off[-1] if off.size else None))
+    flat = cnt.tolist()
+    o = off.tolist()
+    return [[flat[o[i * P + p]:o[i * P + p + 1]] for p in range(P)] for i in range(n)]
+
+
 # --------------------------------------------------------------------------- training image logs (csrc/canvas.hip): uint8 canvases
 def canvas_grid(n, cols=None):
     """(rows, cols) of tf_batch_to_canvas for n tiles (re-derived, UNVERIFIED): cols=None -> the square grid of side ceil(sqrt(n)),

@@ -18,7 +18,8 @@ call per block of ``data.TransferData``, the cells pickled to <root>/comparison_
 MatrixHook's key set (its plotting script reads the file) and drawn by ``evalutil.write_transfer_matrix``.
 
 ``--segment <yaml> -c <ckpt>`` has no counterpart in the reference: the images listed in ``segment_csv`` are segmented and their part
-maps written as PNG files at the resolution of the source photographs (``segment``).
+maps written as PNG files at the resolution of the source photographs, and on request as one COCO annotation file with run-length
+masks encoded on the device (``segment``).
 
 ``--index <yaml> -c <ckpt>`` is the work-alike of deepfashion/code/eval/eval_02's ``make_clusters`` and more: the part-appearance codes of
 the images in ``index_csv``, their per-part nearest neighbours and k-means clusters (``index``; ``partindex.py``).
@@ -407,8 +408,9 @@ SEGMENT_OUTPUTS = ("labels", "overlay", "confidence")
 
 def segment_options(cfg):
     """The `segment_*` keys of a yaml, validated: {"csv", "size", "max_side", "outputs", "alpha"}, with `segment_refine: bilateral`
-    also "refine": {"radius", "sigma"}, and with `segment_clean_min_area` > 0 also "clean": {"min_area", "rounds", "connectivity"}
-    (what ``export_segments`` takes).  ValueError on anything else."""
+    also "refine": {"radius", "sigma"}, with `segment_clean_min_area` > 0 also "clean": {"min_area", "rounds", "connectivity"}
+    (what ``export_segments`` takes), and with `segment_annotations: coco` also "annotations": {"min_area", "path"} (path None: the
+    default, <root>/segment/<global_step>/annotations.json); `segment_outputs` may be empty only then.  ValueError on anything else."""
     csv_path = cfg.get("segment_csv")
     if not csv_path:
         raise ValueError("--segment: `segment_csv` (one image path per line, relative to data_root) is required")
@@ -426,8 +428,13 @@ def segment_options(cfg):
     if isinstance(outputs, str):
         outputs = [outputs]
     outputs = tuple(outputs)
-    if not outputs or len(set(outputs)) != len(outputs) or any(k not in SEGMENT_OUTPUTS for k in outputs):
-        raise ValueError("segment_outputs: a non-empty list of distinct names of {} (got {!r})".format(SEGMENT_OUTPUTS, list(outputs)))
+    annotations = cfg.get("segment_annotations", "none")
+    if not isinstance(annotations, str) or annotations not in ("none", "coco"):
+        raise ValueError("segment_annotations: none | coco (got {!r})".format(annotations))
+    if ((not outputs and annotations != "coco") or len(set(outputs)) != len(outputs)
+            or any(k not in SEGMENT_OUTPUTS for k in outputs)):
+        raise ValueError("segment_outputs: a non-empty list of distinct names of {} -- empty only with segment_annotations: coco "
+                         "(got {!r})".format(SEGMENT_OUTPUTS, list(outputs)))
     alpha = cfg.get("segment_alpha", 0.5)
     if isinstance(alpha, bool) or not isinstance(alpha, (int, float)) or not 0.0 <= float(alpha) <= 1.0:
         raise ValueError("segment_alpha: a number in [0, 1] (got {!r})".format(alpha))
@@ -455,6 +462,15 @@ def segment_options(cfg):
         raise ValueError("segment_clean_connectivity: 4 or 8 (got {!r})".format(conn))
     if min_area > 0:
         opt["clean"] = {"min_area": int(min_area), "rounds": int(rounds), "connectivity": int(conn)}
+    # COCO annotations of the final labels: one record per image and part of at least `segment_annotation_min_area` pixels
+    ann_area = cfg.get("segment_annotation_min_area", 1)
+    if not isinstance(ann_area, int) or isinstance(ann_area, bool) or ann_area < 0:
+        raise ValueError("segment_annotation_min_area: an integer count of output pixels >= 0 (got {!r})".format(ann_area))
+    ann_path = cfg.get("segment_annotation_path")
+    if ann_path is not None and (not isinstance(ann_path, str) or not ann_path):
+        raise ValueError("segment_annotation_path: a file path (got {!r})".format(ann_path))
+    if annotations == "coco":
+        opt["annotations"] = {"min_area": int(ann_area), "path": ann_path}
     return opt
 
 
@@ -487,6 +503,43 @@ def write_segment_index(path, rows, n_parts):
             wr.writerow([rel, h, w] + [repr(int(c) / float(h * w)) for c in counts])
 
 
+def coco_annotations(images, masks, palette, min_area=1):
+    """The dict of annotations.json (COCO's layout, uncompressed run-length masks), keys in a fixed order.
+    images: [(file_name, h, w)] in csv order; masks: per image the P tuples (counts list, area, (x, y, w, h)) of its parts, as
+    ``ops.segment_rle`` gives them; palette [P,3]: the export's colours.  Image ids are 1-based in csv order, category p + 1 is
+    part p, annotation ids are 1-based in (image, part) order over the parts of at least `min_area` pixels."""
+    P = len(palette)
+    doc = OrderedDict()
+    doc["images"] = [OrderedDict((("id", i + 1), ("file_name", name), ("height", int(h)), ("width", int(w))))
+                     for i, (name, h, w) in enumerate(images)]
+    doc["categories"] = [OrderedDict((("id", p + 1), ("name", "part_{}".format(p)), ("color", [int(c) for c in palette[p]])))
+                         for p in range(P)]
+    anns = []
+    for i, ((name, h, w), parts) in enumerate(zip(images, masks)):
+        if len(parts) != P:
+            raise ValueError("coco_annotations: {} masks for {} parts (image {})".format(len(parts), P, name))
+        for p, (counts, area, bbox) in enumerate(parts):
+            if int(area) < min_area:
+                continue
+            anns.append(OrderedDict((
+                ("id", len(anns) + 1), ("image_id", i + 1), ("category_id", p + 1),
+                ("segmentation", OrderedDict((("size", [int(h), int(w)]), ("counts", [int(c) for c in counts])))),
+                ("area", int(area)), ("bbox", [int(v) for v in bbox]), ("iscrowd", 1))))
+    doc["annotations"] = anns
+    return doc
+
+
+def write_coco_annotations(path, images, masks, palette, min_area=1):
+    """annotations.json with the standard library's json: fixed key order and separators, so two runs write the same bytes."""
+    import json
+    doc = coco_annotations(images, masks, palette, min_area)
+    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+    with open(path, "w") as f:
+        json.dump(doc, f, separators=(",", ":"))
+        f.write("\n")
+    return doc
+
+
 def segment_files(model, cfg, root, step, profile=None):
     """The export itself: every image of `segment_csv` is decoded ONCE with PIL, resized to S x S by the dataset's preprocess_image
     rule (bilinear, / 127.5 - 1) for the model and kept at its output size as uint8 for the overlay; passes of 2 * batch_size images
@@ -494,6 +547,9 @@ def segment_files(model, cfg, root, step, profile=None):
     pinned buffers behind an event, are encoded by the bounded writer thread (it blocks, never drops, and is joined before return).
     With `segment_clean_min_area` > 0 each pass also cleans specks out of its labels before the copies (``export_segments(clean=)``)
     and one line logs how many pixels were relabelled in all; with the key at 0 the call is the one it was.
+    With `segment_annotations: coco` each pass also run-length encodes its final labels on the device (``export_segments(rle=True)``)
+    and annotations.json is written after the last pass; with `segment_outputs: []` nothing is handed to the writer thread, which
+    is then never started, and no PNG directory appears.  index.csv is written either way.
     A missing file raises FileNotFoundError before anything is computed: there is no synthetic fall-back on this route.
     profile: a dict that receives wall-clock seconds per phase (decode, model passes, packing and upload of the sources, kernel,
     copies, encode); the phases are then SYNCHRONISED so that the device time is attributed, which a normal run does not do.
@@ -503,7 +559,8 @@ def segment_files(model, cfg, root, step, profile=None):
     from . import imglog as IL
     from . import ops
     opt = segment_options(cfg)
-    refine, clean = opt.get("refine"), opt.get("clean")
+    refine, clean, ann = opt.get("refine"), opt.get("clean"), opt.get("annotations")
+    extra = dict(({"clean": clean} if clean is not None else {}), **({"rle": True} if ann is not None else {}))
     relabelled = 0
     if refine is None:
         LOG.info("--segment: segment_refine = none: labels are the arg-max of the bilinearly resampled map")
@@ -519,7 +576,7 @@ def segment_files(model, cfg, root, step, profile=None):
         if not os.path.isfile(os.path.join(data_root, rel)):
             raise FileNotFoundError("--segment: {} (listed in {}) does not exist".format(os.path.join(data_root, rel), opt["csv"]))
     palette = IL.mask_color_bytes(IL.mask_colors01(model.n_parts))
-    writer = IL.ImageWriter(root, path_fn=segment_png_path)
+    writer = IL.ImageWriter(root, path_fn=segment_png_path) if opt["outputs"] else None
     rows, pending, warned = [], [], False
     t = dict.fromkeys(("decode", "model", "upload", "kernel", "copies", "encode"), 0.0)
     dev = model.device
@@ -550,7 +607,7 @@ def segment_files(model, cfg, root, step, profile=None):
             vt = torch.from_numpy(np.stack(views))
             if profile is None:
                 res = model.export_segments(vt, sizes, sources=sources or None, outputs=opt["outputs"], alpha=opt["alpha"], colors=palette,
-                                            refine=refine, **({"clean": clean} if clean is not None else {}))
+                                            refine=refine, **extra)
             else:                           # the phases apart: the pose pass, the kernel and the copies each behind a synchronisation
                 maps = model.segment_soft(vt)
                 t0 = lap("model", t0)
@@ -562,7 +619,7 @@ def segment_files(model, cfg, root, step, profile=None):
                 laps = []
                 res = model.export_segments(vt, sizes, sources=packed, outputs=opt["outputs"], alpha=opt["alpha"],
                                             colors=palette, maps=maps, after_launch=lambda: laps.append(lap("kernel", t0)), refine=refine,
-                                            **({"clean": clean} if clean is not None else {}))
+                                            **extra)
                 res["ready"].synchronize()
                 lap("copies", laps[0])
             relabelled += res.get("relabelled", 0)
@@ -571,25 +628,40 @@ def segment_files(model, cfg, root, step, profile=None):
                 for kind in opt["outputs"]:
                     v = res["views"][kind][i]
                     images[(kind, rel)] = IL.Paletted(v, palette) if kind == "labels" else v
-            writer.submit(step, images, res["ready"])
-            pending.append((chunk, sizes, res["host"]["counts"], res["ready"]))       # (the planes live on in the writer's queue only)
-            if profile is not None:         # encoded here and now, not beside the next pass
+            if writer is not None:
+                writer.submit(step, images, res["ready"])
+            rle = {k: res["host"][k] for k in ("rle_offsets", "rle_counts", "area", "bbox")} if ann is not None else None
+            pending.append((chunk, sizes, res["host"]["counts"], res["ready"], rle))  # (the planes live on in the writer's queue only)
+            if profile is not None and writer is not None:      # encoded here and now, not beside the next pass
                 t0 = time.perf_counter()
                 writer.flush()
                 t["encode"] += time.perf_counter() - t0
-        writer.flush()
+        if writer is not None:
+            writer.flush()
     finally:
-        writer.close()
+        if writer is not None:
+            writer.close()
     if clean is not None:
         LOG.info("--segment: clean-up (min_area %d, up to %d round(s), connectivity %d) relabelled %d pixel(s)", clean["min_area"],
                  clean["rounds"], clean["connectivity"], relabelled)
-    for chunk, sizes, counts, ready in pending:
+    masks = []
+    t0 = time.perf_counter()
+    for chunk, sizes, counts, ready, rle in pending:
         ready.synchronize()
         for i, rel in enumerate(chunk):
             rows.append((rel, sizes[i][0], sizes[i][1], [int(c) for c in counts[i].tolist()]))
+        if rle is not None:
+            lists = ops.rle_lists(rle["rle_offsets"], rle["rle_counts"], len(chunk), model.n_parts)
+            area, bbox = rle["area"].tolist(), rle["bbox"].tolist()
+            masks.extend([(lists[i][p], area[i][p], bbox[i][p]) for p in range(model.n_parts)] for i in range(len(chunk)))
     odir = os.path.join(root, "segment", str(step))
     os.makedirs(odir, exist_ok=True)
     write_segment_index(os.path.join(odir, "index.csv"), rows, model.n_parts)
+    if ann is not None:
+        path = ann["path"] or os.path.join(odir, "annotations.json")
+        doc = write_coco_annotations(path, [(rel, h, w) for rel, h, w, _ in rows], masks, palette.tolist(), ann["min_area"])
+        LOG.info("--segment: %d annotation(s) of %d image(s) written to %s", len(doc["annotations"]), len(rows), path)
+        t["annotations"] = time.perf_counter() - t0
     if profile is not None:
         profile.update(t)
     return rows
@@ -597,7 +669,8 @@ def segment_files(model, cfg, root, step, profile=None):
 
 def segment(args):
     """``--segment``: see ``segment_files``.  Outputs: <root>/segment/<global_step>/{labels,overlay,confidence}/<relative path>.png
-    (labels: a palette PNG whose bytes are the part ids) and index.csv.  Returns {"rows", "root", "dir", "model"}."""
+    (labels: a palette PNG whose bytes are the part ids) and index.csv; with `segment_annotations: coco` also annotations.json (COCO
+    records with uncompressed run-length masks, one per image and part).  Returns {"rows", "root", "dir", "model"}."""
     cfg = load_config(args.segment)
     for kv in args.set:
         k, v = kv.split("=", 1)
